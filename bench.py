@@ -19,6 +19,8 @@ eager launches at N > 1) -> the graph is released -> a separate eager pass of 2 
 kernel family is bracketed by HIP events on the launch stream (`roofline`, `profile_pass`; not part of `value`) -> `secondary` (BASELINE's
 second metric, contrastive pairs/s, from a short run of the configs[3] step, and its inter-video bank mode) -> `cpu_baseline` (the CPU
 oracle timed on this host, N = 1 only).  `value_normalised` = `value` referred to a box whose MFMA probe reads bench.py's CAL_REF.
+`--dump-outputs DIR` writes, right after the timed steps, what the last of them computed (loss, logits, model state, gradients;
+large arrays as a fixed seeded sample) as DIR/<name>.npy: the inputs are seeded, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -67,7 +69,46 @@ def parse():
                     help="seg (default, BASELINE configs[1]) or contrast (configs[3]: ConsistencyLoss pre-training step)")
     ap.add_argument("--graph", type=int, default=-1, help="1: capture the whole step in a hipGraph and replay it (a training mode: "
                     "stswincl_amd/graph.py); 0: eager; -1 (default): graph when N == 1")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (loss, logits, model state, gradients) as "
+                         "DIR/<name>.npy, float32; arrays above 4 M elements as a fixed seeded sample (rank 0; at most 64 MB in all)")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
+
+
+DUMP_MAX_ELEMS = 1 << 22        # per dumped array: 4 M float32 = 16 MB, so the four arrays of a step stay under 64 MB
+
+
+def step_outputs(model, **extra):
+    """What a caller of the training step holds after it: `extra` (loss, logits), the model's floating state (parameters and
+    running statistics, flattened in state-dict order) and the parameters' gradients (flattened in parameter order; zeros where
+    a parameter has none)."""
+    state = torch.cat([v.detach().float().reshape(-1) for v in model.state_dict().values() if v.is_floating_point()])
+    grads = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().float().reshape(-1) for p in model.parameters()])
+    return {**extra, "state": state, "grads": grads}
+
+
+def dump_outputs(out_dir, arrays):
+    """Write {name: tensor} as out_dir/<name>.npy (float32; float64 stays float64).  An array of more than DUMP_MAX_ELEMS elements is
+    replaced by a fixed sample of its flattened values (numpy default_rng(0) over its element count, sorted), so that two builds run
+    with the same arguments write files that compare element for element.  -> {name: shape, dtype, sampled element count or None}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    info = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        n = t.numel()
+        sampled = n > DUMP_MAX_ELEMS
+        v = t
+        if sampled:
+            idx = np.sort(np.random.default_rng(0).choice(n, DUMP_MAX_ELEMS, replace=False))
+            v = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        arr = v.to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+        info[name] = {"shape": list(t.shape), "dtype": str(t.dtype).replace("torch.", ""), "sampled": DUMP_MAX_ELEMS if sampled else None}
+    return info
 
 
 def physical_cores():
@@ -285,7 +326,7 @@ def calibration_block(cal, value):
     return cal, value * scale
 
 
-def contrast_run(a, ctx, steps, warmup, profile_stride, batch=8, bank="sample", eager=False):
+def contrast_run(a, ctx, steps, warmup, profile_stride, batch=8, bank="sample", eager=False, dump_dir=None):
     """BASELINE.json configs[3] as far as the reference can run it: ConsistencyLoss (PixPro-style, 2 query + 6 momentum-key
     encoder passes) at 256x256 (224 is illegal for the window sizes), B clips/GPU, LARS over SGD-momentum as in
     main_pretrain_swinv5.py:37-47.  Reports contrastive pairs/s = 2 directions x B x HW x 5 HW per step."""
@@ -326,6 +367,7 @@ def contrast_run(a, ctx, steps, warmup, profile_stride, batch=8, bank="sample", 
         step = capture(eager_step, lambda: opt.zero_grad(set_to_none=True), [opt])
         warmup = max(0, warmup - 2)            # (the capture helper ran two real steps)
     dt, _, loss = timed_steps(ctx, step, steps, warmup, 0)          # the headline region: no event brackets
+    dumped = dump_outputs(dump_dir, step_outputs(model, loss=loss)) if dump_dir and rank == 0 else None
     prof = {}
     if profile_stride:                         # separate bracketed eager pass: the similarity kernel's live roofline figures
         if graphed:                            # (drop the graph's memory pool first: see seg_run)
@@ -352,6 +394,8 @@ def contrast_run(a, ctx, steps, warmup, profile_stride, batch=8, bank="sample", 
                       "input_frames_per_s": world * 6 * B * 4 * steps / dt, "loss": float(loss.detach()),
                       "launch": "hipGraph replay of the whole step (device-resident optimizer / EMA scalars: a training mode)" if graphed else "eager launches"},
            "dist": ctx.dist_info(reducer)}
+    if dumped is not None:
+        res["dumped_outputs"] = {"dir": dump_dir, "arrays": dumped}
     for name in ("contrast_fwd_bf16", "contrast_bank_fwd_bf16"):
         if name in prof:
             q = prof[name]
@@ -391,12 +435,15 @@ def seg_run(a, ctx):
     torch.manual_seed(1234 + rank)            # each rank owns different clips (weak scaling)
     x = torch.randn(B, 4, 3, S, S, device=dev)
     y = torch.randint(0, 12, (B, S, S), device=dev)
+    last = {}          # --dump-outputs: the step's logits (under graph replay: the captured buffer that every replay rewrites)
 
     def eager_step():
         opt.zero_grad(set_to_none=True)
         with torch.autocast("cuda", dtype=torch.bfloat16):
             out = model(x)
             loss = crit(out, y)
+        if a.dump_outputs:
+            last["logits"] = out
         loss.backward()
         if reducer is not None:
             reducer.finish()
@@ -432,6 +479,10 @@ def seg_run(a, ctx):
             cal["matmul_probe_error"] = f"{type(e).__name__}: {e}"[:200]
     # headline: exactly K steps, NO event brackets, graph replay when N == 1 (two more untimed steps re-warm the caches behind the probes)
     dt, _, loss = timed_steps(ctx, step, a.steps, 2 if cal is not None else 0, 0)
+    dumped = None
+    if a.dump_outputs and rank == 0:       # before the roofline pass: its eager steps would move the weights on
+        dumped = dump_outputs(a.dump_outputs, step_outputs(model, loss=loss, logits=last["logits"]))
+    last.clear()
     # roofline pass: the same step, eager, rank 0's launches bracketed by HIP events (one launch in `stride` per family, rotating, so that
     # 2 x stride steps time every launch site twice); NOT part of `value`
     prof, prof_steps, dt_prof = {}, 0, None
@@ -466,6 +517,8 @@ def seg_run(a, ctx):
     }
     if cal is not None:
         res["calibration"], res["value_normalised"] = calibration_block(cal, frames / dt)
+    if dumped is not None:
+        res["dumped_outputs"] = {"dir": a.dump_outputs, "arrays": dumped}
     if dt_prof is not None:
         res["profile_pass"] = {"steps": prof_steps, "ms_per_step": 1e3 * dt_prof / prof_steps, "launch": "eager launches, one launch in "
                                f"{profile_stride} per kernel family bracketed by HIP events (the source of `roofline`; not part of `value`)"}
@@ -562,7 +615,7 @@ def main():
     hip.load()
     if a.workload == "contrast":
         res = contrast_run(a, ctx, a.steps, a.warmup, 0 if a.no_profile else a.profile_stride, batch=(a.batch if a.batch != 4 else 8),
-                           bank=a.bank)
+                           bank=a.bank, dump_dir=a.dump_outputs)
     else:
         res = seg_run(a, ctx)
         if not a.no_secondary:
