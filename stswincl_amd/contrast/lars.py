@@ -16,7 +16,7 @@ from __future__ import annotations
 import torch
 
 from .. import hip
-from ..optim import _mark_updated, group_clock
+from ..optim import LrClocks, _mark_updated, load_in_place
 
 __all__ = ["LARS", "add_weight_decay"]
 
@@ -41,6 +41,7 @@ class LARS:
         self.optim = optimizer
         self.eps = eps
         self.trust_coef = trust_coef
+        self._lr = LrClocks()             # (its own: the wrapped optimizer may be torch.optim.SGD)
 
     def __getstate__(self):
         return (self.optim, {"eps": self.eps, "trust_coef": self.trust_coef})
@@ -48,6 +49,7 @@ class LARS:
     def __setstate__(self, state):
         self.optim, d = state
         self.eps, self.trust_coef = d["eps"], d["trust_coef"]
+        self._lr = LrClocks()
 
     def __repr__(self):
         return "%s(%r)" % (self.__class__.__name__, self.optim)
@@ -61,18 +63,13 @@ class LARS:
         return self.optim.state
 
     def state_dict(self):
-        sd = self.optim.state_dict()
-        sd["param_groups"] = [{k: v for k, v in g.items() if k != "_clock"} for g in sd["param_groups"]]
-        return sd
+        return self.optim.state_dict()
 
     def push_hyper(self):
-        """Before a hipGraph replay of the step: the groups' current learning rates -> device (stswincl_amd.graph.GraphedStep)."""
-        for group in self.optim.param_groups:
-            if group.get("_clock") is not None:
-                group["_clock"].push_lr(group["lr"])
+        self._lr.push(self.optim.param_groups)
 
     def load_state_dict(self, state_dict):
-        self.optim.load_state_dict(state_dict)
+        load_in_place(self.optim, state_dict, self)
 
     def zero_grad(self, set_to_none=True):
         self.optim.zero_grad(set_to_none=set_to_none)
@@ -86,7 +83,7 @@ class LARS:
         if closure is not None:                    # (torch.optim re-enables grad for the closure: it runs forward + backward)
             with torch.enable_grad():
                 loss = closure()
-        for group in self.optim.param_groups:
+        for gi, group in enumerate(self.optim.param_groups):
             if group.get("dampening", 0) != 0 or group.get("nesterov", False) or group.get("maximize", False):
                 raise hip.StswinHipError("fused LARS wraps plain SGD-momentum (dampening 0, nesterov off)")
             momentum = float(group.get("momentum", 0.0))
@@ -113,6 +110,6 @@ class LARS:
                     # (the learning rate travels through device memory: a hipGraph replay of the step sees the scheduler's current value)
                     hip.multi_tensor_lars(ps, gs, ms, None, lr=float(group["lr"]), momentum=momentum,
                                           wd=wd, trust_coef=self.trust_coef, eps=self.eps, first=is_first, adaptive=adaptive,
-                                          hyper=group_clock(group, ps[0].device).hyper)
+                                          hyper=self._lr.hyper(gi, group["lr"], ps[0].device))
             _mark_updated(touched)
         return loss

@@ -343,19 +343,18 @@ class PixPro(nn.Module):
 
     @property
     def k(self) -> int:
-        """Key-encoder updates done so far (PixPro_swin_v5.py:246,262).  Once the schedule lives on the device this is its host mirror:
-        exact in eager loops; after hipGraph replays of the step call `sync_k()` (one device read) before relying on it."""
+        """Key-encoder updates done so far (PixPro_swin_v5.py:246,262).  Once the schedule lives on the device this is its host mirror
+        (optim._Clock.step): exact after eager steps and hipGraph replays alike."""
         return self._ema.k if self._ema is not None else self._k
 
     @k.setter
     def k(self, value) -> None:
         self._k = int(value)
-        self._ema = None                   # re-made from _k at the next update
+        if self._ema is not None:
+            self._ema.clock.load(self._k)      # in place: a captured step keeps ticking this counter
 
     def sync_k(self) -> int:
-        if self._ema is not None:
-            self._k = self._ema.sync()
-        return self._k
+        return self.k
 
     @torch.no_grad()
     def _momentum_update_key_encoder(self):
@@ -371,8 +370,6 @@ class PixPro(nn.Module):
                 ks.append(pk)                              # the parameter itself: ema_update bumps its version counter
         if self._ema is None or self._ema.clock.counter.device != ks[0].device or self._ema.K != float(self.K) \
                 or self._ema.m0 != float(self.pixpro_momentum):
-            if torch.cuda.is_current_stream_capturing():
-                raise hip.StswinHipError("PixPro: first key-encoder update inside a hipGraph capture; run one eager step first")
             self._ema = EmaSchedule(ks[0].device, self.pixpro_momentum, self.K, self._k)
         ema_update(ks, qs, 0.0, hyper=self._ema.tick())
 

@@ -5,8 +5,13 @@ Every kernel of libstswin_hip is launched on the caller's stream with caller-own
 scalars baked into kernel arguments: Adam's step count / bias corrections, the learning rate of SGD / LARS, the key-encoder momentum
 schedule of the contrastive stage.  They now live in device memory (stswincl_amd.optim._Clock / EmaSchedule, csrc/optim.hip
 stswin_optim_tick): counters advance inside the graph, and values the HOST changes between steps (a scheduler's learning rate) are
-handed over by a stream-ordered fill in front of the replay (`push_hyper`).  N replays == N eager steps, bit for bit
-(tests/test_hip_graph_training.py).
+handed over by a stream-ordered fill in front of the replay (`push_hyper`; a learning rate changed INSIDE the capture raises, since
+its fill would be captured and freeze the rate).  N replays == N eager steps, bit for bit (tests/test_hip_graph_training.py).
+
+stswincl_amd.optim owns that state.  The capture (also one that raises) and every replay move its replay generation, and each host
+mirror - the `step` counts of state_dict(), PixPro.k - is re-read from its device counter at its first read after that.
+load_state_dict of FusedAdam / FusedSGD / LARS and `PixPro.k = v` write into the tensors and counters the graph holds, so replays
+after a resume continue like eager steps after it; a load that cannot be written in place raises once the optimizer is captured.
 
     step = GraphedStep(step_fn, [opt], zero_grad=lambda: opt.zero_grad(set_to_none=True))
     for batch in loader:
@@ -22,7 +27,7 @@ from typing import Callable, Iterable, Optional
 
 import torch
 
-from . import hip
+from . import hip, optim
 
 
 class GraphedStep:
@@ -52,12 +57,12 @@ class GraphedStep:
             zero_grad()
         hip.note_capture()
         self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
-            self.loss = step_fn()
-        # the capture ran the host side of one step without executing it: host mirrors of device counters are one ahead until re-read
-        for o in self.optimizers:
-            if hasattr(o, "_replayed"):
-                o._replayed = True
+        try:
+            with torch.cuda.graph(self.graph):
+                self.loss = step_fn()
+            optim.note_captured(self.optimizers)
+        finally:                  # the capture ran the host side of one step without executing it, also when it raised
+            optim.bump_generation()
 
     def __call__(self) -> torch.Tensor:
         if self.before_step is not None:
@@ -67,5 +72,6 @@ class GraphedStep:
             if push is not None:
                 push()
         self.graph.replay()
+        optim.bump_generation()
         self.steps_run += 1
         return self.loss

@@ -9,6 +9,7 @@
 from __future__ import annotations
 
 import math
+import weakref
 from typing import Iterable, Sequence
 
 import torch
@@ -36,36 +37,136 @@ def _mark_updated(params: Sequence[torch.Tensor]) -> None:
         ops.repack(params)
 
 
+_generation = 0            # replay generation: moves when device counters advanced without the host side of the step (graph.GraphedStep)
+_CAPTURED = weakref.WeakSet()     # optimizers a GraphedStep captured: their state tensors and clocks are operands of a live graph
+
+
+def bump_generation() -> None:
+    """A captured step ran on the device, or a capture ran its host side without executing it: every host mirror of a device
+    counter (_Clock.step, hence EmaSchedule.k / PixPro.k and FusedAdam's per-parameter `step`) is re-read at its next read."""
+    global _generation
+    _generation += 1
+
+
+def note_captured(optimizers) -> None:
+    """(graph.GraphedStep) these optimizers are captured: a load_state_dict that cannot be written in place raises from now on."""
+    _CAPTURED.update(optimizers)
+
+
+def _refuse_in_capture(what: str, advice: str) -> None:
+    if torch.cuda.is_current_stream_capturing():
+        raise hip.StswinHipError(f"{what} inside a hipGraph capture: {advice}")
+
+
 class _Clock:
-    """Device-resident step state shared by the parameters of one Adam launch group: `counter` int32 [1] (steps taken) and `hyper`
-    fp32 [4] = {lr, 1 - b1^t, sqrt(1 - b2^t), -} (csrc/optim.hip, stswin_optim_tick).  The update kernels read their step-dependent
-    scalars from `hyper`, so a hipGraph replay of the step advances the bias corrections exactly like eager steps do; the host
-    mirror `step` is what state_dict() reports and is re-read from the device after replays (sync())."""
+    """Device-resident step state: `counter` int32 [1] (steps taken) and `hyper` fp32 [4] = {lr, 1 - b1^t, sqrt(1 - b2^t), EMA
+    momentum} (csrc/optim.hip, stswin_optim_tick).  The update kernels read their step-dependent scalars from `hyper`, so a hipGraph
+    replay of the step advances them exactly like eager steps do.  `step` is the host mirror of the counter: exact after eager steps,
+    re-read from the device at its first read after the replay generation moved."""
 
     def __init__(self, device, step: int = 0):
+        _refuse_in_capture("a new device step clock (a parameter's first gradient, the first key-encoder update, a new parameter group)",
+                           "run the step eagerly once before capturing it")
         self.counter = torch.full((1,), int(step), dtype=torch.int32, device=device)
         self.hyper = torch.zeros(4, dtype=torch.float32, device=device)
-        self.step = int(step)
+        self._step, self._gen = int(step), _generation
         self.lr = None                       # the value hyper[0] holds
         self.members = []                    # optimizer state dicts of the parameters that took the last step on this clock
 
+    @property
+    def step(self) -> int:
+        return self._step if self._gen == _generation else self.sync()
+
+    def sync(self) -> int:
+        """Host mirror <- device counter (one device read)."""
+        _refuse_in_capture("a host step mirror that graph replays left stale is read", "read it before the capture")
+        self._step, self._gen = int(self.counter.item()), _generation
+        return self._step
+
+    def tick(self, kind: int, a: float, b: float) -> None:
+        hip.optim_tick(kind, self.counter, self.hyper, a, b)
+        if self._gen == _generation:         # (a stale mirror stays stale: its next read sees this tick on the device)
+            self._step += 1
+
+    def load(self, step: int) -> None:
+        """Re-seed the counter in place (a captured graph keeps ticking this one); hyper is re-derived from it at the next tick."""
+        _refuse_in_capture("a device step clock is re-seeded", "load before the capture or between replays")
+        self.counter.fill_(int(step))
+        self._step, self._gen = int(step), _generation
+
     def push_lr(self, lr: float) -> None:
         """Stream-ordered fill of hyper[0] when the host's learning rate differs from what the device holds (schedulers); a no-op
-        otherwise - in particular inside a capture whose warm-up steps already ran with this rate."""
+        otherwise.  Inside a capture the fill would become a graph node that overwrites every later push: refused."""
         lr = float(lr)
         if self.lr != lr:
+            _refuse_in_capture(f"learning rate changed ({self.lr} -> {lr})", "change it in before_step, outside the captured step")
             self.hyper[0:1].fill_(lr)
             self.lr = lr
 
-    def sync(self) -> int:
-        self.step = int(self.counter.item())
-        return self.step
+
+class LrClocks:
+    """The device-resident learning rate of each parameter group of an SGD-like optimizer (lr is its only step-dependent scalar),
+    by group POSITION: torch's load_state_dict replaces the group dicts, while a captured graph keeps reading these clocks."""
+
+    def __init__(self):
+        self.clocks = {}
+
+    def hyper(self, i: int, lr: float, device) -> torch.Tensor:
+        c = self.clocks.get(i)
+        if c is None or c.hyper.device != device:
+            c = self.clocks[i] = _Clock(device)
+        c.push_lr(lr)
+        return c.hyper
+
+    def push(self, param_groups) -> None:
+        """Before a graph replay: the groups' current learning rates -> device (graph.GraphedStep)."""
+        for i, c in self.clocks.items():
+            c.push_lr(param_groups[i]["lr"])
+
+
+def load_in_place(opt, state_dict, owner) -> None:
+    """torch's Optimizer.load_state_dict on `opt`, then the loaded values written INTO the state tensors and Adam clocks `opt` held
+    before - a captured graph keeps their addresses, so replays after the load continue like eager steps after it.  A load that
+    cannot be written so (another shape / dtype / device, no loaded tensor for one the graph reads, parameters of one clock loading
+    different counts) raises when `owner` (opt or its wrapper) was captured, and leaves `opt` as it was; otherwise it keeps torch's
+    new objects and the clocks are re-made at the next step."""
+    old_state, old_groups = opt.state, opt.param_groups
+    torch.optim.Optimizer.load_state_dict(opt, state_dict)
+    copies, clocks, bad = [], {}, None
+    for p, old in old_state.items():
+        new = opt.state.get(p, {})
+        for key, o in old.items():
+            v = new.get(key)
+            if key == "_clock":
+                if old.get("step") == o.step:           # (one that sat the clock's last step out is not on it any more)
+                    clocks.setdefault(id(o), (o, []))[1].append(new)
+            elif torch.is_tensor(o):
+                if torch.is_tensor(v) and v.shape == o.shape and v.dtype == o.dtype and v.device == o.device:
+                    copies.append((new, key, o, v))
+                else:
+                    bad = f"state '{key}' of a parameter loads as {None if v is None else (tuple(v.shape), v.dtype, v.device)}"
+    for c, sts in clocks.values():
+        if bad is None and len({int(st.get("step", -1)) for st in sts}) != 1:
+            bad = "parameters that share a device clock load different step counts"
+    if bad is not None:
+        if owner in _CAPTURED:
+            opt.state, opt.param_groups = old_state, old_groups
+            raise hip.StswinHipError(f"load_state_dict after a hipGraph capture cannot be written into what the graph reads: {bad}")
+        return
+    for new, key, o, v in copies:
+        o.copy_(v)
+        new[key] = o
+    for c, sts in clocks.values():
+        c.load(int(sts[0]["step"]))
+        c.members = sts
+        for st in sts:
+            st["step"], st["_clock"] = c.step, c
 
 
 class FusedAdam(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
-        self._replayed = False
+        self._gen = _generation
         self._clock_groups = []
 
     def _clocks(self):
@@ -78,17 +179,17 @@ class FusedAdam(torch.optim.Optimizer):
 
     def push_hyper(self) -> None:
         """Before a graph replay: hand the groups' current learning rates to the device (stswincl_amd.graph.GraphedStep calls this)."""
-        self._replayed = True
-        for clock, group in self._clock_groups:         # (clock, group) pairs of the last step() - the one that was captured
-            clock.push_lr(group["lr"])
+        for clock, i in self._clock_groups:              # (clock, group position) pairs of the last step() - the one that was captured
+            clock.push_lr(self.param_groups[i]["lr"])
 
     def sync_steps(self) -> None:
-        """Host step counts <- device counters (after graph replays the host mirrors are stale)."""
-        for c in self._clocks():
-            c.sync()
-            for st in c.members:            # (a parameter that shares the clock but sat the captured step out keeps its own count)
-                st["step"] = c.step
-        self._replayed = False
+        """Host step counts <- device counters: a device read only at the first call after the replay generation moved
+        (step() and state_dict() call it)."""
+        if self._gen != _generation:
+            for c in self._clocks():
+                for st in c.members:        # (a parameter that shares the clock but sat the last step out keeps its own count)
+                    st["step"] = c.step
+            self._gen = _generation
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -96,11 +197,9 @@ class FusedAdam(torch.optim.Optimizer):
         if closure is not None:                    # (torch.optim re-enables grad for the closure: it runs forward + backward)
             with torch.enable_grad():
                 loss = closure()
-        capturing = torch.cuda.is_current_stream_capturing()
-        if self._replayed and not capturing:       # eager steps after graph replays: the host mirrors first
-            self.sync_steps()
+        self.sync_steps()
         self._clock_groups = []
-        for group in self.param_groups:
+        for gi, group in enumerate(self.param_groups):
             b1, b2 = group["betas"]
             by_clock = {}         # torch.optim.Adam keeps the step count PER PARAMETER (bias corrections differ when a branch
             touched = []          # had no gradient on some steps, or a parameter was unfrozen later): one launch per count.
@@ -119,9 +218,6 @@ class FusedAdam(torch.optim.Optimizer):
                 if clock is not None and clock.step != st["step"]:
                     clock = None                             # it sat out steps the clock's other parameters took: its own count, its own clock
                 if clock is None:                            # first gradient (or a loaded state): join the clock of this count
-                    if capturing:
-                        raise hip.StswinHipError("FusedAdam: a parameter got its first gradient inside a hipGraph capture; run the "
-                                                 "step eagerly once before capturing it")
                     key = (st["step"], p.device)
                     clock = fresh.get(key)
                     if clock is None:
@@ -136,10 +232,9 @@ class FusedAdam(torch.optim.Optimizer):
                 vs.append(st["exp_avg_sq"])
                 sts.append(st)
             for clock, ps, gs, ms, vs, sts in by_clock.values():
-                self._clock_groups.append((clock, group))
+                self._clock_groups.append((clock, gi))
                 clock.push_lr(group["lr"])
-                hip.optim_tick(0, clock.counter, clock.hyper, float(b1), float(b2))
-                clock.step += 1
+                clock.tick(0, float(b1), float(b2))
                 clock.members = sts
                 for st in sts:
                     st["step"] = clock.step
@@ -149,44 +244,31 @@ class FusedAdam(torch.optim.Optimizer):
 
     def state_dict(self):
         """(the device clocks stay out of the checkpoint: `step` per parameter is what torch.optim.Adam writes, too)"""
-        if self._replayed:
-            self.sync_steps()
+        self.sync_steps()
         sd = super().state_dict()
         sd["state"] = {k: {kk: vv for kk, vv in v.items() if kk != "_clock"} for k, v in sd["state"].items()}
         return sd
 
     def load_state_dict(self, state_dict):
         """torch.optim.Adam checkpoints keep `step` as a (possibly GPU) tensor per parameter; the counts become Python ints here -
-        once, outside any hipGraph capture - and the device clocks are re-made from them at the next step()."""
-        super().load_state_dict(state_dict)
+        once, outside any hipGraph capture.  The loaded state is written into the existing tensors and clocks (load_in_place)."""
+        self.sync_steps()
+        load_in_place(self, state_dict, self)
         for st in self.state.values():
-            st.pop("_clock", None)
             if "step" in st and not isinstance(st["step"], int):
                 st["step"] = int(st["step"])
-
-
-def group_clock(group, device) -> _Clock:
-    """The device-resident learning rate of a parameter group (SGD / LARS: lr is their only step-dependent scalar)."""
-    c = group.get("_clock")
-    if c is None or c.hyper.device != device:
-        c = group["_clock"] = _Clock(device)
-    c.push_lr(group["lr"])
-    return c
 
 
 class FusedSGD(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, momentum=0.0, weight_decay=0.0):
         super().__init__(params, dict(lr=lr, momentum=momentum, weight_decay=weight_decay))
+        self._lr = LrClocks()
 
     def push_hyper(self) -> None:
-        for group in self.param_groups:
-            if group.get("_clock") is not None:
-                group["_clock"].push_lr(group["lr"])
+        self._lr.push(self.param_groups)
 
-    def state_dict(self):
-        sd = super().state_dict()
-        sd["param_groups"] = [{k: v for k, v in g.items() if k != "_clock"} for g in sd["param_groups"]]
-        return sd
+    def load_state_dict(self, state_dict):
+        load_in_place(self, state_dict, self)
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -194,7 +276,7 @@ class FusedSGD(torch.optim.Optimizer):
         if closure is not None:                    # (torch.optim re-enables grad for the closure: it runs forward + backward)
             with torch.enable_grad():
                 loss = closure()
-        for group in self.param_groups:
+        for gi, group in enumerate(self.param_groups):
             first, later, touched = ([], [], []), ([], [], []), []
             for p in group["params"]:
                 if p.grad is None:
@@ -213,7 +295,7 @@ class FusedSGD(torch.optim.Optimizer):
             for (ps, gs, ms), c1 in ((first, 1.0), (later, 0.0)):
                 if ps:
                     hip.multi_tensor(1, ps, gs, ms, None, b1=group["momentum"], wd=group["weight_decay"], c1=c1,
-                                     hyper=group_clock(group, ps[0].device).hyper)
+                                     hyper=self._lr.hyper(gi, group["lr"], ps[0].device))
             _mark_updated(touched)
         return loss
 
@@ -230,15 +312,14 @@ def ema_update(keys: Sequence[torch.Tensor], queries: Sequence[torch.Tensor], mo
 class EmaSchedule:
     """The key-encoder momentum schedule of PixPro_swin_v5.py:258-262 - m = 1 - (1 - m0)(cos(pi k / K) + 1) / 2, k += 1 per update -
     with k and m in device memory (stswin_optim_tick kind 1), so that eager steps and hipGraph replays of the step walk the same
-    schedule.  `k` (host mirror) is re-read from the device by sync()."""
+    schedule.  `k` is the clock's host mirror (_Clock.step)."""
 
     def __init__(self, device, base_momentum: float, K: int, k: int = 0):
         self.clock = _Clock(device, k)
         self.m0, self.K = float(base_momentum), float(K)
 
     def tick(self) -> torch.Tensor:
-        hip.optim_tick(1, self.clock.counter, self.clock.hyper, self.m0, self.K)
-        self.clock.step += 1
+        self.clock.tick(1, self.m0, self.K)
         return self.clock.hyper
 
     @property

@@ -4,6 +4,7 @@ The step-dependent scalars (Adam's step count and bias corrections, the SGD / LA
 key-encoder momentum schedule of PixPro_swin_v5.py:258-262) live in device memory (stswincl_amd.optim._Clock / EmaSchedule, csrc/optim.hip
 stswin_optim_tick), so nothing of the optimizer's trajectory is frozen into kernel arguments at capture time.  Reference loops:
 seg18/train_swin.py:151-173 (Adam), pixcontrast_18/main_pretrain_swinv5.py:113-153 (LARS + per-iteration cosine learning rate)."""
+import copy
 import math
 import types
 
@@ -15,7 +16,8 @@ BF = torch.bfloat16
 STEPS = 20
 
 
-def _seg_run(graphed: bool):
+def _seg_run(graphed: bool, resume=None):
+    """resume=(n, l): opt.state_dict() is snapshot before step n and loaded again before step l (a resume; the model is not reloaded)."""
     from stswincl_amd.graph import GraphedStep
     from stswincl_amd.net.Ours.base18 import TswinPlus
     from stswincl_amd.optim import FusedAdam
@@ -47,15 +49,25 @@ def _seg_run(graphed: bool):
         for grp in opt.param_groups:
             grp["lr"] = lr_at(i)
 
+    snap = []
+
+    def reload(i):
+        if resume is not None and i == resume[0]:
+            snap.append(copy.deepcopy(opt.state_dict()))
+        if resume is not None and i == resume[1]:
+            opt.load_state_dict(snap[0])
+
     losses = []
     if not graphed:
         for i in range(STEPS):
+            reload(i)
             before(i)
             losses.append(float(step()))
     else:
         run = GraphedStep(step, [opt], zero_grad=lambda: opt.zero_grad(set_to_none=True), warmup=2, before_step=before)
         losses += [float(v) for v in run.warmup_losses]
         for i in range(2, STEPS):
+            reload(i)
             losses.append(float(run()))
     torch.cuda.synchronize()
     sd = opt.state_dict()
@@ -72,23 +84,29 @@ def test_adam_graph_replays_equal_eager_steps_bit_for_bit():
     assert all(torch.equal(a, b) for a, b in zip(be, bg))
 
 
-def _contrast_run(graphed: bool):
-    from stswincl_amd.contrast.lars import LARS, add_weight_decay
+def _contrast_model():
     from stswincl_amd.contrast.models.PixPro_swin_v5 import ConsistencyLoss
-    from stswincl_amd.graph import GraphedStep
-    from stswincl_amd.optim import FusedSGD
     S, B = 64, 2
     args = types.SimpleNamespace(pixpro_p=1.0, pixpro_momentum=0.99, pixpro_clamp_value=0.0, pixpro_transform_layer=1,
                                  pixpro_ins_loss_weight=0.0, pixpro_pos_ratio=0.7, data="endo18", tag="1", pretrainpth=None,
                                  num_instances=400, batch_size=B, epochs=1, start_epoch=1)          # K = 200 steps: the momentum moves visibly
     torch.manual_seed(0)
     model = ConsistencyLoss(args, input_resolution=(S // 8, S // 8)).cuda().train()
-    base_lr = 0.05
-    opt = LARS(FusedSGD(add_weight_decay(model.pixpro, 1e-5), lr=base_lr, momentum=0.9))
     g = torch.Generator().manual_seed(5)
     ims = [torch.randn(B, 4, 3, S, S, generator=g).cuda() for _ in range(6)]
     masks = [torch.randint(0, 12, (B, 1, S // 8, S // 8), generator=g).float().repeat_interleave(8, 2).repeat_interleave(8, 3).cuda()
              for _ in range(6)]
+    return model, ims, masks
+
+
+def _contrast_run(graphed: bool, resume=None):
+    """resume=(n, l): as in _seg_run, and model.pixpro.k is set back to its value at the snapshot."""
+    from stswincl_amd.contrast.lars import LARS, add_weight_decay
+    from stswincl_amd.graph import GraphedStep
+    from stswincl_amd.optim import FusedSGD
+    model, ims, masks = _contrast_model()
+    base_lr = 0.05
+    opt = LARS(FusedSGD(add_weight_decay(model.pixpro, 1e-5), lr=base_lr, momentum=0.9))
 
     def step():
         opt.zero_grad(set_to_none=True)
@@ -102,18 +120,30 @@ def _contrast_run(graphed: bool):
         for grp in opt.param_groups:
             grp["lr"] = base_lr * 0.5 * (1.0 + math.cos(math.pi * i / 50.0))
 
+    snap = []
+
+    def reload(i):
+        if resume is not None and i == resume[0]:
+            snap.append((copy.deepcopy(opt.state_dict()), model.pixpro.k))
+        if resume is not None and i == resume[1]:
+            opt.load_state_dict(snap[0][0])
+            model.pixpro.k = snap[0][1]
+
     losses = []
     if not graphed:
         for i in range(STEPS):
+            reload(i)
             set_lr(i)
             losses.append(float(step()))
     else:
         run = GraphedStep(step, [opt], zero_grad=lambda: opt.zero_grad(set_to_none=True), warmup=2, before_step=set_lr)
         losses += [float(v) for v in run.warmup_losses]
         for i in range(2, STEPS):
+            reload(i)
             losses.append(float(run()))
     torch.cuda.synchronize()
-    k = model.pixpro.sync_k()
+    k = model.pixpro.k                                 # (exact without sync_k(), which stays a public no-op read)
+    assert model.pixpro.sync_k() == k
     return [p.detach().clone() for p in model.parameters()], losses, k
 
 
@@ -123,6 +153,121 @@ def test_lars_and_momentum_schedule_graph_replays_equal_eager_steps_bit_for_bit(
     assert ke == kg == STEPS, (ke, kg)                 # the key-encoder schedule advanced once per step in both modes
     assert le == lg, (le, lg)
     assert all(torch.equal(a, b) for a, b in zip(pe, pg))      # query AND momentum-key parameters
+
+
+def test_adam_resume_under_graph_replay_equals_eager_resume_bit_for_bit():
+    """load_state_dict between replays writes into the exp_avg / exp_avg_sq tensors and the device clock the graph holds; the
+    host lr schedule keeps reaching the graph through the reloaded param groups."""
+    pe, le, se, be = _seg_run(False, resume=(6, 13))
+    pg, lg, sg, bg = _seg_run(True, resume=(6, 13))
+    assert se == sg == [6 + STEPS - 13], (se, sg)
+    assert le == lg, (le, lg)
+    assert all(torch.equal(a, b) for a, b in zip(pe, pg))
+
+
+def test_lars_and_key_encoder_resume_under_graph_replay_equals_eager_resume_bit_for_bit():
+    pe, le, ke = _contrast_run(False, resume=(6, 13))
+    pg, lg, kg = _contrast_run(True, resume=(6, 13))
+    assert ke == kg == 6 + STEPS - 13, (ke, kg)
+    assert le == lg, (le, lg)
+    assert all(torch.equal(a, b) for a, b in zip(pe, pg))
+
+
+def _small_seg():
+    from stswincl_amd.net.Ours.base18 import TswinPlus
+    from stswincl_amd.optim import FusedAdam
+    from stswincl_amd.utils.losses import OhemCELoss2D
+    S, B = 64, 2
+    torch.manual_seed(0)
+    model = TswinPlus(12, (S // 8, S // 8)).cuda().train()
+    opt = FusedAdam(model.parameters(), 1e-3)
+    crit = OhemCELoss2D(S * S // 16)
+    torch.manual_seed(1)
+    x, y = torch.randn(B, 4, 3, S, S, device="cuda"), torch.randint(0, 12, (B, S, S), device="cuda")
+
+    def step():
+        opt.zero_grad(set_to_none=True)
+        with torch.autocast("cuda", dtype=BF):
+            loss = crit(model(x), y)
+        loss.backward()
+        opt.step()
+        return loss
+
+    return model, opt, step
+
+
+def test_a_learning_rate_changed_inside_the_capture_raises():
+    """Its fill would be captured as a graph node that overwrites every later push: the learning rate would freeze."""
+    from stswincl_amd.graph import GraphedStep
+    from stswincl_amd.hip import StswinHipError
+    model, opt, step = _small_seg()
+
+    def step_fn():
+        if torch.cuda.is_current_stream_capturing():
+            for grp in opt.param_groups:
+                grp["lr"] = 5e-4
+        return step()
+
+    with pytest.raises(StswinHipError, match="learning rate"):
+        GraphedStep(step_fn, [opt], zero_grad=lambda: opt.zero_grad(set_to_none=True), warmup=2)
+
+
+def test_a_capture_that_raises_leaves_the_host_mirrors_on_the_device_counters():
+    """The host side of the aborted capture's step ran (Adam's step counts, PixPro.k one ahead), its kernels did not."""
+    from stswincl_amd.graph import GraphedStep
+    from stswincl_amd.optim import FusedAdam
+    res = []
+    for abort in (False, True):
+        model, ims, masks = _contrast_model()
+        opt = FusedAdam([p for p in model.parameters() if p.requires_grad], 1e-4)
+
+        def step():
+            opt.zero_grad(set_to_none=True)
+            with torch.autocast("cuda", dtype=BF):
+                loss = model(*ims, *masks)
+            loss.backward()
+            opt.step()
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("step_fn failed after opt.step()")
+            return loss
+
+        if abort:
+            with pytest.raises(RuntimeError, match="after opt.step"):
+                GraphedStep(step, [opt], zero_grad=lambda: opt.zero_grad(set_to_none=True), warmup=2)
+            torch.cuda.synchronize()
+            steps = sorted({int(v["step"]) for v in opt.state_dict()["state"].values()})
+            counters = sorted({int(c.counter.item()) for c in opt._clocks()})
+            assert steps == counters == [2], (steps, counters)
+            assert model.pixpro.k == int(model.pixpro._ema.clock.counter.item()) == 2
+        else:
+            step()
+            step()
+        step()                                         # eager from here on: like the eager reference's third step
+        torch.cuda.synchronize()
+        res.append(([p.detach().clone() for p in model.parameters()], model.pixpro.k,
+                    sorted({int(v["step"]) for v in opt.state_dict()["state"].values()})))
+    (pe, ke, se), (pa, ka, sa) = res
+    assert ke == ka == 3 and se == sa == [3], (ke, ka, se, sa)
+    assert all(torch.equal(a, b) for a, b in zip(pe, pa))
+
+
+def test_a_load_that_cannot_be_written_in_place_raises_after_a_capture_and_changes_nothing():
+    from stswincl_amd.graph import GraphedStep
+    from stswincl_amd.hip import StswinHipError
+    model, opt, step = _small_seg()
+    run = GraphedStep(step, [opt], zero_grad=lambda: opt.zero_grad(set_to_none=True), warmup=2)
+    run()
+    before = copy.deepcopy(opt.state_dict())
+    bad = copy.deepcopy(before)
+    first = next(iter(bad["state"]))
+    bad["state"][first]["step"] += 5                   # all parameters stepped together: they share one device clock
+    with pytest.raises(StswinHipError, match="different step counts"):
+        opt.load_state_dict(bad)
+    after = opt.state_dict()
+    assert after["param_groups"] == before["param_groups"] and after["state"].keys() == before["state"].keys()
+    for i, st in before["state"].items():
+        assert after["state"][i]["step"] == st["step"] == 3
+        assert all(torch.equal(after["state"][i][k], st[k]) for k in ("exp_avg", "exp_avg_sq"))
 
 
 def test_graphed_step_helper_runs_warmup_capture_and_replays():
