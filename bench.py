@@ -12,13 +12,16 @@ N > 1 without WORLD_SIZE in the environment: this process starts N ranks itself 
 --nproc-per-node N ... bench.py <same flags>`, BEFORE anything here touches the GPU) and exits with the child's code;
 under torch.distributed.run (WORLD_SIZE set) it is one rank of the job.
 
-Prints ONE JSON line on rank 0 (contract in the task statement).  Order of a run (round 6): W warm-up steps -> `calibration`
-probes (0.1 s: an MFMA loop on pseudo-random operands, a 1 GB copy) -> 2 more untimed steps -> EXACTLY K timed steps between barrier +
-synchronize, with NO event brackets inside (`value`; a hipGraph replay of the whole step at N = 1 - a training mode, stswincl_amd/graph.py -,
-eager launches at N > 1) -> the graph is released -> a separate eager pass of 2 x stride steps in which one launch in `stride` of every
-kernel family is bracketed by HIP events on the launch stream (`roofline`, `profile_pass`; not part of `value`) -> `secondary` (BASELINE's
-second metric, contrastive pairs/s, from a short run of the configs[3] step, and its inter-video bank mode) -> `cpu_baseline` (the CPU
-oracle timed on this host, N = 1 only).  `value_normalised` = `value` referred to a box whose MFMA probe reads bench.py's CAL_REF.
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run does what the headline needs and nothing else: W
+warm-up steps -> 2 more untimed steps -> EXACTLY K timed steps between barrier + synchronize, with NO event brackets inside (`value`,
+`ms_per_step`; a hipGraph replay of the whole step at N = 1 - a training mode, stswincl_amd/graph.py -, eager launches at N > 1) ->
+`--dump-outputs` -> the line.  `--full` adds the measurements that take runs of their own: `calibration` probes (0.1 s: an MFMA loop
+on pseudo-random operands, a 1 GB copy, a vendor matmul) between the warm-up and the 2 untimed steps; then, behind the timed steps and
+the dump, the graph is released -> a separate eager pass of 2 x stride steps in which one launch in `stride` of every kernel family is
+bracketed by HIP events on the launch stream (`roofline`, `profile_pass`; not part of `value`) -> `secondary` (BASELINE's second
+metric, contrastive pairs/s, from a short run of the configs[3] step, and its inter-video bank mode) -> `cpu_baseline` (the CPU oracle
+timed on this host, N = 1 only).  The --no-* switches drop single parts of a --full run.  Both kinds of run time and dump the same
+steps.  `value_normalised` = `value` referred to a box whose MFMA probe reads bench.py's CAL_REF.
 `--dump-outputs DIR` writes, right after the timed steps, what the last of them computed (loss, logits, model state, gradients;
 large arrays as a fixed seeded sample) as DIR/<name>.npy: the inputs are seeded, so two builds can be compared output for output.
 """
@@ -48,10 +51,14 @@ def parse():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=4, help="clips per GPU")
     ap.add_argument("--size", type=int, default=512)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: calibration probes, the bracketed roofline pass, the contrastive "
+                         "`secondary` and the CPU baseline (the --no-* switches below drop single parts of it)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-size", type=int, default=512)
-    ap.add_argument("--no-profile", action="store_true", help="skip the bracketed roofline pass behind the timed region")
-    ap.add_argument("--no-calibration", action="store_true", help="skip the 0.2 s box-calibration probes")
+    ap.add_argument("--no-profile", action="store_true", help="--full: skip the bracketed roofline pass behind the timed region")
+    ap.add_argument("--no-calibration", action="store_true",
+                    help="skip the 0.2 s box-calibration probes (--full) and the 2 untimed steps that follow them (every run)")
     ap.add_argument("--profile-stride", type=int, default=9,
                     help="bracket one launch in n of each kernel family (seeded random choice) with HIP events (1 = all; the "
                          "records cost host time)")
@@ -61,10 +68,10 @@ def parse():
     ap.add_argument("--comm-dtype", default="fp32", choices=["fp32", "bf16"],
                     help="N > 1: wire dtype of the gradient all-reduce buckets (bf16 halves the bytes on the xGMI links; the averaged "
                          "gradients are converted back to fp32 behind the collective)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the short contrastive run that fills `secondary`")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the short contrastive run that fills `secondary`")
     ap.add_argument("--secondary-steps", type=int, default=20)
     ap.add_argument("--dump-prof", default=None,
-                    help="write the per-span timing table here (with STSWIN_SHAPE_PROFILE=1: one row per GEMM shape)")
+                    help="--full: write the per-span timing table here (with STSWIN_SHAPE_PROFILE=1: one row per GEMM shape)")
     ap.add_argument("--workload", default="seg", choices=["seg", "contrast"],
                     help="seg (default, BASELINE configs[1]) or contrast (configs[3]: ConsistencyLoss pre-training step)")
     ap.add_argument("--graph", type=int, default=-1, help="1: capture the whole step in a hipGraph and replay it (a training mode: "
@@ -426,7 +433,7 @@ def seg_run(a, ctx):
                 t = p.data.cpu()
                 dist.broadcast(t, 0)
                 p.data.copy_(t)
-    profile_stride = 0 if a.no_profile else max(1, a.profile_stride)
+    profile_stride = max(1, a.profile_stride) if (a.full and not a.no_profile) else 0
     use_graph = a.graph == 1 or (a.graph == -1 and world == 1)
     opt = FusedAdam(model.parameters(), 1e-4)          # == torch.optim.Adam (tests/test_hip_optim.py), 8 launches per step
     crit = OhemCELoss2D(S * S // 16)
@@ -470,15 +477,18 @@ def seg_run(a, ctx):
     for _ in range(warm_left):
         step()
     ctx.barrier()
-    cal = hip.calibrate(dev) if not a.no_calibration else None      # every rank probes its own GPU at the same time; rank 0 reports
+    # two more untimed steps before the timed ones (behind the probes of a --full run they re-warm the caches); a plain run takes
+    # them too, so that both kinds of run time and dump the same steps
+    settle = 0 if a.no_calibration else 2
+    cal = hip.calibrate(dev) if (a.full and settle) else None      # every rank probes its own GPU at the same time; rank 0 reports
     if cal is not None:
         try:
             cal["matmul_bf16_tflops"] = matmul_probe(dev)
         except Exception as e:     # noqa: BLE001   (informational: a missing / failing vendor library must not cost the line)
             cal["matmul_bf16_tflops"] = None
             cal["matmul_probe_error"] = f"{type(e).__name__}: {e}"[:200]
-    # headline: exactly K steps, NO event brackets, graph replay when N == 1 (two more untimed steps re-warm the caches behind the probes)
-    dt, _, loss = timed_steps(ctx, step, a.steps, 2 if cal is not None else 0, 0)
+    # headline: exactly K steps, NO event brackets, graph replay when N == 1
+    dt, _, loss = timed_steps(ctx, step, a.steps, settle, 0)
     dumped = None
     if a.dump_outputs and rank == 0:       # before the roofline pass: its eager steps would move the weights on
         dumped = dump_outputs(a.dump_outputs, step_outputs(model, loss=loss, logits=last["logits"]))
@@ -614,11 +624,11 @@ def main():
     from stswincl_amd import hip
     hip.load()
     if a.workload == "contrast":
-        res = contrast_run(a, ctx, a.steps, a.warmup, 0 if a.no_profile else a.profile_stride, batch=(a.batch if a.batch != 4 else 8),
-                           bank=a.bank, dump_dir=a.dump_outputs)
+        res = contrast_run(a, ctx, a.steps, a.warmup, a.profile_stride if (a.full and not a.no_profile) else 0,
+                           batch=(a.batch if a.batch != 4 else 8), bank=a.bank, dump_dir=a.dump_outputs)
     else:
         res = seg_run(a, ctx)
-        if not a.no_secondary:
+        if a.full and not a.no_secondary:
             import gc
             gc.collect()
             torch.cuda.empty_cache()
@@ -645,7 +655,7 @@ def main():
                                             if "roofline" in secb else None}
             except Exception as e:     # noqa: BLE001
                 res["secondary"] = {"error": f"{type(e).__name__}: {e}"[:400]}
-        if ctx.world == 1 and not a.no_cpu_baseline and ctx.rank == 0:
+        if a.full and ctx.world == 1 and not a.no_cpu_baseline and ctx.rank == 0:
             res["cpu_baseline"] = cpu_baseline(a.cpu_size)
     if ctx.rank == 0:
         print(json.dumps(res), flush=True)

@@ -61,3 +61,34 @@ def test_bench_dump_outputs_are_the_last_timed_step_and_repeat(tmp_path):
         assert a.dtype == np.float32 and np.isfinite(a).all() and np.array_equal(a, b), name
     assert total <= 64 << 20
     assert float(np.load(os.path.join(dirs[0], "loss.npy"))) == lines[0]["config"]["loss"]
+
+
+FULL_ONLY = ("calibration", "value_normalised", "profile_pass", "roofline", "secondary", "cpu_baseline")
+
+
+@pytest.mark.gpu
+def test_plain_run_is_the_headline_of_a_full_run(tmp_path):
+    """A plain bench.py run prints the headline alone, and it times and dumps the same steps as a --full run of the same arguments:
+    the calibration probes before the timed steps and the bracketed pass behind them change nothing that is dumped."""
+    env = dict(os.environ)
+    env.pop("WORLD_SIZE", None)
+    args = ["--steps", "3", "--warmup", "3", "--batch", "2", "--size", "256"]
+    lines, dirs = {}, {}
+    for run, extra in (("plain", []), ("full", ["--full", "--no-cpu-baseline", "--no-secondary", "--profile-stride", "2"])):
+        dirs[run] = str(tmp_path / run)
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args + extra + ["--dump-outputs", dirs[run]],
+                             env=env, capture_output=True, text=True, timeout=900)
+        assert out.returncode == 0, out.stderr[-2000:]
+        stdout = [ln for ln in out.stdout.splitlines() if ln.strip()]
+        assert len(stdout) == 1, stdout                # ONE JSON line on stdout
+        lines[run] = json.loads(stdout[0])
+    plain, full = lines["plain"], lines["full"]
+    assert not set(FULL_ONLY) & set(plain), sorted(plain)
+    assert {"calibration", "value_normalised", "profile_pass", "roofline"} <= set(full), sorted(full)
+    for key in ("metric", "unit", "higher_is_better", "dtype", "steps", "warmup"):
+        assert plain[key] == full[key], key
+    assert plain["value"] > 0 and plain["ms_per_step"] > 0 and plain["config"]["launch"] == full["config"]["launch"]
+    assert plain["config"]["loss"] == full["config"]["loss"]
+    for name in ("loss", "logits", "state", "grads"):
+        a, b = (np.load(os.path.join(dirs[run], f"{name}.npy")) for run in ("plain", "full"))
+        assert np.array_equal(a, b), name

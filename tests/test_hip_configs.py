@@ -445,8 +445,9 @@ def test_bench_two_ranks_sharing_the_gpu_runs_the_data_parallel_path():
 
 
 def test_bench_line_carries_the_round6_blocks():
-    """bench.py's N = 1 line (small clips, few steps): graph-replayed headline, calibration block with the normalised value, a separate
-    bracketed pass for the roofline figures, and gemm_tn's sampled work close to its launches' (the cancelled-span accounting of round 6)."""
+    """bench.py --full's N = 1 line (small clips, few steps): graph-replayed headline, calibration block with the normalised value, a
+    separate bracketed pass for the roofline figures, and gemm_tn's sampled work close to its launches' (the cancelled-span accounting
+    of round 6)."""
     import json
     import subprocess
     import sys
@@ -454,7 +455,8 @@ def test_bench_line_carries_the_round6_blocks():
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None)
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "4", "--warmup", "3", "--batch", "2", "--size", "256",
-                          "--no-cpu-baseline", "--no-secondary", "--profile-stride", "2"], env=env, capture_output=True, text=True, timeout=900)
+                          "--full", "--no-cpu-baseline", "--no-secondary", "--profile-stride", "2"], env=env, capture_output=True, text=True,
+                         timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, lines                      # ONE JSON line on stdout

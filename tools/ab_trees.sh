@@ -5,7 +5,8 @@ OLD=$1; R=${2:-2}; shift 2
 for i in $(seq 1 $R); do
   for side in old new; do
     if [ $side = old ]; then D=$OLD; else D=.; fi
-    (cd $D && python3 bench.py --steps 15 --warmup 4 --no-cpu-baseline --no-secondary "$@" 2>/dev/null | grep '^{"metric"' | python3 -c "
+    # (--full for the roofline fraction; a tree from before that option measures everything by default)
+    (cd $D && python3 bench.py --steps 15 --warmup 4 $(grep -q '"--full"' bench.py && echo --full) --no-cpu-baseline --no-secondary "$@" 2>/dev/null | grep '^{"metric"' | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read()); r=d.get('roofline',{})
 print('$side', round(d['value'],1), 'frames/s', round(d['ms_per_step'],3), 'ms  gemm_nt frac', round(r.get('frac',0),4))")

@@ -27,9 +27,9 @@ ST=$(find /tmp/prof_kt -name "*kernel_stats.csv" | head -1)
 [ -n "$KT" ] && python3 tools/step_sequence.py "$KT" --no-list > $OUT/${TAG}_step_sequence_graph.txt 2>&1
 grep '^{"metric"' $OUT/bench_under_rocprof.log | tail -1 > $OUT/${TAG}_bench_line_under_rocprof.json
 # 2. clean bench line + per-shape table
-python3 bench.py --steps 20 --warmup 3 > $OUT/bench_clean.log 2>&1
+python3 bench.py --steps 20 --warmup 3 --full > $OUT/bench_clean.log 2>&1
 grep '^{"metric"' $OUT/bench_clean.log | tail -1 > $OUT/${TAG}_bench_line.json
-STSWIN_SHAPE_PROFILE=1 python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-secondary --profile-stride 1 --dump-prof $OUT/${TAG}_gemm_shapes_in_step.txt > $OUT/bench_shapes.log 2>&1
+STSWIN_SHAPE_PROFILE=1 python3 bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --no-secondary --profile-stride 1 --dump-prof $OUT/${TAG}_gemm_shapes_in_step.txt > $OUT/bench_shapes.log 2>&1
 # 3. PMC passes (each its own run)
 for C in FETCH_SIZE WRITE_SIZE; do
   rm -rf /tmp/prof_pmc_$C
@@ -40,15 +40,15 @@ for C in FETCH_SIZE WRITE_SIZE; do
 done
 [ -f /tmp/pmc_FETCH_SIZE.csv ] && [ -f /tmp/pmc_WRITE_SIZE.csv ] && python3 tools/pmc_dominant.py /tmp/pmc_FETCH_SIZE.csv /tmp/pmc_WRITE_SIZE.csv $OUT/${TAG}_pmc_dominant_kernel.json $COMMIT > $OUT/pmc_dominant.log 2>&1
 # 4. contrastive workload
-python3 bench.py --workload contrast --steps 6 --warmup 2 > $OUT/bench_contrast.log 2>&1
+python3 bench.py --workload contrast --steps 6 --warmup 2 --full > $OUT/bench_contrast.log 2>&1
 grep '^{"metric"' $OUT/bench_contrast.log | tail -1 > $OUT/${TAG}_bench_contrast_line.json
 rm -rf /tmp/prof_ktc
 rocprofv3 --output-format csv --kernel-trace --stats -d /tmp/prof_ktc -o kt -- python3 bench.py --workload contrast --steps 4 --warmup 2 --no-profile --graph 0 > $OUT/bench_contrast_under_rocprof.log 2>&1
 KTC=$(find /tmp/prof_ktc -name "*kernel_trace.csv" | head -1)
 [ -n "$KTC" ] && python3 tools/prof_summary.py "$KTC" --last-ms 120 --top 50 --gaps 15 > $OUT/${TAG}_contrast_steady_state_kernels.txt 2>&1
-python3 bench.py --workload contrast --bank batch --steps 6 --warmup 2 > $OUT/bench_contrast_bank.log 2>&1
+python3 bench.py --workload contrast --bank batch --steps 6 --warmup 2 --full > $OUT/bench_contrast_bank.log 2>&1
 grep '^{"metric"' $OUT/bench_contrast_bank.log | tail -1 > $OUT/${TAG}_bench_contrast_bank_line.json
-python3 bench.py --batch 8 --steps 8 --warmup 2 --no-cpu-baseline --no-secondary > $OUT/bench_b8.log 2>&1
+python3 bench.py --batch 8 --steps 8 --warmup 2 --full --no-cpu-baseline --no-secondary > $OUT/bench_b8.log 2>&1
 grep '^{"metric"' $OUT/bench_b8.log | tail -1 > $OUT/${TAG}_bench_batch8_line.json
 # 5. kernel micro-benchmarks
 python3 tools/bench_attn.py > $OUT/${TAG}_attention_kernels.txt 2>&1
