@@ -523,6 +523,26 @@ int stswin_pair_loss_bwd(const float* pos, const float* all, const float* cnt, c
 int stswin_upsample_argmax(int dtype, const void* logits, unsigned char* labels, const long* gt, int* counts, int frames,
                            int nc, int h, int w, int H, int W, void* stream);
 
+/* ---- video inference (stswincl_amd/video.py), the evaluation loop of seg18/test.py:147-175 over the clips of
+ * seg18/dataset/Endovis2018_new.py:109-127.
+ * stswin_frame_ingest: uint8 RGB frames in [n][Hs][Ws][3] (HWC) -> fp32 images out [n][3][H][W], the stem's input
+ * (Endovis2018_new.py:125-127 `Image.resize((W, H), Image.BILINEAR)`, then `astype(float) / 255.` and test.py:149 `.float()`).
+ * Bit-exact with Pillow's separable BILINEAR resampler: when Ws != W a horizontal pass writes the uint8 intermediate
+ * tmp [n][Hs][W][3] (caller-owned), then when Hs != H a vertical pass; per output index i the taps are [bounds[2i],
+ * bounds[2i] + bounds[2i+1]) with int32 weights coef[i][ksize] of 22 fraction bits, out = clip((2^21 + sum u * k) >> 22, 0, 255).
+ * The tables are the caller's (float64 on the host); a pass whose size is unchanged needs none.  lut[256] maps the byte
+ * to its fp32 value (float32(u / 255.)).  Integer arithmetic only.
+ * stswin_clip_assemble: clips [B][4][frame_elems] from a frame-feature ring [slots][frame_elems] and this step's fresh frame
+ * features [n_fresh][frame_elems] (the T = 4 frames of base18.py:86-89 computed once per frame): table (int32, device) holds B*4
+ * sources, >= 0 = ring slot, < 0 = fresh frame -1 - e, then n_store ring slots that fresh frames 0 .. n_store-1 are stored
+ * into (< 0 = not kept).  A source out of range yields zeros, a store out of range is skipped.  No slot may be both read and
+ * stored by one call.  frame_elems * sizeof(dtype) % 16 == 0. */
+int stswin_frame_ingest(const unsigned char* in, unsigned char* tmp, float* out, int n, int Hs, int Ws, int H, int W,
+                        const int* hbounds, const int* hcoef, int hksize, const int* vbounds, const int* vcoef, int vksize,
+                        const float* lut, void* stream);
+int stswin_clip_assemble(int dtype, void* ring, const void* fresh, void* clips, const int* table, int B, int n_store, int slots,
+                         int n_fresh, long frame_elems, void* stream);
+
 /* ---- f2: multi-tensor optimizer / EMA step, up to 48 fp32 tensors per launch (host arrays of device pointers).
  * mode 0 = torch.optim.Adam (seg18/train_swin.py:122; c1 = 1 - b1^t, c2 = sqrt(1 - b2^t)), 1 = torch.optim.SGD with
  * momentum b1 (train_CL_ft_mswin_sgd_minput.py:147-162; c1 != 0 marks the first step: buf = grad), 2 = EMA

@@ -1129,3 +1129,140 @@ extern "C" int stswin_linear_pack(int dtype, const float* w, void* fwd, void* tr
   STSWIN_CHECK_LAUNCH();
   return 0;
 }
+
+// ---------------------------------------------------------------------------------------------------
+// Video inference (stswincl_amd/video.py).
+//
+// Frame ingest: uint8 RGB frames [n][Hs][Ws][3] -> fp32 images [n][3][H][W], the per-frame transform of
+// seg18/dataset/Endovis2018_new.py:125-127 + seg18/test.py:149 (PIL resize BILINEAR, astype(float) / 255., .float()).
+// Pillow's resampler is separable: a horizontal pass (only when the width changes) into a uint8 intermediate, then a
+// vertical pass (only when the height changes).  Per output index: taps [xmin, xmin + n) with int32 weights of 22 fraction
+// bits (host tables, stswincl_amd/video.py), out = clip((2^21 + sum u * k) >> 22, 0, 255).  Integer arithmetic only: the
+// result is bit-exact with Pillow.  The value -> fp32 map is a 256-entry table (float32(u / 255.) of the reference).
+// ---------------------------------------------------------------------------------------------------
+DEVI int pil_clip8(int ss) {
+  ss >>= 22;
+  return ss < 0 ? 0 : (ss > 255 ? 255 : ss);
+}
+
+// one thread per output pixel (row, xx) of the horizontal pass, three channels
+__global__ __launch_bounds__(256) void ingest_hpass_kernel(const unsigned char* __restrict__ in, unsigned char* __restrict__ out,
+                                                            const int* __restrict__ bounds, const int* __restrict__ coef, int ksize,
+                                                            long rows, int Ws, int W) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= rows * W) return;
+  const long row = i / W;
+  const int xx = (int)(i - row * W);
+  const int xmin = bounds[2 * xx], nk = bounds[2 * xx + 1];
+  const int* k = coef + (long)xx * ksize;
+  const unsigned char* src = in + (row * Ws + xmin) * 3;
+  int s0 = 1 << 21, s1 = 1 << 21, s2 = 1 << 21;
+  for (int x = 0; x < nk; ++x) {
+    const int w = k[x];
+    s0 += (int)src[3 * x] * w;
+    s1 += (int)src[3 * x + 1] * w;
+    s2 += (int)src[3 * x + 2] * w;
+  }
+  unsigned char* dst = out + i * 3;
+  dst[0] = (unsigned char)pil_clip8(s0);
+  dst[1] = (unsigned char)pil_clip8(s1);
+  dst[2] = (unsigned char)pil_clip8(s2);
+}
+
+// one thread per output pixel (frame, yy, x): the vertical pass (bounds == NULL: the height is unchanged, no pass) + the table
+// conversion into three fp32 planes
+__global__ __launch_bounds__(256) void ingest_vpass_kernel(const unsigned char* __restrict__ in, float* __restrict__ out,
+                                                            const int* __restrict__ bounds, const int* __restrict__ coef, int ksize,
+                                                            const float* __restrict__ lut, int n, int Hs, int H, int W) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  const long plane = (long)H * W;
+  if (i >= (long)n * plane) return;
+  const int f = (int)(i / plane);
+  const long p = i - (long)f * plane;
+  const int yy = (int)(p / W), x = (int)(p - (long)yy * W);
+  const unsigned char* src = in + (long)f * Hs * W * 3;
+  int v0, v1, v2;
+  if (bounds == nullptr) {
+    const unsigned char* s = src + ((long)yy * W + x) * 3;
+    v0 = s[0]; v1 = s[1]; v2 = s[2];
+  } else {
+    const int ymin = bounds[2 * yy], nk = bounds[2 * yy + 1];
+    const int* k = coef + (long)yy * ksize;
+    int s0 = 1 << 21, s1 = 1 << 21, s2 = 1 << 21;
+    for (int y = 0; y < nk; ++y) {
+      const unsigned char* s = src + ((long)(ymin + y) * W + x) * 3;
+      const int w = k[y];
+      s0 += (int)s[0] * w;
+      s1 += (int)s[1] * w;
+      s2 += (int)s[2] * w;
+    }
+    v0 = pil_clip8(s0); v1 = pil_clip8(s1); v2 = pil_clip8(s2);
+  }
+  float* o = out + (long)f * 3 * plane + p;
+  o[0] = lut[v0];
+  o[plane] = lut[v1];
+  o[2 * plane] = lut[v2];
+}
+
+extern "C" int stswin_frame_ingest(const unsigned char* in, unsigned char* tmp, float* out, int n, int Hs, int Ws, int H, int W,
+                                   const int* hbounds, const int* hcoef, int hksize, const int* vbounds, const int* vcoef,
+                                   int vksize, const float* lut, void* stream) {
+  if (n <= 0 || Hs <= 0 || Ws <= 0 || H <= 0 || W <= 0) return -1801;
+  if (in == nullptr || out == nullptr || lut == nullptr) return -1802;
+  const bool hpass = Ws != W, vpass = Hs != H;
+  if (hpass && (tmp == nullptr || hbounds == nullptr || hcoef == nullptr || hksize <= 0)) return -1803;
+  if (vpass && (vbounds == nullptr || vcoef == nullptr || vksize <= 0)) return -1804;
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned char* vin = in;
+  if (hpass) {
+    const long total = (long)n * Hs * W;
+    hipLaunchKernelGGL(ingest_hpass_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, in, tmp, hbounds, hcoef, hksize,
+                       (long)n * Hs, Ws, W);
+    STSWIN_CHECK_LAUNCH();
+    vin = tmp;
+  }
+  const long total = (long)n * H * W;
+  hipLaunchKernelGGL(ingest_vpass_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, vin, out,
+                     vpass ? vbounds : nullptr, vcoef, vksize, lut, n, Hs, H, W);
+  STSWIN_CHECK_LAUNCH();
+  return 0;
+}
+
+// Clip assembly from a frame-feature ring: unit u < B*4 writes clip frame u (= clip u / 4, position u % 4) from
+// table[u] >= 0 -> ring slot table[u], table[u] < 0 -> fresh frame -1 - table[u]; unit B*4 + j stores fresh frame j into ring slot
+// table[B*4 + j] (< 0: not kept).  Entries out of range write zeros / store nothing.  The caller guarantees that no slot a launch
+// reads is one it stores into.  grid (pieces / 1024 rounded up, units), 16-byte pieces.
+__global__ __launch_bounds__(256) void clip_assemble_kernel(uint4* ring, const uint4* fresh, uint4* clips, const int* table, int units,
+                                                             int clip_units, int slots, int n_fresh, long pieces) {
+  const int u = blockIdx.y;
+  const int e = table[u];
+  const uint4* src;
+  uint4* dst;
+  if (u < clip_units) {
+    dst = clips + (long)u * pieces;
+    src = e >= 0 ? (e < slots ? ring + (long)e * pieces : nullptr) : (-1 - e < n_fresh ? fresh + (long)(-1 - e) * pieces : nullptr);
+  } else {
+    const int j = u - clip_units;
+    if (e < 0 || e >= slots || j >= n_fresh) return;
+    dst = ring + (long)e * pieces;
+    src = fresh + (long)j * pieces;
+  }
+  for (long c = (long)blockIdx.x * 256 + threadIdx.x; c < pieces; c += (long)gridDim.x * 256)
+    dst[c] = src != nullptr ? src[c] : make_uint4(0u, 0u, 0u, 0u);
+}
+
+extern "C" int stswin_clip_assemble(int dtype, void* ring, const void* fresh, void* clips, const int* table, int B, int n_store,
+                                    int slots, int n_fresh, long frame_elems, void* stream) {
+  if (B < 0 || n_store < 0 || B + n_store == 0 || slots < 0 || n_fresh < 0 || frame_elems <= 0) return -1805;
+  const long bytes = frame_elems * (dtype == 0 ? 2 : 4);
+  if (bytes % 16) return -1806;
+  if (table == nullptr || (B > 0 && clips == nullptr) || (slots > 0 && ring == nullptr) || (n_fresh > 0 && fresh == nullptr))
+    return -1807;
+  const long pieces = bytes / 16;
+  const int units = B * 4 + n_store;
+  const long gx = (pieces + 1023) / 1024;
+  hipLaunchKernelGGL(clip_assemble_kernel, dim3((unsigned)(gx < 64 ? gx : 64), (unsigned)units), dim3(256), 0, (hipStream_t)stream,
+                     (uint4*)ring, (const uint4*)fresh, (uint4*)clips, table, units, B * 4, slots, n_fresh, pieces);
+  STSWIN_CHECK_LAUNCH();
+  return 0;
+}

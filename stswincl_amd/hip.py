@@ -584,6 +584,8 @@ def gemm_nt(A: torch.Tensor, Bw: torch.Tensor, out: torch.Tensor, *, M: int, a_r
     if (_NT_SPLITK and A.dtype == torch.bfloat16 and out.dtype == torch.bfloat16 and c_rows is None and resid is None and out2 is None
             and colsum_out is None and scale == 1.0 and scale_cols == 0 and not (flags & ~GF_RELU)):
         need = load().stswin_gemm_nt_splitk_scratch(M, N, Kseg, S)
+        if need > 0 and _PLAN_ROWS[0] != 1 and load().stswin_gemm_nt_splitk_scratch(M * _PLAN_ROWS[0], N, Kseg, S) <= 0:
+            need = 0
         if need > 0:
             ws = scratch(A.device, need)
             with _Span(name, 2.0 * M * N * Ktot):
@@ -632,6 +634,25 @@ def _log_variant(family: str, shape, fam_id: int) -> None:
 
 _WARNED = {}
 _NT_SPLITK = os.environ.get("STSWIN_NO_NT_SPLITK") != "1"                 # (A/B switch)
+_PLAN_ROWS = [1]             # splitk_as_rows: plan the split-K choice for this many times the launch's rows
+
+
+class splitk_as_rows:
+    """While active, gemm_nt takes its split-K path only where a launch of `factor` times the rows would take it too.  Split-K is
+    chosen for few output tiles, so its use depends on the row count, and it adds the K partitions in another order than the tiled
+    kernels.  stswincl_amd.video runs the ResNet on one new frame where model(clip) runs it on the clip's four: with factor 4 the
+    convolutions of both pick the same kernels, and a frame's features are the same bits in both."""
+
+    def __init__(self, factor: int):
+        self.factor = int(factor)
+
+    def __enter__(self):
+        self.prev = _PLAN_ROWS[0]
+        _PLAN_ROWS[0] = self.factor
+        return self
+
+    def __exit__(self, *exc):
+        _PLAN_ROWS[0] = self.prev
 _CS_PARTIAL_MIN_M = int(os.environ.get("STSWIN_CS_PARTIAL_MIN_M", "1"))   # (the table + fold path is the deterministic one: always)
 _CS_TABLES = {}
 
@@ -1296,6 +1317,63 @@ def upsample_argmax(logits, H, W, gt=None):
     _check(load().stswin_upsample_argmax(_dt(lg), _p(lg), _p(labels), _p(gt.contiguous() if gt is not None else None),
                                          _p(counts), F_, nc, h, w, H, W, _stream()), "upsample_argmax")
     return labels, counts
+
+
+def _int_table(t: Optional[torch.Tensor], rows: int, what: str):
+    if t is None:
+        raise StswinHipError(f"frame_ingest: the {what} table is missing")
+    if t.dtype != torch.int32 or t.dim() != 2 or t.shape[0] != rows or not t.is_contiguous():
+        raise StswinHipError(f"frame_ingest: the {what} table must be contiguous int32 [{rows}][k], got {t.dtype} {tuple(t.shape)}")
+    return t
+
+
+def frame_ingest(frames: torch.Tensor, out: torch.Tensor, lut: torch.Tensor, htab=None, vtab=None, tmp: Optional[torch.Tensor] = None):
+    """uint8 HWC frames [n][Hs][Ws][3] -> fp32 NCHW images `out` [n][3][H][W], Pillow BILINEAR resize + the 256-entry value
+    table `lut` (include/stswin_hip.h, stswin_frame_ingest).  htab / vtab = (bounds int32 [W|H][2], coef int32 [W|H][k]) for a
+    width / height that changes; tmp = uint8 [n][Hs][W][3] when the width changes."""
+    if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3 or not frames.is_contiguous():
+        raise StswinHipError(f"frame_ingest: frames must be contiguous uint8 [n][Hs][Ws][3], got {frames.dtype} {tuple(frames.shape)}")
+    n, Hs, Ws, _ = frames.shape
+    if out.dtype != torch.float32 or out.dim() != 4 or tuple(out.shape[:2]) != (n, 3) or not out.is_contiguous():
+        raise StswinHipError(f"frame_ingest: out must be contiguous fp32 [{n}][3][H][W], got {out.dtype} {tuple(out.shape)}")
+    H, W = out.shape[2:]
+    if lut.dtype != torch.float32 or lut.numel() != 256 or not lut.is_contiguous():
+        raise StswinHipError("frame_ingest: lut must be 256 contiguous fp32 values")
+    hb = hc = vb = vc = None
+    hk = vk = 0
+    if Ws != W:
+        hb, hc = _int_table(htab[0] if htab else None, W, "horizontal bounds"), _int_table(htab[1] if htab else None, W, "horizontal weight")
+        hk = hc.shape[1]
+        if tmp is None or tmp.dtype != torch.uint8 or tmp.numel() < n * Hs * W * 3 or not tmp.is_contiguous():
+            raise StswinHipError(f"frame_ingest: the width changes: tmp must be contiguous uint8 with >= {n * Hs * W * 3} bytes")
+    if Hs != H:
+        vb, vc = _int_table(vtab[0] if vtab else None, H, "vertical bounds"), _int_table(vtab[1] if vtab else None, H, "vertical weight")
+        vk = vc.shape[1]
+    _check(load().stswin_frame_ingest(_p(frames), _p(tmp if Ws != W else None), _p(out), n, Hs, Ws, H, W, _p(hb), _p(hc), hk,
+                                      _p(vb), _p(vc), vk, _p(lut), _stream()), "frame_ingest")
+    return out
+
+
+def clip_assemble(ring: torch.Tensor, fresh: Optional[torch.Tensor], clips: Optional[torch.Tensor], table: torch.Tensor, B: int,
+                  n_store: int) -> None:
+    """clips [B][4][...] <- ring [S][...] / fresh [n][...] frame features by `table` (int32 device [B*4 + n_store]: sources, then the
+    ring slots fresh frames 0..n_store-1 go to); include/stswin_hip.h, stswin_clip_assemble.  The table's values are read on the
+    device (a captured graph replays whatever the host last wrote into it)."""
+    frame = ring[0].numel()
+    for t, what in ((fresh, "fresh"), (clips, "clips")):
+        if t is not None and (t.dtype != ring.dtype or not t.is_contiguous() or t.numel() % frame or t.device != ring.device):
+            raise StswinHipError(f"clip_assemble: {what} must be contiguous {ring.dtype} frame features on {ring.device}")
+    if not ring.is_contiguous():
+        raise StswinHipError("clip_assemble: the ring must be contiguous")
+    if table.dtype != torch.int32 or table.numel() < B * 4 + n_store or not table.is_contiguous():
+        raise StswinHipError(f"clip_assemble: table must be contiguous int32 with >= {B * 4 + n_store} entries")
+    n_fresh = fresh.numel() // frame if fresh is not None else 0
+    if B > 0 and (clips is None or clips.numel() < B * 4 * frame):
+        raise StswinHipError(f"clip_assemble: clips must hold {B} x 4 frames")
+    if n_store > n_fresh:
+        raise StswinHipError(f"clip_assemble: {n_store} stores but {n_fresh} fresh frames")
+    _check(load().stswin_clip_assemble(_dt(ring), _p(ring), _p(fresh), _p(clips), _p(table), B, n_store, ring.shape[0], n_fresh,
+                                       _c_long(frame), _stream()), "clip_assemble")
 
 
 def optim_tick(kind: int, counter: torch.Tensor, hyper: torch.Tensor, a: float, b: float) -> None:

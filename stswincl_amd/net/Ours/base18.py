@@ -27,8 +27,15 @@ def decode_tokens(resnet, swin, aspp, proj1, proj2, proj3, x):
     """Frames (B,4,3,Hi,Wi) -> 400-channel decode feature as a padded token matrix [B*h*w][448] (base18.py:80-105 up to
     the concat; PixPro_swin_v5.py:302-327 is the same pipeline).  The ResNet runs once per frame so that train-mode
     BatchNorm statistics stay per frame (base18.py:86-89)."""
-    b, t = x.shape[:2]
     tem, h, w = resnet.forward_frames(x)                                     # (B, 4, L, 512) tokens
+    return decode_frame_tokens(swin, aspp, proj1, proj2, proj3, tem, h, w)
+
+
+def decode_frame_tokens(swin, aspp, proj1, proj2, proj3, tem, h, w):
+    """Frame tokens (B,4,h*w,512) of the ResNet feeder -> the 400-channel decode feature of decode_tokens: temporal Swin, ASPP,
+    the three projections and the concat.  The ResNet features of a frame do not depend on its clip in eval mode, so
+    stswincl_amd.video computes them once per frame and calls this on clips assembled from them."""
+    b = tem.shape[0]
     c = tem.shape[-1]
     res_last = tem[:, -1].reshape(b * h * w, c)
     t1_all, t2_all = swin.forward_tokens(tem)
@@ -68,6 +75,18 @@ class TswinPlus(nn.Module):
         hip.arena_reset(x.device)                           # one zero-fill block per step (forward + backward accumulators)
         with H.deferred_bn_counters():
             cat, (b, h, w) = decode_tokens(self.resnet, self.swin, self.aspp, self.project1, self.project2, self.project3, x)
-            y = H.conv_bn_relu(cat, self.classifier[0], self.classifier[1], (b, h, w), lin=LCAT)
-            y = H.conv1x1_tokens(y, self.classifier[3], b, h, w)
+            y = self.classify_tokens(cat, b, h, w)
+        return H.LogitsUpFn.apply(y, (b, h, w, hi, wi, self.num_classes))
+
+    def classify_tokens(self, cat, b, h, w):
+        """The 400-channel decode feature -> logit tokens [B*h*w][num_classes] (base18.py:105; LogitsUpFn follows)."""
+        y = H.conv_bn_relu(cat, self.classifier[0], self.classifier[1], (b, h, w), lin=LCAT)
+        return H.conv1x1_tokens(y, self.classifier[3], b, h, w)
+
+    def forward_frame_tokens(self, tem, h, w, hi, wi):
+        """Eval-mode forward from the ResNet tokens (B,4,h*w,512) of each clip's frames: -> logits (B,num_classes,hi,wi), what
+        forward gives for the clips those frames came from (stswincl_amd.video).  The caller resets the zero arena."""
+        with H.deferred_bn_counters():
+            cat, (b, h, w) = decode_frame_tokens(self.swin, self.aspp, self.project1, self.project2, self.project3, tem, h, w)
+            y = self.classify_tokens(cat, b, h, w)
         return H.LogitsUpFn.apply(y, (b, h, w, hi, wi, self.num_classes))

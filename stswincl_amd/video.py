@@ -1,0 +1,491 @@
+"""Video inference: segment whole sequences with TswinPlus, computing each frame's ResNet features once.
+
+The reference evaluates a sequence with batch 1 and one 4-frame clip per labelled frame (seg18/test.py:147-175 over
+seg18/dataset/Endovis2018_new.py:109-127): frames f-3 .. f, and f+3, f+2, f+1, f for f < 4 (the rule is `t > frame`).  Each
+frame is resized with PIL BILINEAR on the host, divided by 255 and sent to the model as an fp32 clip, so every frame runs
+through the ResNet feeder four times.  In eval mode BatchNorm uses its running statistics: a frame's ResNet features do not
+depend on the clip around it.  VideoSegmenter therefore
+
+  * ingests the new uint8 frames on the GPU (stswin_frame_ingest: Pillow's resampler, bit-exact, and the /255 table),
+  * runs the ResNet on the new frames only and keeps their tokens in a device ring of frame-feature slots,
+  * assembles the clips (B, 4, h*w, 512) from ring slots and new frames (stswin_clip_assemble, one launch that also stores the
+    new frames' tokens into their slots) and runs Swin / ASPP / head on them (TswinPlus.forward_frame_tokens).
+
+    from stswincl_amd.video import VideoSegmenter
+    seg = VideoSegmenter(model.eval(), out="labels", out_size=(1024, 1280))
+    for frame in decoder:                                  # uint8 [Hs][Ws][3] or [n][Hs][Ws][3], CPU or GPU
+        for f, labels in seg.push(frame):                  # frames whose clip is complete, in release order
+            ...
+    for f, labels in seg.finish():                         # end of the sequence
+        ...
+    seg.reset()                                            # next sequence: frame indices restart at 0
+
+Which clips are ready after each frame, which slots they read and which slots the new frames take is decided on the host by
+ClipPlanner (pure Python).  With batch 1 a clip is released when its last frame arrives: frame 3 -> {0}, 4 -> {1, 4}, 5 -> {2, 5},
+6 -> {3, 6}, f >= 7 -> {f}.  A sequence needs at least 7 frames (frame 3's clip reads frame 6).
+"""
+from __future__ import annotations
+
+from collections import deque
+from typing import List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import hip
+from .hip import StswinHipError
+
+T = 4                   # frames per clip (the model asserts T == 4)
+
+
+def clip_frames(f: int, t: int = T) -> Tuple[int, ...]:
+    """The frames of frame f's clip in clip order (Endovis2018_new.py:119-124)."""
+    if t > f:
+        return tuple(range(f + t - 1, f - 1, -1))
+    return tuple(range(f - t + 1, f + 1))
+
+
+def ready_at(f: int) -> List[int]:
+    """The clips whose last missing frame is frame f, in release order."""
+    out = []
+    if T - 1 <= f <= 2 * T - 2:           # clip f - 3 < 4 reads f - 3 .. f
+        out.append(f - (T - 1))
+    if f >= T:
+        out.append(f)
+    return out
+
+
+class Step:
+    """One launch group: ResNet on `new` (frame indices), `clips` (frame indices) assembled from `sources` (per clip, T entries:
+    ring slot >= 0 or new frame -1 - j) and the new frames stored into `stores` (slot per new frame, -1 = not kept)."""
+
+    __slots__ = ("new", "stores", "clips", "sources")
+
+    def __init__(self, new, stores, clips, sources):
+        self.new, self.stores, self.clips, self.sources = new, stores, clips, sources
+
+    def table(self) -> List[int]:
+        """The int32 slot table of stswin_clip_assemble: B*4 sources, then the stores."""
+        return [e for src in self.sources for e in src] + list(self.stores)
+
+    def __repr__(self):
+        return f"Step(new={self.new}, stores={self.stores}, clips={self.clips}, sources={self.sources})"
+
+
+class ClipPlanner:
+    """Host-side schedule of a VideoSegmenter: which clips are ready, which ring slots they read, which slots new frames take.
+
+    Frames are counted from 0 per sequence.  Ready clips are run `batch` at a time (finish() runs the rest).  A frame stays in the
+    ring while a clip that still has to run reads it: the clips of frames >= F (F = frames pushed) read frames >= F - 3, so the
+    ring holds those and the frames of ready clips not yet run.  No step stores into a slot it reads."""
+
+    def __init__(self, batch: int = 1, slots: Optional[int] = None):
+        if batch < 1:
+            raise StswinHipError(f"batch must be >= 1, got {batch}")
+        self.batch = batch
+        self.slots = slots if slots is not None else max(2 * T - 1, batch + T - 1)
+        if self.slots < max(2 * T - 1, batch + T - 1):
+            raise StswinHipError(f"a ring of {self.slots} slots is too small for batch {batch}: needs >= {max(2 * T - 1, batch + T - 1)}")
+        self.reset()
+
+    def reset(self) -> None:
+        self.seen = 0
+        self.unprocessed: List[int] = []
+        self.slot_of = {}
+        self.pending = deque()
+        self.cursor = 0
+
+    def push(self, n: int = 1) -> List[Step]:
+        steps = []
+        for _ in range(n):
+            f = self.seen
+            self.seen += 1
+            self.unprocessed.append(f)
+            self.pending.extend(ready_at(f))
+            while len(self.pending) >= self.batch:
+                steps.append(self._step([self.pending.popleft() for _ in range(self.batch)]))
+        return steps
+
+    def finish(self) -> List[Step]:
+        short = [g for g in range(min(T, self.seen)) if max(clip_frames(g)) >= self.seen]
+        if short:
+            raise StswinHipError(f"a sequence of {self.seen} frames is too short: the clip of frame {short[0]} reads frames "
+                                 f"{clip_frames(short[0])} (the reference's rule needs >= {2 * T - 1} frames)")
+        steps = []
+        while self.pending:
+            steps.append(self._step([self.pending.popleft() for _ in range(min(self.batch, len(self.pending)))]))
+        return steps
+
+    def _step(self, clips: List[int]) -> Step:
+        new, self.unprocessed = self.unprocessed, []
+        pos = {fr: j for j, fr in enumerate(new)}
+        sources = []
+        for g in clips:
+            src = []
+            for fr in clip_frames(g):
+                if fr in pos:
+                    src.append(-1 - pos[fr])
+                elif fr in self.slot_of:
+                    src.append(self.slot_of[fr])
+                else:                                                   # (a planner bug, not a user error)
+                    raise AssertionError(f"frame {fr} of clip {g} is neither new nor in the ring")
+            sources.append(src)
+        needed = {fr for g in self.pending for fr in clip_frames(g)}
+        needed.update(range(max(0, self.seen - (T - 1)), self.seen))
+        read = {e for src in sources for e in src if e >= 0}
+        for fr in [fr for fr in self.slot_of if fr not in needed]:
+            del self.slot_of[fr]
+        taken = set(self.slot_of.values()) | read
+        stores = []
+        for fr in new:
+            if fr not in needed:
+                stores.append(-1)
+                continue
+            for k in range(self.slots):
+                s = (self.cursor + k) % self.slots
+                if s not in taken:
+                    break
+            else:
+                raise AssertionError(f"frame-feature ring of {self.slots} slots is full")
+            self.cursor = (s + 1) % self.slots
+            taken.add(s)
+            self.slot_of[fr] = s
+            stores.append(s)
+        return Step(new, stores, clips, sources)
+
+
+# ----------------------------------------------------------------------------------------------- frame ingest
+# float32(u / 255.) of the reference (astype(float) / 255., then .float()): equal to the fp32 division u / 255.f for all 256 values,
+# not to u * (1 / 255.f) (126 differ)
+VALUE_TABLE = (np.arange(256, dtype=np.float64) / 255.).astype(np.float32)
+_PRECISION_BITS = 22
+
+
+def bilinear_coeffs(in_size: int, out_size: int) -> Tuple[np.ndarray, np.ndarray]:
+    """Pillow's BILINEAR coefficients for one axis (libImaging/Resample.c precompute_coeffs + normalize_coeffs_8bpc), in float64:
+    -> (bounds int32 [out][2] = (first tap, taps), weights int32 [out][ksize] with 22 fraction bits)."""
+    scale = float(in_size) / out_size
+    fs = max(scale, 1.0)
+    support = fs                                            # the triangle filter's support is 1
+    ksize = int(np.ceil(support)) * 2 + 1
+    center = (np.arange(out_size, dtype=np.float64) + 0.5) * scale
+    xmin = np.maximum(np.trunc(center - support + 0.5), 0).astype(np.int64)
+    xmax = np.minimum(np.trunc(center + support + 0.5), in_size).astype(np.int64)
+    n = xmax - xmin
+    x = np.arange(ksize)
+    t = np.abs((x[None, :] + xmin[:, None] - center[:, None] + 0.5) * (1.0 / fs))
+    w = np.where((t < 1.0) & (x[None, :] < n[:, None]), 1.0 - t, 0.0)
+    ww = np.zeros(out_size)
+    for k in range(ksize):                                   # the sequential float64 sum of the C loop
+        ww += w[:, k]
+    w = np.where(ww[:, None] != 0.0, w / np.where(ww == 0.0, 1.0, ww)[:, None], w)
+    kk = np.trunc(np.where(w < 0, -0.5, 0.5) + w * (1 << _PRECISION_BITS)).astype(np.int32)
+    return np.stack([xmin, n], 1).astype(np.int32), np.ascontiguousarray(kk)
+
+
+_TABLES = {}            # (in, out, device) -> (bounds, weights) on the device
+_LUTS = {}
+
+
+def _tables(in_size: int, out_size: int, device):
+    key = (in_size, out_size, str(device))
+    tab = _TABLES.get(key)
+    if tab is None:
+        b, k = bilinear_coeffs(in_size, out_size)
+        assert int((b[:, 0] + b[:, 1]).max()) <= in_size and int(b[:, 0].min()) >= 0
+        tab = (torch.from_numpy(b).to(device), torch.from_numpy(k).to(device))
+        _TABLES[key] = tab
+    return tab
+
+
+def _lut(device):
+    t = _LUTS.get(str(device))
+    if t is None:
+        t = _LUTS[str(device)] = torch.from_numpy(VALUE_TABLE).to(device)
+    return t
+
+
+def ingest(frames: torch.Tensor, size: Tuple[int, int], out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint8 RGB frames [n][Hs][Ws][3] on the GPU -> fp32 images [n][3][H][W] (the stem's input): PIL.Image.resize((W, H),
+    Image.BILINEAR) bit for bit, then float32(u / 255.).  One or two launches (horizontal pass into a uint8 intermediate when the
+    width changes, vertical pass + conversion)."""
+    H, W = size
+    n, Hs, Ws, _ = frames.shape
+    dev = frames.device
+    if out is None:
+        out = torch.empty(n, 3, H, W, dtype=torch.float32, device=dev)
+    htab = _tables(Ws, W, dev) if Ws != W else None
+    vtab = _tables(Hs, H, dev) if Hs != H else None
+    tmp = torch.empty(n * Hs * W * 3, dtype=torch.uint8, device=dev) if Ws != W else None
+    return hip.frame_ingest(frames, out, _lut(dev), htab, vtab, tmp)
+
+
+# ----------------------------------------------------------------------------------------------- the segmenter
+class _Pinned:
+    """Pinned host staging buffers for host -> device copies that do not block the host: a buffer is reused only after the copy
+    that last read it has run (its event)."""
+
+    def __init__(self, count: int = 4):
+        self.bufs = [None] * count
+        self.events = [None] * count
+        self.i = 0
+
+    def upload(self, arr: np.ndarray, dst: torch.Tensor) -> torch.Tensor:
+        i = self.i = (self.i + 1) % len(self.bufs)
+        if self.events[i] is not None:
+            self.events[i].synchronize()
+        flat = np.ascontiguousarray(arr).reshape(-1)
+        buf = self.bufs[i]
+        if buf is None or buf.numel() < flat.nbytes:
+            buf = self.bufs[i] = torch.empty(flat.nbytes, dtype=torch.uint8).pin_memory()
+        buf[:flat.nbytes].numpy().view(flat.dtype)[:] = flat
+        dst.view(torch.uint8).view(-1).copy_(buf[:flat.nbytes], non_blocking=True)
+        ev = self.events[i] = torch.cuda.Event()
+        ev.record()
+        return dst
+
+
+class VideoSegmenter:
+    """Segment video sequences with an eval-mode TswinPlus, one result per frame, each frame's ResNet features computed once.
+
+    seg = VideoSegmenter(model, batch=1, out="logits" | "labels", out_size=None, graph=False)
+
+    push(frames, gt=None) takes uint8 RGB frames [n][Hs][Ws][3] (or one [Hs][Ws][3]; torch tensor on the model's GPU or the CPU, or
+    a numpy array) and returns [(frame_index, result), ...] for the frames whose clip is now complete.  finish() runs what is
+    left at the end of the sequence; reset() starts the next one (frame indices restart at 0).  segment_sequence(frames, gt=None)
+    is reset + push + finish, results in frame order.  Frames are resized to the model's input size (H, W) = 8 x
+    swin.input_resolution.
+
+    result: out="logits": the fp32 (bf16 under autocast) logits (nc, H, W) that model(clip) gives for the frame's clip;
+    out="labels": uint8 labels (out_size, default (H, W)) of the bilinear (align_corners=True) resize + argmax
+    (hip.upsample_argmax).  With gt (int64 [n][*out_size], one per pushed frame) the result is (labels or logits, dice, iou) with the
+    per-frame [[class, value], ...] lists of utils.EndoMetric.predict_and_score.
+
+    batch = B > 1 runs ready clips B at a time (offline throughput; the last results come with finish()).  graph=True (batch 1)
+    captures the steady-state step - ingest, ResNet on the new frame, clip assembly, Swin / ASPP / head, logits or labels - once
+    after the warm-up frames and replays it for every later frame; the host only copies the frame (a CPU frame from pinned memory)
+    and the slot table into the captured buffers.  As with torch.cuda.graphs, the result of the last replayed step of a push is a
+    view of the graph's output buffer that the next push overwrites (clone what you keep); earlier replayed results of the same
+    push are copies, and segment_sequence returns copies.
+
+    Runs under torch.no_grad().  Refuses (StswinHipError): a model in train mode, a model or frames not on the GPU, a frame size
+    that differs from the earlier frames'."""
+
+    def __init__(self, model, batch: int = 1, out: str = "logits", out_size: Optional[Sequence[int]] = None, graph: bool = False):
+        if out not in ("logits", "labels"):
+            raise StswinHipError(f"out must be 'logits' or 'labels', got {out!r}")
+        if graph and batch != 1:
+            raise StswinHipError("graph replay runs the online step: batch must be 1")
+        self.model = model
+        self._check_train()
+        if any(not p.is_cuda for p in model.parameters()):
+            raise StswinHipError("VideoSegmenter needs the model on the GPU (model.cuda()); there is no CPU path")
+        self.device = next(model.parameters()).device
+        ir = tuple(model.swin.input_resolution)
+        self.size = (8 * ir[0], 8 * ir[1])
+        self.batch = batch
+        self.out = out
+        self.out_size = tuple(out_size) if out_size is not None else self.size
+        self.graph = graph
+        self.planner = ClipPlanner(batch)
+        self.frame_shape = None
+        self._ring = None
+        self._pinned = _Pinned()
+        self._g = None
+        self.reset()
+
+    def _check_train(self):
+        if self.model.training:
+            raise StswinHipError("VideoSegmenter needs the model in eval mode (model.eval()): in train mode BatchNorm uses batch "
+                                 "statistics and a frame's features depend on its clip")
+
+    def reset(self) -> None:
+        self.planner.reset()
+        self._frames = {}                 # frame index -> (uint8 tensor [k][Hs][Ws][3], GPU or CPU, row) until its ResNet pass
+        self._gt = {}
+
+    # ----------------------------------------------------------------------------------------- public
+    def push(self, frames, gt=None) -> List[Tuple[int, object]]:
+        self._check_train()
+        fr = self._as_frames(frames)
+        n = fr.shape[0]
+        if gt is not None:
+            gt = torch.as_tensor(gt)
+            if gt.dim() == 2:
+                gt = gt[None]
+            if gt.shape[0] != n or tuple(gt.shape[1:]) != self.out_size:
+                raise StswinHipError(f"gt must be [{n}][{self.out_size[0]}][{self.out_size[1]}], got {tuple(gt.shape)}")
+            gt = gt.to(self.device, torch.int64)
+        f0 = self.planner.seen
+        for j in range(n):
+            self._frames[f0 + j] = (fr, j)
+            if gt is not None:
+                self._gt[f0 + j] = gt[j:j + 1]
+        return self._run_all(self.planner.push(n))
+
+    def finish(self) -> List[Tuple[int, object]]:
+        self._check_train()
+        return self._run_all(self.planner.finish())
+
+    def segment_sequence(self, frames, gt=None) -> list:
+        self.reset()
+        res = self.push(frames, gt) + self.finish()
+        if self.graph:
+            res = [(f, _clone(r)) for f, r in res]
+        self.reset()
+        return [r for _, r in sorted(res, key=lambda fr: fr[0])]
+
+    # ----------------------------------------------------------------------------------------- internals
+    def _as_frames(self, frames) -> torch.Tensor:
+        if isinstance(frames, np.ndarray):
+            frames = torch.from_numpy(frames)
+        if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8:
+            raise StswinHipError("frames must be uint8 RGB [n][Hs][Ws][3] (torch tensor or numpy array)")
+        if frames.dim() == 3:
+            frames = frames[None]
+        if frames.dim() != 4 or frames.shape[3] != 3:
+            raise StswinHipError(f"frames must be uint8 RGB [n][Hs][Ws][3], got {tuple(frames.shape)}")
+        shape = tuple(frames.shape[1:3])
+        if self.frame_shape is None:
+            self.frame_shape = shape
+        elif shape != self.frame_shape:
+            raise StswinHipError(f"frame size {shape} differs from the earlier frames' {self.frame_shape}")
+        if frames.is_cuda and frames.device != self.device:
+            raise StswinHipError(f"frames on {frames.device}, the model on {self.device}")
+        return frames.contiguous()           # (CPU frames stay on the host until their step copies them from pinned memory)
+
+    def _put_frames(self, src: torch.Tensor, r0: int, k: int, dst: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Rows r0 .. r0+k of a pushed frame tensor on the GPU: a view of it, or (CPU frames, or a static buffer `dst`) a copy."""
+        part = src[r0:r0 + k]
+        if dst is None:
+            if part.is_cuda:
+                return part
+            dst = torch.empty(part.shape, dtype=torch.uint8, device=self.device)
+        if part.is_cuda:
+            return dst.copy_(part)
+        return self._pinned.upload(part.numpy(), dst)
+
+    def _upload_table(self, values: List[int], dst: Optional[torch.Tensor] = None) -> torch.Tensor:
+        if dst is None:
+            dst = torch.empty(len(values), dtype=torch.int32, device=self.device)
+        return self._pinned.upload(np.asarray(values, dtype=np.int32), dst)
+
+    def _ingest_new(self, new: List[int]) -> torch.Tensor:
+        """The new frames' fp32 images [n][3][H][W]: one ingest launch per run of rows of one pushed tensor."""
+        out = torch.empty(len(new), 3, *self.size, dtype=torch.float32, device=self.device)
+        j = 0
+        while j < len(new):
+            src, r0 = self._frames.pop(new[j])
+            k = 1
+            while j + k < len(new) and self._frames[new[j + k]][0] is src and self._frames[new[j + k]][1] == r0 + k:
+                self._frames.pop(new[j + k])
+                k += 1
+            ingest(self._put_frames(src, r0, k), self.size, out[j:j + k])
+            j += k
+        return out
+
+    def _compute(self, img: Optional[torch.Tensor], table: torch.Tensor, B: int, n_new: int, labels: bool = False):
+        """ResNet on the new frames' images, clip assembly, Swin / ASPP / head: -> logits (B, nc, H, W) (and with labels = True the
+        labels (B, *out_size)).  Every launch on the current stream, no host synchronisation (graph-capturable)."""
+        m = self.model
+        hip.arena_reset(self.device)
+        h, w = self.size[0] // 8, self.size[1] // 8
+        tok = None
+        if n_new:
+            # the GEMMs plan as for model(clip)'s launch over the clip's T frames: the same kernels, a frame's features the same bits
+            with hip.splitk_as_rows(T):
+                tok, h2, w2 = m.resnet.forward_tokens(img, groups=1)
+            if (h2, w2) != (h, w):
+                raise StswinHipError(f"the ResNet gives {h2}x{w2} features, the model's swin.input_resolution is {(h, w)}")
+        dt = tok.dtype if tok is not None else self._ring.dtype
+        L = h * w
+        if self._ring is None:
+            self._ring = torch.empty(self.planner.slots, L, 512, dtype=dt, device=self.device)
+        elif self._ring.dtype != dt:
+            raise StswinHipError(f"the compute dtype changed within the segmenter ({self._ring.dtype} -> {dt}): keep autocast as it "
+                                 "was, or make a new VideoSegmenter")
+        clips = torch.empty(B, T, L, 512, dtype=dt, device=self.device)
+        hip.clip_assemble(self._ring, tok, clips, table, B, n_new)
+        logits = m.forward_frame_tokens(clips, h, w, self.size[0], self.size[1])
+        if labels:
+            return logits, hip.upsample_argmax(logits, *self.out_size)[0]
+        return logits, None
+
+    def _steady(self, st: Step) -> bool:
+        return len(st.new) == 1 and len(st.clips) == 1 and st.clips[0] == st.new[0] and st.clips[0] >= 2 * T - 1
+
+    def _run_all(self, steps: List[Step]) -> List[Tuple[int, object]]:
+        res = []
+        with torch.no_grad():
+            for i, st in enumerate(steps):
+                r, replayed = self._run(st)
+                if replayed and i + 1 < len(steps):        # the next replay of this call overwrites the graph's output buffers
+                    r = [(f, _clone(x)) for f, x in r]
+                res += r
+        return res
+
+    def _run(self, st: Step):
+        B, n_new = len(st.clips), len(st.new)
+        want_labels = self.out == "labels" and not any(g in self._gt for g in st.clips)
+        if self.graph and self._steady(st):
+            logits, labels, replayed = self._run_graph(st, want_labels)
+        else:
+            img = self._ingest_new(st.new) if n_new else None
+            logits, labels = self._compute(img, self._upload_table(st.table()), B, n_new, want_labels)
+            replayed = False
+        return self._results(st.clips, logits, labels), replayed
+
+    def _run_graph(self, st: Step, want_labels: bool):
+        src, r = self._frames.pop(st.new[0])
+        g = self._g
+        if g is None or g[5] != want_labels:
+            # first steady-state step (or first of the other output form): one eager warm-up on the static buffers (on a side stream,
+            # as graph.py's GraphedStep does), then the capture; this step's result is the warm-up's
+            u8 = torch.empty(1, *self.frame_shape, 3, dtype=torch.uint8, device=self.device)
+            table = torch.empty(T + 1, dtype=torch.int32, device=self.device)
+            self._put_frames(src, r, 1, u8)
+            self._upload_table(st.table(), table)
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                logits, labels = self._compute(ingest(u8, self.size), table, 1, 1, want_labels)
+                logits = logits.clone()
+            torch.cuda.current_stream().wait_stream(side)
+            torch.cuda.synchronize()
+            hip.note_capture()
+            graph = torch.cuda.CUDAGraph()
+            autocast = torch.is_autocast_enabled()
+            with torch.cuda.graph(graph):
+                out, out_labels = self._compute(ingest(u8, self.size), table, 1, 1, want_labels)
+            self._g = (graph, u8, table, out, out_labels, want_labels, autocast)
+            return logits, labels, False
+        graph, u8, table, out, out_labels, _, autocast = g
+        if torch.is_autocast_enabled() != autocast:
+            raise StswinHipError("autocast differs from the state the step was captured under: make a new VideoSegmenter")
+        self._put_frames(src, r, 1, u8)
+        self._upload_table(st.table(), table)
+        graph.replay()
+        return out, out_labels, True
+
+    def _results(self, clips: List[int], logits: torch.Tensor, labels: Optional[torch.Tensor]) -> List[Tuple[int, object]]:
+        if labels is not None:
+            return [(g, labels[b]) for b, g in enumerate(clips)]
+        res = []
+        for b, g in enumerate(clips):
+            gt = self._gt.pop(g, None)
+            lg = logits[b]
+            if gt is None:
+                res.append((g, lg if self.out == "logits" else hip.upsample_argmax(logits[b:b + 1], *self.out_size)[0][0]))
+                continue
+            from .utils.EndoMetric import predict_and_score
+            lab, dices, ious = predict_and_score(logits[b:b + 1], self.out_size, gt)
+            res.append((g, (lg if self.out == "logits" else lab[0], dices[0], ious[0])))
+        return res
+
+
+def _clone(r):
+    if isinstance(r, torch.Tensor):
+        return r.clone()
+    if isinstance(r, tuple):
+        return tuple(_clone(x) for x in r)
+    return r
