@@ -522,6 +522,14 @@ int stswin_pair_loss_bwd(const float* pos, const float* all, const float* cnt, c
  * counts[f][0|1|2][c] = |gt == c|, |pred == c|, |gt == c and pred == c|  (int32, zeroed by the caller). */
 int stswin_upsample_argmax(int dtype, const void* logits, unsigned char* labels, const long* gt, int* counts, int frames,
                            int nc, int h, int w, int H, int W, void* stream);
+/* ---- CaDIS evaluation (segcata/cata_test.py:115-170 + utils/cata_metrics.py ConfusionMatrix): labels[f][y][x] = argmax_c of the
+ * bilinear resize of NCHW logits [F][nc][h][w] (nc <= 64) to (H, W), align_corners = 1 as stswin_upsample_argmax, 0 as ATen
+ * (cata_test.py:129: src = max((in / out) (dst + 0.5) - 0.5, 0)); first maximum wins.  labels may be NULL (not written).  With gt
+ * (int64 [F][H][W]) and cm (uint64 [ncm][ncm], ncm <= 64) every pixel with 0 <= gt < ncm and 0 <= label < ncm adds 1 to
+ * cm[gt][label] (rows gt, columns prediction, as the reference's `num_classes * gt + pred`).  The matrix is accumulated, never
+ * cleared: the caller zeroes it once per evaluation.  Integer atomics only (exact, independent of order). */
+int stswin_upsample_argmax_cm(int dtype, const void* logits, unsigned char* labels, const long* gt, unsigned long long* cm, int ncm,
+                              int align_corners, int frames, int nc, int h, int w, int H, int W, void* stream);
 
 /* ---- video inference (stswincl_amd/video.py), the evaluation loop of seg18/test.py:147-175 over the clips of
  * seg18/dataset/Endovis2018_new.py:109-127.
@@ -540,6 +548,11 @@ int stswin_upsample_argmax(int dtype, const void* logits, unsigned char* labels,
 int stswin_frame_ingest(const unsigned char* in, unsigned char* tmp, float* out, int n, int Hs, int Ws, int H, int W,
                         const int* hbounds, const int* hcoef, int hksize, const int* vbounds, const int* vcoef, int vksize,
                         const float* lut, void* stream);
+/* stswin_frame_ingest_planes: stswin_frame_ingest with one value table per RGB plane, lut [3][256] (the CaDIS transform,
+ * segcata/dataset/CATA_new_512.py:21-22, 228-229: float32((u / 255. - MEAN[c]) / STD[c]) computed in float64 on the host). */
+int stswin_frame_ingest_planes(const unsigned char* in, unsigned char* tmp, float* out, int n, int Hs, int Ws, int H, int W,
+                               const int* hbounds, const int* hcoef, int hksize, const int* vbounds, const int* vcoef, int vksize,
+                               const float* lut, void* stream);
 int stswin_clip_assemble(int dtype, void* ring, const void* fresh, void* clips, const int* table, int B, int n_store, int slots,
                          int n_fresh, long frame_elems, void* stream);
 

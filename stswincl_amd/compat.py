@@ -4,6 +4,8 @@ they already use:
     net.Ours.swin_512 / base18 / ASPP / resnet,  utils.losses,  contrast.models.PixPro_swin_v5,
     contrast.models.Ours.{base,swin_tem,ASPPv5,resnet}
 
+and the CaDIS package's (segcata): net.Ours.base_cata_np / swin_tem_cata / ASPP_swin,  utils.cata_metrics
+
 Call ``stswincl_amd.compat.install()`` before the script's own imports."""
 from __future__ import annotations
 
@@ -25,6 +27,10 @@ _ALIASES = {
     "contrast.models.Ours.swin_tem": "stswincl_amd.net.Ours.swin_512",
     "contrast.models.Ours.ASPPv5": "stswincl_amd.net.Ours.ASPP",
     "contrast.models.Ours.resnet": "stswincl_amd.net.Ours.resnet",
+    "utils.cata_metrics": "stswincl_amd.utils.cata_metrics",
+    "net.Ours.base_cata_np": "stswincl_amd.net.Ours.base_cata_np",
+    "net.Ours.swin_tem_cata": "stswincl_amd.net.Ours.swin_512",       # (the same module as seg18's swin_512.py)
+    "net.Ours.ASPP_swin": "stswincl_amd.net.Ours.ASPP",               # (its ASPP is seg18's ASPP.py, lines 1-99)
 }
 
 

@@ -1025,6 +1025,87 @@ extern "C" int stswin_upsample_argmax(int dtype, const void* logits, unsigned ch
   return 0;
 }
 
+// segcata/cata_test.py:115-170 + utils/cata_metrics.py: F.interpolate(out, (H, W), bilinear, align_corners) -> argmax, then one
+// confusion matrix over the whole test set (rows gt, columns prediction; a pixel counts only when both lie in [0, ncm)).  Each block
+// takes UA_CM_PIX consecutive output pixels of one frame, counts its pixels into an LDS histogram of ncm x ncm int32 bins and adds
+// every non-zero bin to the caller's 64-bit matrix with one atomic: integer adds only, so the matrix does not depend on the order.
+// align_corners = 0 is ATen's area_pixel_compute_source_index: src = max(scale (dst + 0.5) - 0.5, 0), scale = in / out.
+#define UA_CM_PIX 1024
+
+template <typename TL, bool CM>
+__global__ __launch_bounds__(256) void upsample_argmax_cm_kernel(const TL* __restrict__ logits, unsigned char* __restrict__ labels,
+                                                                 const long* __restrict__ gt, unsigned long long* cm, int ncm,
+                                                                 int align, int nc, int h, int w, int H, int W) {
+  __shared__ int hist[CM ? 64 * 64 : 1];
+  const int bins = ncm * ncm;
+  if (CM) {
+    for (int i = threadIdx.x; i < bins; i += 256) hist[i] = 0;
+    __syncthreads();
+  }
+  const long per_frame = (long)H * W;
+  const long blocks_per_frame = (per_frame + UA_CM_PIX - 1) / UA_CM_PIX;
+  const int f = (int)(blockIdx.x / blocks_per_frame);
+  const long p0 = (blockIdx.x % blocks_per_frame) * UA_CM_PIX;
+  const float sy = align ? (H > 1 ? (float)(h - 1) / (float)(H - 1) : 0.f) : (float)h / (float)H;
+  const float sx = align ? (W > 1 ? (float)(w - 1) / (float)(W - 1) : 0.f) : (float)w / (float)W;
+  const TL* b = logits + (long)f * nc * h * w;
+  for (int k = 0; k < UA_CM_PIX / 256; ++k) {
+    const long px = p0 + k * 256 + threadIdx.x;
+    if (px >= per_frame) break;
+    const int x = (int)(px % W), y = (int)(px / W);
+    float fy, fx;
+    if (align) {
+      fy = y * sy;
+      fx = x * sx;
+    } else {
+      fy = fmaxf(sy * ((float)y + 0.5f) - 0.5f, 0.f);
+      fx = fmaxf(sx * ((float)x + 0.5f) - 0.5f, 0.f);
+    }
+    const int y0 = min((int)fy, h - 1), x0 = min((int)fx, w - 1);
+    const int y1 = min(y0 + 1, h - 1), x1 = min(x0 + 1, w - 1);
+    const float wy = fy - y0, wx = fx - x0;
+    float best = -3.0e38f; int arg = 0;
+    for (int c = 0; c < nc; ++c) {
+      const TL* pl = b + (long)c * h * w;
+      const float v = (1.f - wy) * ((1.f - wx) * to_f32<TL>(pl[y0 * w + x0]) + wx * to_f32<TL>(pl[y0 * w + x1])) +
+                      wy * ((1.f - wx) * to_f32<TL>(pl[y1 * w + x0]) + wx * to_f32<TL>(pl[y1 * w + x1]));
+      if (v > best) { best = v; arg = c; }
+    }
+    if (labels) labels[(long)f * per_frame + px] = (unsigned char)arg;
+    if (CM) {
+      const long g = gt[(long)f * per_frame + px];
+      if (g >= 0 && g < ncm && arg < ncm) atomicAdd(&hist[(int)g * ncm + arg], 1);
+    }
+  }
+  if (CM) {
+    __syncthreads();
+    for (int i = threadIdx.x; i < bins; i += 256)
+      if (hist[i]) atomicAdd(cm + i, (unsigned long long)hist[i]);
+  }
+}
+
+extern "C" int stswin_upsample_argmax_cm(int dtype, const void* logits, unsigned char* labels, const long* gt, unsigned long long* cm,
+                                         int ncm, int align_corners, int frames, int nc, int h, int w, int H, int W, void* stream) {
+  if (nc <= 0 || nc > 64 || frames <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0) return -1406;
+  if (logits == nullptr) return -1407;
+  const bool with_cm = gt != nullptr || cm != nullptr;
+  if (with_cm && (gt == nullptr || cm == nullptr || ncm <= 0 || ncm > 64)) return -1408;
+  if (!with_cm && labels == nullptr) return -1409;                  // nothing to write
+  const long bpf = ((long)H * W + UA_CM_PIX - 1) / UA_CM_PIX;
+  dim3 grid((unsigned)(bpf * frames));
+  hipStream_t st = (hipStream_t)stream;
+  const int al = align_corners ? 1 : 0;
+  if (dtype == 0) {
+    if (with_cm) hipLaunchKernelGGL((upsample_argmax_cm_kernel<bf16, true>), grid, dim3(256), 0, st, (const bf16*)logits, labels, gt, cm, ncm, al, nc, h, w, H, W);
+    else hipLaunchKernelGGL((upsample_argmax_cm_kernel<bf16, false>), grid, dim3(256), 0, st, (const bf16*)logits, labels, gt, cm, ncm, al, nc, h, w, H, W);
+  } else {
+    if (with_cm) hipLaunchKernelGGL((upsample_argmax_cm_kernel<float, true>), grid, dim3(256), 0, st, (const float*)logits, labels, gt, cm, ncm, al, nc, h, w, H, W);
+    else hipLaunchKernelGGL((upsample_argmax_cm_kernel<float, false>), grid, dim3(256), 0, st, (const float*)logits, labels, gt, cm, ncm, al, nc, h, w, H, W);
+  }
+  STSWIN_CHECK_LAUNCH();
+  return 0;
+}
+
 
 // ----------------------------------------------------------------------------------------- statistics from a GEMM epilogue
 // A convolution GEMM launched with STSWIN_GF_CS_PARTIAL | STSWIN_GF_CS_SQ leaves per-128-row-block column sums and sums of

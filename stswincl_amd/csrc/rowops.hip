@@ -1170,10 +1170,11 @@ __global__ __launch_bounds__(256) void ingest_hpass_kernel(const unsigned char* 
 }
 
 // one thread per output pixel (frame, yy, x): the vertical pass (bounds == NULL: the height is unchanged, no pass) + the table
-// conversion into three fp32 planes
+// conversion into three fp32 planes (channel c reads lut[c * lut_stride + v]: stride 0 = one table for all three)
 __global__ __launch_bounds__(256) void ingest_vpass_kernel(const unsigned char* __restrict__ in, float* __restrict__ out,
                                                             const int* __restrict__ bounds, const int* __restrict__ coef, int ksize,
-                                                            const float* __restrict__ lut, int n, int Hs, int H, int W) {
+                                                            const float* __restrict__ lut, int lut_stride, int n, int Hs, int H,
+                                                            int W) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   const long plane = (long)H * W;
   if (i >= (long)n * plane) return;
@@ -1200,13 +1201,13 @@ __global__ __launch_bounds__(256) void ingest_vpass_kernel(const unsigned char* 
   }
   float* o = out + (long)f * 3 * plane + p;
   o[0] = lut[v0];
-  o[plane] = lut[v1];
-  o[2 * plane] = lut[v2];
+  o[plane] = lut[lut_stride + v1];
+  o[2 * plane] = lut[2 * lut_stride + v2];
 }
 
-extern "C" int stswin_frame_ingest(const unsigned char* in, unsigned char* tmp, float* out, int n, int Hs, int Ws, int H, int W,
-                                   const int* hbounds, const int* hcoef, int hksize, const int* vbounds, const int* vcoef,
-                                   int vksize, const float* lut, void* stream) {
+static int frame_ingest_impl(const unsigned char* in, unsigned char* tmp, float* out, int n, int Hs, int Ws, int H, int W,
+                             const int* hbounds, const int* hcoef, int hksize, const int* vbounds, const int* vcoef, int vksize,
+                             const float* lut, int lut_stride, void* stream) {
   if (n <= 0 || Hs <= 0 || Ws <= 0 || H <= 0 || W <= 0) return -1801;
   if (in == nullptr || out == nullptr || lut == nullptr) return -1802;
   const bool hpass = Ws != W, vpass = Hs != H;
@@ -1223,9 +1224,22 @@ extern "C" int stswin_frame_ingest(const unsigned char* in, unsigned char* tmp, 
   }
   const long total = (long)n * H * W;
   hipLaunchKernelGGL(ingest_vpass_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, vin, out,
-                     vpass ? vbounds : nullptr, vcoef, vksize, lut, n, Hs, H, W);
+                     vpass ? vbounds : nullptr, vcoef, vksize, lut, lut_stride, n, Hs, H, W);
   STSWIN_CHECK_LAUNCH();
   return 0;
+}
+
+extern "C" int stswin_frame_ingest(const unsigned char* in, unsigned char* tmp, float* out, int n, int Hs, int Ws, int H, int W,
+                                   const int* hbounds, const int* hcoef, int hksize, const int* vbounds, const int* vcoef,
+                                   int vksize, const float* lut, void* stream) {
+  return frame_ingest_impl(in, tmp, out, n, Hs, Ws, H, W, hbounds, hcoef, hksize, vbounds, vcoef, vksize, lut, 0, stream);
+}
+
+// The same with one table per RGB plane, lut [3][256] (segcata/dataset/CATA_new_512.py:228-229: (u / 255. - MEAN[c]) / STD[c]).
+extern "C" int stswin_frame_ingest_planes(const unsigned char* in, unsigned char* tmp, float* out, int n, int Hs, int Ws, int H, int W,
+                                          const int* hbounds, const int* hcoef, int hksize, const int* vbounds, const int* vcoef,
+                                          int vksize, const float* lut, void* stream) {
+  return frame_ingest_impl(in, tmp, out, n, Hs, Ws, H, W, hbounds, hcoef, hksize, vbounds, vcoef, vksize, lut, 256, stream);
 }
 
 // Clip assembly from a frame-feature ring: unit u < B*4 writes clip frame u (= clip u / 4, position u % 4) from

@@ -1319,6 +1319,39 @@ def upsample_argmax(logits, H, W, gt=None):
     return labels, counts
 
 
+def upsample_argmax_cm(logits, H, W, gt=None, cm=None, align_corners=True, labels=True):
+    """NCHW logits [F][nc][h][w] (bf16 / fp32, nc <= 64) -> uint8 labels [F][H][W] of the bilinear resize (align_corners as
+    F.interpolate) + argmax, or None with labels=False.  With gt (int64 [F][H][W]) and cm (int64 [ncm][ncm] on the device) every
+    pixel with gt and label in [0, ncm) adds 1 to cm[gt][label]; cm is accumulated, not cleared (include/stswin_hip.h,
+    stswin_upsample_argmax_cm)."""
+    if logits.dim() != 4:
+        raise StswinHipError(f"upsample_argmax_cm: logits must be [F][nc][h][w], got {tuple(logits.shape)}")
+    F_, nc, h, w = logits.shape
+    if not 1 <= nc <= 64:
+        raise StswinHipError(f"upsample_argmax_cm: {nc} classes, the kernel takes 1 .. 64")
+    if (gt is None) != (cm is None):
+        raise StswinHipError("upsample_argmax_cm: gt and cm go together")
+    if gt is None and not labels:
+        raise StswinHipError("upsample_argmax_cm: neither labels nor a confusion matrix asked for")
+    ncm = 0
+    if gt is not None:
+        if gt.dtype != torch.int64 or tuple(gt.shape) != (F_, H, W) or gt.device != logits.device:
+            raise StswinHipError(f"upsample_argmax_cm: gt must be int64 [{F_}][{H}][{W}] on {logits.device}, got {gt.dtype} "
+                                 f"{tuple(gt.shape)} on {gt.device}")
+        if cm.dtype != torch.int64 or cm.dim() != 2 or cm.shape[0] != cm.shape[1] or not cm.is_contiguous() or cm.device != logits.device:
+            raise StswinHipError(f"upsample_argmax_cm: cm must be contiguous int64 [ncm][ncm] on {logits.device}, got {cm.dtype} "
+                                 f"{tuple(cm.shape)}")
+        ncm = cm.shape[0]
+        if not 1 <= ncm <= 64:
+            raise StswinHipError(f"upsample_argmax_cm: a {ncm} x {ncm} matrix, the kernel takes 1 .. 64 classes")
+        gt = gt.contiguous()
+    lg = logits.contiguous()
+    out = torch.empty(F_, H, W, dtype=torch.uint8, device=logits.device) if labels else None
+    _check(load().stswin_upsample_argmax_cm(_dt(lg), _p(lg), _p(out), _p(gt), _p(cm), ncm, 1 if align_corners else 0, F_, nc, h, w,
+                                            H, W, _stream()), "upsample_argmax_cm")
+    return out
+
+
 def _int_table(t: Optional[torch.Tensor], rows: int, what: str):
     if t is None:
         raise StswinHipError(f"frame_ingest: the {what} table is missing")
@@ -1329,16 +1362,18 @@ def _int_table(t: Optional[torch.Tensor], rows: int, what: str):
 
 def frame_ingest(frames: torch.Tensor, out: torch.Tensor, lut: torch.Tensor, htab=None, vtab=None, tmp: Optional[torch.Tensor] = None):
     """uint8 HWC frames [n][Hs][Ws][3] -> fp32 NCHW images `out` [n][3][H][W], Pillow BILINEAR resize + the 256-entry value
-    table `lut` (include/stswin_hip.h, stswin_frame_ingest).  htab / vtab = (bounds int32 [W|H][2], coef int32 [W|H][k]) for a
-    width / height that changes; tmp = uint8 [n][Hs][W][3] when the width changes."""
+    table `lut` (include/stswin_hip.h, stswin_frame_ingest), or with lut fp32 [3][256] one table per RGB plane
+    (stswin_frame_ingest_planes).  htab / vtab = (bounds int32 [W|H][2], coef int32 [W|H][k]) for a width / height that changes;
+    tmp = uint8 [n][Hs][W][3] when the width changes."""
     if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3 or not frames.is_contiguous():
         raise StswinHipError(f"frame_ingest: frames must be contiguous uint8 [n][Hs][Ws][3], got {frames.dtype} {tuple(frames.shape)}")
     n, Hs, Ws, _ = frames.shape
     if out.dtype != torch.float32 or out.dim() != 4 or tuple(out.shape[:2]) != (n, 3) or not out.is_contiguous():
         raise StswinHipError(f"frame_ingest: out must be contiguous fp32 [{n}][3][H][W], got {out.dtype} {tuple(out.shape)}")
     H, W = out.shape[2:]
-    if lut.dtype != torch.float32 or lut.numel() != 256 or not lut.is_contiguous():
-        raise StswinHipError("frame_ingest: lut must be 256 contiguous fp32 values")
+    planes = lut.dim() == 2
+    if lut.dtype != torch.float32 or not lut.is_contiguous() or tuple(lut.shape) not in ((256,), (3, 256)):
+        raise StswinHipError(f"frame_ingest: lut must be contiguous fp32 [256] or [3][256], got {lut.dtype} {tuple(lut.shape)}")
     hb = hc = vb = vc = None
     hk = vk = 0
     if Ws != W:
@@ -1349,8 +1384,9 @@ def frame_ingest(frames: torch.Tensor, out: torch.Tensor, lut: torch.Tensor, hta
     if Hs != H:
         vb, vc = _int_table(vtab[0] if vtab else None, H, "vertical bounds"), _int_table(vtab[1] if vtab else None, H, "vertical weight")
         vk = vc.shape[1]
-    _check(load().stswin_frame_ingest(_p(frames), _p(tmp if Ws != W else None), _p(out), n, Hs, Ws, H, W, _p(hb), _p(hc), hk,
-                                      _p(vb), _p(vc), vk, _p(lut), _stream()), "frame_ingest")
+    entry = load().stswin_frame_ingest_planes if planes else load().stswin_frame_ingest
+    _check(entry(_p(frames), _p(tmp if Ws != W else None), _p(out), n, Hs, Ws, H, W, _p(hb), _p(hc), hk, _p(vb), _p(vc), vk, _p(lut),
+                 _stream()), "frame_ingest")
     return out
 
 

@@ -146,3 +146,18 @@ def load_model_full_fortest(model, pretrain_dir, log=True, trusted=None):
     sd = _raw_state_dict(pretrain_dir, model, trusted)
     sd = OrderedDict((k[7:] if (k.startswith('module') and not k.startswith('module_list')) else k, v) for k, v in sd.items())
     return _after_load(_merge_into(model, sd, log))
+
+
+# ------------------------------------------------------------------ the CaDIS package's names (segcata/utils/LoadModel.py)
+def load_model_test(model, pretrain_dir, log=True, trusted=None):
+    """segcata/utils/LoadModel.py:101-136 (imported by cata_test.py:15): the key handling of ``load_model_full_fortest``, every
+    ``module*`` key but ``module_list*`` loses its first 7 characters."""
+    return load_model_full_fortest(model, pretrain_dir, log, trusted)
+
+
+def load_model_cata(model, pretrain_dir, log=True, trusted=None):
+    """segcata/utils/LoadModel.py:6-24 (imported, never called, by train_cata_swin.py:18): builds the state-dict of ``load_model``,
+    where only ``module.resnet*`` keys lose their DataParallel prefix, and ends there - the reference's function merges nothing and
+    returns None.  This one finishes the job: the shape-checked merge of that state-dict, and the model is returned.  Which keys
+    that takes is pinned against the dict the reference builds (tests/golden/cata_metrics.npz)."""
+    return load_model(model, pretrain_dir, log, trusted)

@@ -23,6 +23,12 @@ depend on the clip around it.  VideoSegmenter therefore
 Which clips are ready after each frame, which slots they read and which slots the new frames take is decided on the host by
 ClipPlanner (pure Python).  With batch 1 a clip is released when its last frame arrives: frame 3 -> {0}, 4 -> {1, 4}, 5 -> {2, 5},
 6 -> {3, 6}, f >= 7 -> {f}.  A sequence needs at least 7 frames (frame 3's clip reads frame 6).
+
+protocol="cadis" evaluates as segcata/cata_test.py:115-170 does over segcata/dataset/CATA_new_512.py:155-158, 192-195, 228-237:
+the clip rule is `f > t` (frames f+3 .. f for f <= 4: frame 3 -> {0}, 4 -> {1}, 5 -> {2, 5}, 6 -> {3, 6}, 7 -> {4, 7}, f >= 8 -> {f};
+at least 8 frames), the input values are (u / 255. - MEAN[c]) / STD[c] per channel (a [3][256] table), the labels come from a
+bilinear resize with align_corners=False to the original 540 x 960, and with gt the segmenter accumulates one confusion matrix
+over every frame of every sequence (stswin_upsample_argmax_cm; reset_metrics() clears it, confusion_matrix() reads it).
 """
 from __future__ import annotations
 
@@ -36,23 +42,37 @@ from . import hip
 from .hip import StswinHipError
 
 T = 4                   # frames per clip (the model asserts T == 4)
+RULES = ("endovis18", "cadis")
 
 
-def clip_frames(f: int, t: int = T) -> Tuple[int, ...]:
-    """The frames of frame f's clip in clip order (Endovis2018_new.py:119-124)."""
-    if t > f:
+def _check_rule(rule: str) -> None:
+    if rule not in RULES:
+        raise StswinHipError(f"clip rule must be one of {RULES}, got {rule!r}")
+
+
+def clip_frames(f: int, t: int = T, rule: str = "endovis18") -> Tuple[int, ...]:
+    """The frames of frame f's clip in clip order: Endovis2018_new.py:119-124 (`t > f` reads forward), or under rule="cadis"
+    CATA_new_512.py:155-158 (`f > t`: frame t = 4 reads forward too)."""
+    forward = f <= t if rule == "cadis" else t > f
+    if forward:
         return tuple(range(f + t - 1, f - 1, -1))
     return tuple(range(f - t + 1, f + 1))
 
 
-def ready_at(f: int) -> List[int]:
+def ready_at(f: int, rule: str = "endovis18") -> List[int]:
     """The clips whose last missing frame is frame f, in release order."""
     out = []
-    if T - 1 <= f <= 2 * T - 2:           # clip f - 3 < 4 reads f - 3 .. f
+    last_forward = T if rule == "cadis" else T - 1     # the last clip that reads forward, f + 3 .. f
+    if T - 1 <= f <= last_forward + T - 1:             # clip f - 3 reads f - 3 .. f
         out.append(f - (T - 1))
-    if f >= T:
+    if f > last_forward:
         out.append(f)
     return out
+
+
+def min_frames(rule: str = "endovis18") -> int:
+    """The shortest sequence the rule can segment (the last clip that reads forward reads frame min_frames - 1)."""
+    return 2 * T if rule == "cadis" else 2 * T - 1
 
 
 class Step:
@@ -79,9 +99,11 @@ class ClipPlanner:
     ring while a clip that still has to run reads it: the clips of frames >= F (F = frames pushed) read frames >= F - 3, so the
     ring holds those and the frames of ready clips not yet run.  No step stores into a slot it reads."""
 
-    def __init__(self, batch: int = 1, slots: Optional[int] = None):
+    def __init__(self, batch: int = 1, slots: Optional[int] = None, rule: str = "endovis18"):
         if batch < 1:
             raise StswinHipError(f"batch must be >= 1, got {batch}")
+        _check_rule(rule)
+        self.rule = rule
         self.batch = batch
         self.slots = slots if slots is not None else max(2 * T - 1, batch + T - 1)
         if self.slots < max(2 * T - 1, batch + T - 1):
@@ -101,16 +123,16 @@ class ClipPlanner:
             f = self.seen
             self.seen += 1
             self.unprocessed.append(f)
-            self.pending.extend(ready_at(f))
+            self.pending.extend(ready_at(f, self.rule))
             while len(self.pending) >= self.batch:
                 steps.append(self._step([self.pending.popleft() for _ in range(self.batch)]))
         return steps
 
     def finish(self) -> List[Step]:
-        short = [g for g in range(min(T, self.seen)) if max(clip_frames(g)) >= self.seen]
+        short = [g for g in range(min(T + 1, self.seen)) if max(clip_frames(g, rule=self.rule)) >= self.seen]
         if short:
             raise StswinHipError(f"a sequence of {self.seen} frames is too short: the clip of frame {short[0]} reads frames "
-                                 f"{clip_frames(short[0])} (the reference's rule needs >= {2 * T - 1} frames)")
+                                 f"{clip_frames(short[0], rule=self.rule)} (the reference's rule needs >= {min_frames(self.rule)} frames)")
         steps = []
         while self.pending:
             steps.append(self._step([self.pending.popleft() for _ in range(min(self.batch, len(self.pending)))]))
@@ -122,7 +144,7 @@ class ClipPlanner:
         sources = []
         for g in clips:
             src = []
-            for fr in clip_frames(g):
+            for fr in clip_frames(g, rule=self.rule):
                 if fr in pos:
                     src.append(-1 - pos[fr])
                 elif fr in self.slot_of:
@@ -130,7 +152,7 @@ class ClipPlanner:
                 else:                                                   # (a planner bug, not a user error)
                     raise AssertionError(f"frame {fr} of clip {g} is neither new nor in the ring")
             sources.append(src)
-        needed = {fr for g in self.pending for fr in clip_frames(g)}
+        needed = {fr for g in self.pending for fr in clip_frames(g, rule=self.rule)}
         needed.update(range(max(0, self.seen - (T - 1)), self.seen))
         read = {e for src in sources for e in src if e >= 0}
         for fr in [fr for fr in self.slot_of if fr not in needed]:
@@ -159,6 +181,18 @@ class ClipPlanner:
 # not to u * (1 / 255.f) (126 differ)
 VALUE_TABLE = (np.arange(256, dtype=np.float64) / 255.).astype(np.float32)
 _PRECISION_BITS = 22
+
+# CaDIS (CATA_new_512.py:21-22, 228-229): float32 MEAN / STD arrays, `imgs / 255.` in float64, `(imgs - mean) / std` promoted to
+# float64, `.float()` at cata_test.py:125
+CADIS_MEAN = np.array([0.40789654, 0.44719302, 0.47026115], dtype=np.float32)
+CADIS_STD = np.array([0.28863828, 0.27408164, 0.27809835], dtype=np.float32)
+CADIS_SIZE = (540, 960)   # the CaDIS frames' size, which cata_test.py:129 resizes the logits back to
+
+
+def cadis_value_table() -> np.ndarray:
+    """fp32 [3][256]: the CaDIS value of byte u in RGB plane c, computed in float64 as the reference does, then cast."""
+    u = np.arange(256, dtype=np.float64) / 255.
+    return ((u[None, :] - CADIS_MEAN.astype(np.float64)[:, None]) / CADIS_STD.astype(np.float64)[:, None]).astype(np.float32)
 
 
 def bilinear_coeffs(in_size: int, out_size: int) -> Tuple[np.ndarray, np.ndarray]:
@@ -198,17 +232,19 @@ def _tables(in_size: int, out_size: int, device):
     return tab
 
 
-def _lut(device):
-    t = _LUTS.get(str(device))
+def _lut(device, protocol: str = "endovis18"):
+    """The value table of a protocol on a device: a persistent tensor (a captured graph reads it)."""
+    key = (protocol, str(device))
+    t = _LUTS.get(key)
     if t is None:
-        t = _LUTS[str(device)] = torch.from_numpy(VALUE_TABLE).to(device)
+        t = _LUTS[key] = torch.from_numpy(cadis_value_table() if protocol == "cadis" else VALUE_TABLE).to(device)
     return t
 
 
-def ingest(frames: torch.Tensor, size: Tuple[int, int], out: Optional[torch.Tensor] = None) -> torch.Tensor:
+def ingest(frames: torch.Tensor, size: Tuple[int, int], out: Optional[torch.Tensor] = None, protocol: str = "endovis18") -> torch.Tensor:
     """uint8 RGB frames [n][Hs][Ws][3] on the GPU -> fp32 images [n][3][H][W] (the stem's input): PIL.Image.resize((W, H),
-    Image.BILINEAR) bit for bit, then float32(u / 255.).  One or two launches (horizontal pass into a uint8 intermediate when the
-    width changes, vertical pass + conversion)."""
+    Image.BILINEAR) bit for bit, then float32(u / 255.) (protocol="cadis": the per-plane cadis_value_table()).  One or two launches
+    (horizontal pass into a uint8 intermediate when the width changes, vertical pass + conversion)."""
     H, W = size
     n, Hs, Ws, _ = frames.shape
     dev = frames.device
@@ -217,7 +253,7 @@ def ingest(frames: torch.Tensor, size: Tuple[int, int], out: Optional[torch.Tens
     htab = _tables(Ws, W, dev) if Ws != W else None
     vtab = _tables(Hs, H, dev) if Hs != H else None
     tmp = torch.empty(n * Hs * W * 3, dtype=torch.uint8, device=dev) if Ws != W else None
-    return hip.frame_ingest(frames, out, _lut(dev), htab, vtab, tmp)
+    return hip.frame_ingest(frames, out, _lut(dev, protocol), htab, vtab, tmp)
 
 
 # ----------------------------------------------------------------------------------------------- the segmenter
@@ -268,14 +304,25 @@ class VideoSegmenter:
     view of the graph's output buffer that the next push overwrites (clone what you keep); earlier replayed results of the same
     push are copies, and segment_sequence returns copies.
 
+    protocol="cadis" (segcata/cata_test.py:115-170): the CaDIS clip rule and per-channel normalisation, labels of a bilinear
+    resize with align_corners=False (pass align_corners=True for the training-time validation form, train_cata_swin.py:203) to
+    out_size, default (540, 960).  With gt the result is the labels (or logits) alone, and every pixel of the frame is counted into a
+    device int64 confusion matrix of metric_classes classes (default: the model's classes - 1, the last one being the remapped ignore
+    label, CATA_new_512.py:237) that pools all frames of all sequences, as cata_test.py does: reset() keeps it, reset_metrics() clears
+    it, confusion_matrix() returns it as float64 numpy (utils.cata_metrics.ConfusionMatrix.get_confusion_matrix()).
+
     Runs under torch.no_grad().  Refuses (StswinHipError): a model in train mode, a model or frames not on the GPU, a frame size
     that differs from the earlier frames'."""
 
-    def __init__(self, model, batch: int = 1, out: str = "logits", out_size: Optional[Sequence[int]] = None, graph: bool = False):
+    def __init__(self, model, batch: int = 1, out: str = "logits", out_size: Optional[Sequence[int]] = None, graph: bool = False,
+                 protocol: str = "endovis18", metric_classes: Optional[int] = None, align_corners: Optional[bool] = None):
         if out not in ("logits", "labels"):
             raise StswinHipError(f"out must be 'logits' or 'labels', got {out!r}")
         if graph and batch != 1:
             raise StswinHipError("graph replay runs the online step: batch must be 1")
+        _check_rule(protocol)
+        if protocol == "endovis18" and (align_corners is False or metric_classes is not None):
+            raise StswinHipError("align_corners=False and metric_classes belong to protocol='cadis'")
         self.model = model
         self._check_train()
         if any(not p.is_cuda for p in model.parameters()):
@@ -285,9 +332,19 @@ class VideoSegmenter:
         self.size = (8 * ir[0], 8 * ir[1])
         self.batch = batch
         self.out = out
-        self.out_size = tuple(out_size) if out_size is not None else self.size
+        self.protocol = protocol
+        self.cadis = protocol == "cadis"
+        default_size = CADIS_SIZE if self.cadis else self.size
+        self.out_size = tuple(out_size) if out_size is not None else default_size
+        self.align_corners = True if align_corners is None and not self.cadis else bool(align_corners)
+        self.metric_classes = None
+        if self.cadis:
+            self.metric_classes = metric_classes if metric_classes is not None else model.classifier[-1].out_channels - 1
+            if not 1 <= self.metric_classes <= 64:
+                raise StswinHipError(f"metric_classes must be 1 .. 64, got {self.metric_classes}")
+        self._cm = None
         self.graph = graph
-        self.planner = ClipPlanner(batch)
+        self.planner = ClipPlanner(batch, rule=protocol)
         self.frame_shape = None
         self._ring = None
         self._pinned = _Pinned()
@@ -303,6 +360,19 @@ class VideoSegmenter:
         self.planner.reset()
         self._frames = {}                 # frame index -> (uint8 tensor [k][Hs][Ws][3], GPU or CPU, row) until its ResNet pass
         self._gt = {}
+
+    def reset_metrics(self) -> None:
+        """protocol="cadis": clear the confusion matrix (reset() keeps it: it pools every sequence of an evaluation)."""
+        if self._cm is not None:
+            self._cm.zero_()
+
+    def confusion_matrix(self) -> np.ndarray:
+        """protocol="cadis": the pooled confusion matrix, float64 [metric_classes][metric_classes], rows gt, columns prediction."""
+        if not self.cadis:
+            raise StswinHipError("confusion_matrix() belongs to protocol='cadis'")
+        if self._cm is None:
+            return np.zeros((self.metric_classes, self.metric_classes))
+        return self._cm.cpu().numpy().astype(np.float64)
 
     # ----------------------------------------------------------------------------------------- public
     def push(self, frames, gt=None) -> List[Tuple[int, object]]:
@@ -380,7 +450,7 @@ class VideoSegmenter:
             while j + k < len(new) and self._frames[new[j + k]][0] is src and self._frames[new[j + k]][1] == r0 + k:
                 self._frames.pop(new[j + k])
                 k += 1
-            ingest(self._put_frames(src, r0, k), self.size, out[j:j + k])
+            ingest(self._put_frames(src, r0, k), self.size, out[j:j + k], self.protocol)
             j += k
         return out
 
@@ -408,11 +478,21 @@ class VideoSegmenter:
         hip.clip_assemble(self._ring, tok, clips, table, B, n_new)
         logits = m.forward_frame_tokens(clips, h, w, self.size[0], self.size[1])
         if labels:
-            return logits, hip.upsample_argmax(logits, *self.out_size)[0]
+            return logits, self._labels(logits)
         return logits, None
 
+    def _labels(self, logits: torch.Tensor, gt: Optional[torch.Tensor] = None, want: bool = True) -> Optional[torch.Tensor]:
+        if not self.cadis:
+            return hip.upsample_argmax(logits, *self.out_size)[0]
+        cm = None
+        if gt is not None:
+            if self._cm is None:
+                self._cm = torch.zeros(self.metric_classes, self.metric_classes, dtype=torch.int64, device=self.device)
+            cm = self._cm
+        return hip.upsample_argmax_cm(logits, *self.out_size, gt=gt, cm=cm, align_corners=self.align_corners, labels=want)
+
     def _steady(self, st: Step) -> bool:
-        return len(st.new) == 1 and len(st.clips) == 1 and st.clips[0] == st.new[0] and st.clips[0] >= 2 * T - 1
+        return len(st.new) == 1 and len(st.clips) == 1 and st.clips[0] == st.new[0] and st.clips[0] >= min_frames(self.protocol)
 
     def _run_all(self, steps: List[Step]) -> List[Tuple[int, object]]:
         res = []
@@ -448,7 +528,7 @@ class VideoSegmenter:
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
-                logits, labels = self._compute(ingest(u8, self.size), table, 1, 1, want_labels)
+                logits, labels = self._compute(ingest(u8, self.size, protocol=self.protocol), table, 1, 1, want_labels)
                 logits = logits.clone()
             torch.cuda.current_stream().wait_stream(side)
             torch.cuda.synchronize()
@@ -456,7 +536,7 @@ class VideoSegmenter:
             graph = torch.cuda.CUDAGraph()
             autocast = torch.is_autocast_enabled()
             with torch.cuda.graph(graph):
-                out, out_labels = self._compute(ingest(u8, self.size), table, 1, 1, want_labels)
+                out, out_labels = self._compute(ingest(u8, self.size, protocol=self.protocol), table, 1, 1, want_labels)
             self._g = (graph, u8, table, out, out_labels, want_labels, autocast)
             return logits, labels, False
         graph, u8, table, out, out_labels, _, autocast = g
@@ -475,7 +555,11 @@ class VideoSegmenter:
             gt = self._gt.pop(g, None)
             lg = logits[b]
             if gt is None:
-                res.append((g, lg if self.out == "logits" else hip.upsample_argmax(logits[b:b + 1], *self.out_size)[0][0]))
+                res.append((g, lg if self.out == "logits" else self._labels(logits[b:b + 1])[0]))
+                continue
+            if self.cadis:
+                lab = self._labels(logits[b:b + 1], gt, want=self.out == "labels")
+                res.append((g, lg if self.out == "logits" else lab[0]))
                 continue
             from .utils.EndoMetric import predict_and_score
             lab, dices, ious = predict_and_score(logits[b:b + 1], self.out_size, gt)

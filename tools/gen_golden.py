@@ -600,6 +600,74 @@ def gen_loadmodel():
     save("loadmodel.npz", **res)
 
 
+def gen_cata_metrics():
+    """The CaDIS evaluation (segcata): the REFERENCE's utils/cata_metrics.py on the seeded mask pairs of tests/cata_ref_inputs.py
+    for 8 / 17 / 25 classes (confusion matrix, PA, PAC and mIoU with their per-class vectors), and its two loader names
+    (segcata/utils/LoadModel.py) on the toy model / files of golden_util: load_model_test as the seg18 loaders are recorded, and for
+    load_model_cata, which returns None without loading, the keys of the state-dict it builds."""
+    import collections
+    import tempfile
+    import cata_ref_inputs as ci
+    _purge(["utils"])
+    sys.path[:] = [p for p in sys.path if not p.startswith(REF)]
+    sys.path.insert(0, os.path.join(REF, "segcata"))
+    CM = importlib.import_module("utils.cata_metrics")
+    LM = importlib.import_module("utils.LoadModel")
+    res = {}
+    for i, ncm in enumerate(ci.CLASS_COUNTS):
+        seed = 1000 + i
+        pairs = ci.mask_pairs(ncm, seed)
+        gts, preds = [g for g, _ in pairs], [p for _, p in pairs]
+        pa, pac, pac_c, miou, miou_c = CM.segmentation_metrics(gts, preds, num_classes=ncm)
+        acc = CM.ConfusionMatrix(ncm)
+        for g, p in pairs:
+            acc.update_confusion_matrix(g, p)
+        tag = f"{ncm}/"
+        res[tag + "seed"] = np.array(seed)
+        res[tag + "cm"] = acc.get_confusion_matrix()
+        res[tag + "pa"], res[tag + "pac"], res[tag + "pac_c"] = np.array(pa), np.array(pac), np.asarray(pac_c)
+        res[tag + "miou"], res[tag + "miou_c"] = np.array(miou), np.asarray(miou_c)
+        res[tag + "iou_per_class"] = np.asarray(CM.iou_per_class_metrics(gts, preds, num_classes=ncm))
+        print(f"  {ncm} classes: PA {pa:.4f} PAC {pac:.4f} mIoU {miou:.4f}, NaN classes {np.flatnonzero(np.isnan(miou_c)).tolist()}")
+
+    real_load = torch.load
+    LM.torch = types.SimpleNamespace(load=lambda path, map_location=None: real_load(path, map_location="cpu", weights_only=False))
+    built = []
+
+    class Recording(collections.OrderedDict):
+        def __init__(self, *a, **k):
+            super().__init__(*a, **k)
+            built.append(self)
+
+    LM.OrderedDict = Recording
+    with tempfile.TemporaryDirectory() as td:
+        files = {}
+        for case, obj in gu.toy_checkpoints(gu.toy_seg_model()).items():
+            files[case] = os.path.join(td, case + ".pth")
+            torch.save(obj, files[case])
+        for fn in ("load_model_test", "load_model_cata"):
+            for case, path in files.items():
+                m = gu.toy_seg_model()
+                before = {k: v.clone() for k, v in m.state_dict().items()}
+                tag = f"{fn}/{case}"
+                built.clear()
+                try:
+                    ret = getattr(LM, fn)(m, path, log=False)
+                except Exception as e:
+                    res[tag + "/error"] = np.array(type(e).__name__)
+                    print(f"  {tag}: {type(e).__name__}")
+                    continue
+                after = m.state_dict()
+                changed = [k for k in after if not torch.equal(after[k], before[k])]
+                res[tag + "/changed"] = np.array(changed if changed else [""])
+                res[tag + "/checksum"] = np.array(float(sum(v.double().sum() for v in after.values())))
+                res[tag + "/returns_model"] = np.array(ret is m)
+                res[tag + "/built"] = np.array(list(built[0].keys()) if built and built[0] else [""])
+                print(f"  {tag}: {len(changed)} keys taken from the file, {len(built[0]) if built else 0} keys built, "
+                      f"returns the model: {ret is m}")
+    save("cata_metrics.npz", **res)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default=None)
@@ -611,6 +679,10 @@ def main():
 
     if want("loadmodel"):
         gen_loadmodel()
+    if want("cata_metrics"):
+        gen_cata_metrics()
+    if a.only == "cata_metrics":
+        return
     swin, base, aspp_mod, losses = import_seg()
     if want("index_maps"):
         gen_index_maps(swin)
