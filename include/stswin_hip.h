@@ -431,14 +431,19 @@ int stswin_logits_upsample(int dtype, const void* tokens, long ldt, void* nchw, 
                            int nc, int backward, void* stream);
 
 /* ---- a15: OHEM cross entropy (seg18/utils/losses.py:32-40).  ce_fwd: per-pixel CE (ignore_index -> 0) and
- * stats (fp32 [4], zeroed by the caller, 8-byte aligned): [0] = #(loss > thresh) (an exact integer count), [2..3] = one unsigned 64-bit
- * sum of those losses in 2^-32 fixed point (integer atomics: associative, so the value is reproducible).  ce_bwd: dlogits = gscale[0] * sel[1] * (softmax - onehot) for
- * pixels with loss > sel[0] (>= when sel[2] != 0); sel/gscale live on the device, so no host sync is needed. */
+ * stats (fp32 [4], zeroed by the caller, 8-byte aligned): [0] = #(loss > thresh) (an exact integer count), [1] = #pixels whose label
+ * is neither ignore_index nor in [0, nc) (their loss is NaN and the logits are not read at such a label; ohem_select then returns
+ * NaN), [2..3] = one unsigned 64-bit sum of the counted losses in 2^-32 fixed point (integer atomics: associative, so the value is
+ * reproducible).  ce_bwd: dlogits = gscale[0] * w * (softmax - onehot), w = sel[1] for pixels with loss > sel[0], sel[3] for loss
+ * == sel[0], else 0 (and 0 at ignore_index or an out-of-range label); sel/gscale live on the device, so no host sync is needed. */
 int stswin_ce_fwd(int dtype, const void* logits, const long* labels, float* loss, float* stats, int frames, long HW, int nc,
                   int ignore_index, float thresh, void* stream);
-/* The selection of losses.py:35-39 without the sort: value[0] = OHEM loss, sel[3] = (cut, 1/count, inclusive) for ce_bwd.
- * stats = output of ce_fwd; if stats[0] = #(loss > thresh) > n_min the threshold branch is taken, otherwise the mean of the
- * n_min largest losses is computed by an exact 3-level radix select (counts + sums per bin).  work: caller-owned scratch
+/* The selection of losses.py:35-39 without the sort: value[0] = OHEM loss, sel[4] = (cut, weight above the cut, top-n_min branch
+ * taken, weight at the cut) for ce_bwd.  stats = output of ce_fwd; if stats[0] = #(loss > thresh) > n_min the threshold branch is
+ * taken (cut = thresh, 1/count above it, 0 at it), otherwise the mean of the n_min largest losses is computed by an exact 3-level
+ * radix select (counts + sums per bin): cut = the k-th largest loss, 1/n_min above it, and the t losses tied AT the cut share the
+ * k_rem places left, k_rem / (t * n_min) each (the reference's gradient averaged over the orders of the ties).  value[0] is NaN when
+ * stats[1] != 0 (labels outside [0, nc)).  work: caller-owned scratch
  * of >= STSWIN_OHEM_WORK_BYTES bytes (zeroed by the call). */
 #define STSWIN_OHEM_WORK_BYTES (3 * 2048 * 12 + 48)
 int stswin_ohem_select(const float* loss, long n, long n_min, float thresh, const float* stats, void* work, long work_bytes,

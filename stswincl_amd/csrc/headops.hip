@@ -487,8 +487,10 @@ __global__ __launch_bounds__(256) void logits_up_bwd_kernel(const TO* dout, T* d
 }
 
 // ----------------------------------------------------------------------------------------- OHEM cross entropy
-// per-pixel CE (ignore_index -> 0) + the two scalars the OHEM rule needs: stats[0] = #(loss > thresh),
-// stats[1] = sum of those losses.   losses.py:32-34.
+// per-pixel CE (ignore_index -> 0) + the scalars the OHEM rule needs: stats[0] = #(loss > thresh), stats[2..3] = sum of those
+// losses (fixed point, below).   losses.py:32-34.  A label outside [0, nc) that is not ignore_index (the reference raises) is never
+// used as an index: its loss is NaN (so it is neither counted nor selected, and ce_bwd gives it no gradient) and stats[1] counts it,
+// which makes ohem_final_kernel return NaN - the error reaches the caller without a host sync.
 DEVI unsigned long long loss_to_fix(float v) { return (unsigned long long)((double)fmaxf(v, 0.f) * 4294967296.0); }
 DEVI float fix_to_loss(unsigned long long f) { return (float)((double)f * (1.0 / 4294967296.0)); }
 
@@ -497,28 +499,41 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const TL* logits, const lon
                                                       long HW, int nc, int ignore_index, float thresh) {
   // grid-stride over the pixels: at one pixel per thread the 4096 workgroups of a 4 x 512 x 512 batch ended in 8192 same-address
   // fp32 atomics (~40 ns each, serialised at the memory side): 114 us for a 62 MB pass
-  float hc = 0.f, hs = 0.f;
+  float hc = 0.f, hs = 0.f, nbad = 0.f;
   const long n = (long)F * HW;
   for (long px = (long)blockIdx.x * 256 + threadIdx.x; px < n; px += (long)gridDim.x * 256) {
     float l = 0.f;
     const long f = px / HW, p = px % HW;
     const long lab = labels[px];
-    if (lab != ignore_index) {
+    if (lab != ignore_index && (lab < 0 || lab >= nc)) {
+      l = __builtin_nanf("");
+      nbad += 1.f;
+    } else if (lab != ignore_index) {
       const TL* b = logits + f * nc * HW + p;
       float mx = -3.0e38f;
-      for (int c = 0; c < nc; ++c) mx = fmaxf(mx, to_f32<TL>(b[(long)c * HW]));
-      float s = 0.f;
-      for (int c = 0; c < nc; ++c) s += expf(to_f32<TL>(b[(long)c * HW]) - mx);
-      l = mx + logf(s) - to_f32<TL>(b[lab * HW]);
+      int am = 0;
+      for (int c = 0; c < nc; ++c) {
+        const float v = to_f32<TL>(b[(long)c * HW]);
+        if (v > mx) { mx = v; am = c; }
+      }
+      float s = 0.f;                                   // sum over the classes other than the arg-max: log-sum-exp = mx + log1p(s)
+      for (int c = 0; c < nc; ++c)
+        if (c != am) s += expf(to_f32<TL>(b[(long)c * HW]) - mx);
+      // loss = (mx - x[lab]) + log1p(s).  The old mx + log(1 + s) - x[lab] lost ~ulp(|mx|) / 2 when the label is the arg-max (the
+      // small log(1 + s) added to |mx| and taken back out: 1e-6 at |logit| 20 on a loss of 1e-4), and log(1 + s) itself lost s
+      // below ulp(1) / 2: both vanish here (mx - x[lab] is exact or 0; log1p keeps the relative accuracy of s)
+      l = (mx - to_f32<TL>(b[lab * HW])) + log1pf(s);
     }
     loss[px] = l;
     if (l > thresh) { hc += 1.f; hs += l; }
   }
-  float cnt = wave_sum(hc), sm = wave_sum(hs);
-  __shared__ float red[2][4];
-  if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = cnt; red[1][threadIdx.x >> 6] = sm; }
+  float cnt = wave_sum(hc), sm = wave_sum(hs), bad = wave_sum(nbad);
+  __shared__ float red[3][4];
+  if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = cnt; red[1][threadIdx.x >> 6] = sm; red[2][threadIdx.x >> 6] = bad; }
   __syncthreads();
   if (threadIdx.x == 0) {
+    const float nb = red[2][0] + red[2][1] + red[2][2] + red[2][3];
+    if (nb != 0.f) atomicAdd(stats + 1, nb);
     // stats[0]: a count (integers < 2^24: exact in fp32, so the atomic sum does not depend on the order); the SUM goes to the 64-bit
     // fixed-point accumulator at stats[2..3] (2^-32 units; losses are >= 0 and n * max loss < 2^32): integer adds are associative,
     // so two runs give the same bits whatever the order the workgroups finish in
@@ -527,7 +542,8 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const TL* logits, const lon
   }
 }
 
-// dlogits = g * w(px) * (softmax - onehot),  w = sel[1] if loss(px) `>`/`>=` sel[0] else 0   (sel on device: no host sync)
+// dlogits = g * w(px) * (softmax - onehot),  w = sel[1] if loss(px) > sel[0], sel[3] if loss(px) == sel[0], else 0   (sel on device:
+// no host sync; see ohem_final_kernel).  A NaN loss (a label outside [0, nc)) compares false both ways: no gradient.
 template <typename TL>
 __global__ __launch_bounds__(256) void ce_bwd_kernel(const TL* logits, const long* labels, const float* loss, const float* sel,
                                                       const float* gscale, TL* dlogits, int F, long HW, int nc,
@@ -537,8 +553,8 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const TL* logits, const lon
   const long f = px / HW, p = px % HW;
   const long lab = labels[px];
   const float l = loss[px];
-  const bool take = sel[2] != 0.f ? (l >= sel[0]) : (l > sel[0]);
-  const float wgt = (take && lab != ignore_index) ? sel[1] * gscale[0] : 0.f;
+  const float w = l > sel[0] ? sel[1] : (l == sel[0] ? sel[3] : 0.f);
+  const float wgt = (w != 0.f && lab != ignore_index && lab >= 0 && lab < nc) ? w * gscale[0] : 0.f;
   const TL* b = logits + f * nc * HW + p;
   TL* d = dlogits + f * nc * HW + p;
   if (wgt == 0.f) {
@@ -860,6 +876,10 @@ extern "C" int stswin_ce_bwd(int dtype, const void* logits, const long* labels, 
 //   mean = (sum_above + k_rem * kth) / n_min.
 // Three passes over the 4 MB loss vector (L2 resident) + one block of bookkeeping instead of a 1 M-element top-k; every
 // pass returns at once when the threshold branch is taken (stats[0] > n_min).
+// sel (for ce_bwd) = (cut, weight above the cut, 1 if the top-n_min branch was taken, weight AT the cut).  Threshold branch: cut =
+// thresh, weight 1 / n_hard above it, 0 at it.  Top-n_min branch: cut = kth, 1 / n_min above it; the t losses equal to kth share the
+// k_rem places left, k_rem / (t * n_min) each - the reference's sort-then-slice gradient averaged over the orders of the tied pixels
+// (its value, sum_above + k_rem * kth, does not depend on that order).  Level 2 resolves all 31 key bits, so its bin count is t.
 struct OhemWork {                       // zeroed by the launcher
   unsigned cnt[3][2048];
   unsigned long long sum[3][2048];      // sums of the losses per bin in 2^-32 fixed point (see loss_to_fix): integer atomics are
@@ -935,10 +955,12 @@ __global__ __launch_bounds__(256) void ohem_hist_kernel(const float* loss, long 
 __global__ __launch_bounds__(256) void ohem_final_kernel(long n_min, float thresh, const float* stats, const OhemWork* wk, float* value,
                                                          float* sel) {
   const float n_hard = stats[0];
+  const bool bad = stats[1] != 0.f;                    // labels outside [0, nc): no defined loss (ce_fwd_kernel)
   if (n_hard > (float)n_min) {                         // loss[n_min] > thresh: mean over loss > thresh
     if (threadIdx.x == 0) {
       const float inv = 1.f / fmaxf(n_hard, 1.f);
-      value[0] = fix_to_loss(*(const unsigned long long*)(stats + 2)) * inv; sel[0] = thresh; sel[1] = inv; sel[2] = 0.f;
+      value[0] = bad ? __builtin_nanf("") : fix_to_loss(*(const unsigned long long*)(stats + 2)) * inv;
+      sel[0] = thresh; sel[1] = inv; sel[2] = 0.f; sel[3] = 0.f;
     }
     return;
   }
@@ -948,7 +970,10 @@ __global__ __launch_bounds__(256) void ohem_final_kernel(long n_min, float thres
   if (threadIdx.x == 0) {
     const float kth = __uint_as_float((wk->state[2][0] << 10) | sc[0]);
     const float total = fix_to_loss(wk->sabove[2] + ssum[0]) + (float)sc[1] * kth;
-    value[0] = total / (float)n_min; sel[0] = kth; sel[1] = 1.f / (float)n_min; sel[2] = 1.f;
+    const unsigned ties = wk->cnt[2][sc[0]];           // >= k_rem = sc[1] >= 1
+    value[0] = bad ? __builtin_nanf("") : total / (float)n_min;
+    sel[0] = kth; sel[1] = 1.f / (float)n_min; sel[2] = 1.f;
+    sel[3] = (float)((double)sc[1] / ((double)ties * (double)n_min));
   }
 }
 

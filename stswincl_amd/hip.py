@@ -1145,7 +1145,7 @@ def ce_fwd(logits, labels, ignore_index, thresh):
     F_, nc = logits.shape[:2]
     HW = logits[0, 0].numel()
     loss = torch.empty(F_ * HW, dtype=torch.float32, device=logits.device)
-    stats = zeros(4, device=logits.device)          # [count, -, 64-bit fixed-point sum]: include/stswin_hip.h
+    stats = zeros(4, device=logits.device)          # [count, #labels outside [0, nc), 64-bit fixed-point sum]: include/stswin_hip.h
     _check(load().stswin_ce_fwd(_dt(logits), _p(logits), _p(labels), _p(loss), _p(stats), F_, _c_long(HW), nc, ignore_index,
                                 _c_float(thresh), _stream()), "ce_fwd")
     return loss, stats
@@ -1155,10 +1155,11 @@ _OHEM_WORK_BYTES = 3 * 2048 * 12 + 48
 
 
 def ohem_select(loss, stats, n_min: int, thresh: float):
-    """(value [1], sel [3]) of OhemCELoss2D's selection (losses.py:35-39) on the device: no sort, no host sync."""
+    """(value [1], sel [4]) of OhemCELoss2D's selection (losses.py:35-39) on the device: no sort, no host sync.
+    sel = (cut, weight above the cut, top-n_min branch taken, weight at the cut): include/stswin_hip.h."""
     work = torch.empty(_OHEM_WORK_BYTES // 4, dtype=torch.int32, device=loss.device)
     value = torch.empty((), dtype=torch.float32, device=loss.device)
-    sel = torch.empty(3, dtype=torch.float32, device=loss.device)
+    sel = torch.empty(4, dtype=torch.float32, device=loss.device)
     _check(load().stswin_ohem_select(_p(loss), _c_long(loss.numel()), _c_long(n_min), _c_float(thresh), _p(stats), _p(work),
                                      _c_long(_OHEM_WORK_BYTES), _p(value), _p(sel), _stream()), "ohem_select")
     return value, sel
