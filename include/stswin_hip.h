@@ -53,6 +53,13 @@ extern "C" {
 #define STSWIN_GF_ROT 4096      /* tuning (STSWIN_TUNING builds): 256x256 ring with the rotated ping-pong loop, one barrier per stage */
 #define STSWIN_GF_NOBIG 256     /* tuning: forbid it (default: chosen when >= 256 big tiles fill the chip) */
 #define STSWIN_GF_WAVES4 64     /* tuning: 4 waves of 64x64 per 128x128 tile instead of the default 8 waves of 64x32 */
+#define STSWIN_GF_NOREGEPI (1 << 22) /* tuning: 256x256 ring with the LDS-staged fp32 epilogue instead of the register epilogue */
+#define STSWIN_GF_NOSTREAM (1 << 23) /* tuning: 256x256 ring without the persistent streaming variant */
+#define STSWIN_GF_DUO (1 << 24)      /* tuning: 128x256 tiles, 4 waves, two workgroups per CU */
+#define STSWIN_GF_STREAM (1 << 25)   /* tuning: persistent streaming 256x256 variant (measured no faster: both wave rows idle through each other's epilogue) */
+#define STSWIN_GF_NONARROW (1 << 26) /* tuning: forbid the 256x64 tile for N <= 64 */
+#define STSWIN_GF_NODEEP (1 << 27)   /* tuning: the 128x64 few-tiles kernel with its double buffer instead of the 4-stage ring */
+#define STSWIN_GF_DEEP (1 << 28)     /* tuning: 3-stage rings for the 128x128 / 256x64 kernels too (one workgroup per CU) */
 
 int stswin_abi_version(void);
 
@@ -85,20 +92,18 @@ int stswin_stem_im2col(int dtype, const float* img, void* patches, long ld, int 
  * stswin_gemm_nt / stswin_gemm_tn with a row map [4][M], Kseg = bseg = 64 and lda = 16.  The buffer must extend 48 values past
  * the last record (the last segment reads on). */
 int stswin_stem_s2d(int dtype, const float* img, void* out, int frames, int H, int W, void* stream);
-/* Weight gradient of the stem convolution from dy (bf16 [F*Ho*Wo][64]) and the space-to-depth image `rec` of stswin_stem_s2d (bf16):
- * dw fp32 [64][4][4][16] = [cout][tap row][record][position], the order stswin_gemm_tn produces over the row map (accumulate != 0 adds).
- * Record rows pass through an LDS ring once; per-workgroup partials go to `scratch` (>= stswin_stem_wgrad_scratch floats) and are added
- * in a fixed order.  Wo = (W-1)/2 + 1 must be a multiple of 128, else -1722 and nothing is launched.  resnet.py:98-102 backward. */
 /* The stem convolution over the space-to-depth image `rec` of stswin_stem_s2d (bf16): y bf16 [F*Ho*Wo][64] = conv(7, 2, 3) with
  * wmat bf16 [64][4][4][16] (= [cout][tap row][record][position], zeros where the 7 x 7 window has no tap); stats (or NULL): the
  * STSWIN_GF_CS_SQ table of y.  Record rows pass through an LDS ring once, the weights live in registers: replaces stswin_gemm_nt
  * over the row map for this M = F*Ho*Wo, N = 64, K = 256 shape.  Wo % 128 != 0: -1732, nothing launched.  resnet.py:98-102. */
 int stswin_stem_conv(const void* rec, const void* wmat, void* y, float* stats, int frames, int H, int W, void* stream);
+/* Weight gradient of the stem convolution from dy (bf16 [F*Ho*Wo][64]) and the space-to-depth image `rec` of stswin_stem_s2d (bf16):
+ * dw fp32 [64][4][4][16] = [cout][tap row][record][position], the order stswin_gemm_tn produces over the row map (accumulate != 0 adds).
+ * Record rows pass through an LDS ring once; per-workgroup partials go to `scratch` (>= stswin_stem_wgrad_scratch floats) and are added
+ * in a fixed order.  Wo = (W-1)/2 + 1 must be a multiple of 128, else -1722 and nothing is launched.  resnet.py:98-102 backward. */
 long stswin_stem_wgrad_scratch(int frames, int Ho, int Wo);
 int stswin_stem_wgrad(const void* dy, const void* rec, float* dw, int accumulate, float* scratch, long scratch_floats, int frames, int H, int W,
                       void* stream);
-/* nn.MaxPool2d(3, 2, 1) on tokens [F][H][W][C] -> [F][Ho][Wo][C]; arg (uint8 [F*Ho*Wo][C]) = winning tap (first max in
- * (ky,kx) scan order, like torch); backward gathers dy through arg (no atomics). */
 /* (Cout, Cin, k, k) fp32 nn.Conv2d weight -> the bf16 / fp32 GEMM operand matrices of the token convolutions in one launch:
  * fwd [cop][S][cip] (tap-major K of stswin_gemm_nt) and, if not NULL, dgrad [cip][S][cop].  omap[cop] / imap[cip] = source
  * channel of each padded channel position or -1 (zero).  (ASPP.py:37-50, base18.py:60-77, resnet.py convolutions) */
@@ -114,6 +119,8 @@ int stswin_linear_pack_multi(int dtype, int count, const float* const* w, void* 
                              void* stream);
 int stswin_conv_pack_multi(int dtype, int count, const float* const* w, void* const* fwd, void* const* dgrad, const int* const* omap,
                            const int* const* imap, const int* ci, const int* S, const int* cop, const int* cip, void* stream);
+/* nn.MaxPool2d(3, 2, 1) on tokens [F][H][W][C] -> [F][Ho][Wo][C]; arg (uint8 [F*Ho*Wo][C]) = winning tap (first max in
+ * (ky,kx) scan order, like torch); backward gathers dy through arg (no atomics). */
 int stswin_maxpool3x3s2(int dtype, const void* in, long ldi, void* out, long ldo, unsigned char* arg, int frames, int H,
                         int W, int Ho, int Wo, int C, int backward, void* stream);
 /* 3x3 / stride 1 / pad 1 convolution of 64 -> 64 channels over bf16 NHWC tokens [frames*H*W][64] (torchvision resnet18.layer1 as

@@ -19,36 +19,16 @@
 #include <cstdlib>
 #include <type_traits>
 
+// The stswin_gemm_nt flag bits under their short names; include/stswin_hip.h defines and describes them.
 enum {
-  GF_GELU = 1,       // out = gelu(v); C2 (if any) receives v (pre-activation)
-  GF_RESID = 2,      // v += R[r_rows[m]][n]
-  GF_MUL_DGELU = 4,  // v *= gelu'(R[r_rows[m]][n])           (R = saved pre-activation)
-  GF_OUT_F32 = 8,    // C is float regardless of T
-  GF_ACCUM = 16,     // C += v (only with GF_OUT_F32)
-  GF_RELU = 32,
-  GF_MUL_R = 8192,        // v *= R[r_rows[m]][n]                  (R = saved GELU' values, see GF_C2_DGELU)
-  GF_C2_DGELU = 16384,    // with GF_GELU: C2 receives gelu'(v) instead of the pre-activation v, so that the backward
-                          // epilogue is one multiply (the polynomial Phi is shared with the forward GELU)
-  GF_BIG = 128,      // tuning: force the 256x256 4-stage kernel (bf16)
-  GF_NOBIG = 256,    // tuning: forbid it
-  GF_MID = 512,      // tuning: 256x128x32 tile, 3-stage ring, 2 workgroups per CU
-  GF_NOPIPE = 1024,  // tuning: 256x256 ring without the ping-pong schedule
-  GF_HALF = 2048,    // tuning: force the 256x128 ping-pong ring
-  GF_ROT = 4096,     // tuning: the rotated ping-pong loop of the 256x256 ring (one barrier per stage)   [was GF_NOHALF, never tested anywhere]
-  GF_NONARROW = 1 << 26,  // tuning: forbid the 256x64 tile for N <= 64
-  GF_STREAM = 1 << 25,    // tuning: persistent streaming 256x256 variant (measured no faster: both wave rows idle through each other's epilogue)
-  GF_DUO = 1 << 24,       // tuning: 128x256 tiles, 4 waves, two workgroups per CU
-  GF_CS_PARTIAL = 1 << 15,  // colsum is fp32 [2*ceil(M/256)][N]: row b = column sums of output rows 128b..128b+127, stored (not added)
-  GF_TAPSKIP = 1 << 29,     // tiled kernels: skip the segments (taps) whose row map has no row inside this tile (costs a 4 us map scan)
-  GF_CS_SQ = 1 << 16,       // with GF_CS_PARTIAL: a second table plane (offset 2*ceil(M/256)*N floats) receives the column sums of
-                            // SQUARES of the same values - the BatchNorm statistics of a convolution output without a pass over it
-  GF_NOSTREAM = 1 << 23,  // tuning: 256x256 ring without the persistent streaming variant
-  GF_NOREGEPI = 1 << 22,  // tuning: 256x256 ring with the LDS-staged fp32 epilogue instead of the register epilogue
-  GF_M32PP = (int)(1u << 31),   // tuning: the 8-wave ping-pong 256x256 ring on 32x32x16 MFMA tiles
-  GF_W4R = 1 << 30,       // tuning: 256x256 ring with the 4-wave register-pipelined main loop (one wave per SIMD, 128x128 wave tiles)
-  GF_WAVES4 = 64,    // tuning: 4 waves of 64x64 per tile instead of the default 8 waves of 64x32 (4 waves/SIMD)
-  GF_NODEEP = 1 << 27,    // tuning: the 128x64 few-tiles kernel with its double buffer instead of the 4-stage ring
-  GF_DEEP = 1 << 28,      // tuning: 3-stage rings for the 128x128 / 256x64 kernels too (one workgroup per CU)
+  GF_GELU = STSWIN_GF_GELU, GF_RESID = STSWIN_GF_RESID, GF_MUL_DGELU = STSWIN_GF_MUL_DGELU, GF_OUT_F32 = STSWIN_GF_OUT_F32,
+  GF_ACCUM = STSWIN_GF_ACCUM, GF_RELU = STSWIN_GF_RELU, GF_MUL_R = STSWIN_GF_MUL_R, GF_C2_DGELU = STSWIN_GF_C2_DGELU,
+  GF_CS_PARTIAL = STSWIN_GF_CS_PARTIAL, GF_CS_SQ = STSWIN_GF_CS_SQ, GF_TAPSKIP = STSWIN_GF_TAPSKIP,
+  // tuning
+  GF_WAVES4 = STSWIN_GF_WAVES4, GF_BIG = STSWIN_GF_BIG, GF_NOBIG = STSWIN_GF_NOBIG, GF_MID = STSWIN_GF_MID, GF_NOPIPE = STSWIN_GF_NOPIPE,
+  GF_HALF = STSWIN_GF_HALF, GF_ROT = STSWIN_GF_ROT, GF_NOREGEPI = STSWIN_GF_NOREGEPI, GF_NOSTREAM = STSWIN_GF_NOSTREAM,
+  GF_DUO = STSWIN_GF_DUO, GF_STREAM = STSWIN_GF_STREAM, GF_NONARROW = STSWIN_GF_NONARROW, GF_NODEEP = STSWIN_GF_NODEEP,
+  GF_DEEP = STSWIN_GF_DEEP, GF_W4R = STSWIN_GF_W4R, GF_M32PP = (int)STSWIN_GF_M32PP,
 };
 
 // Diagnosis switches of the ring kernels (flag bits 17 stagger, 18 late R, 19 timestamps through p.colsum, 20 no stores, 21 no epilogue;

@@ -6,6 +6,7 @@ every wrapper demands CUDA (ROCm) tensors.  PyTorch is used only for device memo
 from __future__ import annotations
 
 import ctypes
+import functools
 import os
 import re
 from typing import Optional
@@ -17,42 +18,69 @@ LIB_PATH = os.environ.get("STSWIN_HIP_LIB") or os.path.join(_ROOT, "stswincl_amd
 HEADER_PATH = os.path.join(_ROOT, "include", "stswin_hip.h")
 _lib: Optional[ctypes.CDLL] = None
 
-GF_GELU, GF_RESID, GF_MUL_DGELU, GF_OUT_F32, GF_ACCUM, GF_RELU, GF_WAVES4, GF_BIG, GF_NOBIG, GF_MID, GF_NOPIPE, GF_HALF, GF_ROT = 1, 2, 4, 8, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096
-GF_MUL_R, GF_C2_DGELU, GF_CS_PARTIAL = 8192, 16384, 32768
-GF_CS_SQ = 1 << 16
-GF_NOREGEPI = 1 << 22
-GF_NOSTREAM = 1 << 23
-GF_DUO = 1 << 24
-GF_STREAM = 1 << 25
-GF_NONARROW = 1 << 26
-GF_TAPSKIP = 1 << 29
-GF_M32PP = -(1 << 31)        # tuning builds: the 8-wave ping-pong ring on 32x32x16 MFMA tiles (bit 31 of the int flags word)
-GF_W4R = 1 << 30            # 256x256 ring: 4 waves of 128x128, register-pipelined main loop (32x32x16 MFMA)
-GF_NODEEP, GF_DEEP = 1 << 27, 1 << 28        # tuning: prefetch depth of the 128x64 / 128x128 / 256x64 kernels
-TN_OVERWRITE = 1 << 27
-
-_c_int, _c_long, _c_float, _c_void_p = ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_void_p
+_c_int, _c_float, _c_void_p = ctypes.c_int, ctypes.c_float, ctypes.c_void_p        # element types of the host arrays some entry points take
 
 
 class StswinHipError(RuntimeError):
     pass
 
 
+_C_TYPES = {"int": ctypes.c_int, "long": ctypes.c_long, "float": ctypes.c_float, "double": ctypes.c_double}
+
+
+def _c_value(name: str, expr: str) -> int:
+    """Value of a #define: integer literals (optional `u`), `<<`, `*`, `+`, `-` and parentheses - anything else raises.  The constants
+    cross the ABI in `int` parameters, so bit 31 is the sign bit."""
+    tokens = re.findall(r"0[xX][0-9a-fA-F]+|\d+|<<|[-+*()]|\S", re.sub(r"(?<=[0-9a-fA-F])[uU]\b", "", expr))
+    if not tokens or not all(re.fullmatch(r"0[xX][0-9a-fA-F]+|\d+|<<|[-+*()]", t) for t in tokens):
+        raise StswinHipError(f"{HEADER_PATH}: cannot evaluate `#define STSWIN_{name} {expr.strip()}`")
+    try:
+        v = int(eval(" ".join(tokens), {"__builtins__": {}}))       # (digits, shifts, products, sums and parentheses only: checked above)
+    except (SyntaxError, TypeError) as e:
+        raise StswinHipError(f"{HEADER_PATH}: cannot evaluate `#define STSWIN_{name} {expr.strip()}`") from e
+    return v - (1 << 32) if v >= 1 << 31 else v
+
+
+@functools.lru_cache(maxsize=None)
+def _header():
+    """include/stswin_hip.h, read once per process -> (prototypes {symbol: (restype, [argtypes])}, constants {NAME: value} of the
+    `#define STSWIN_NAME value` lines).  A parameter is a pointer (anything with a `*`: c_void_p) or an optionally const int / long /
+    float / double; whatever else appears is an error, never an int by default."""
+    with open(HEADER_PATH) as f:
+        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
+    protos = {}
+    for ret, name, params in re.findall(r"\b(int|long)\s+(stswin_\w+)\s*\(([^()]*)\)\s*;", text):
+        argtypes = []
+        for p in ([] if params.strip() == "void" else params.split(",")):
+            words = [w for w in p.split() if w != "const"]
+            if "*" in p:
+                argtypes.append(ctypes.c_void_p)
+            elif len(words) == 2 and words[0] in _C_TYPES:
+                argtypes.append(_C_TYPES[words[0]])
+            else:
+                raise StswinHipError(f"{HEADER_PATH}: {name}: cannot bind parameter `{p.strip()}`")
+        protos[name] = (_C_TYPES[ret], argtypes)
+    unparsed = set(re.findall(r"\b(stswin_\w+)\s*\(", text)) - set(protos)
+    if unparsed:
+        raise StswinHipError(f"{HEADER_PATH}: cannot bind the declaration of {sorted(unparsed)}")
+    consts = {name: _c_value(name, expr) for name, expr in re.findall(r"^[ \t]*#[ \t]*define[ \t]+STSWIN_(\w+)[ \t]+(\S.*)$", text, flags=re.M)}
+    return protos, consts
+
+
+# GF_* (stswin_gemm_nt flags), TN_* (bits of stswin_gemm_tn's `splits`, TN_GROUP_DECLINED), VAR_* (stswin_last_variant codes) and
+# OHEM_WORK_BYTES are the header's STSWIN_* #defines without the prefix: hip.GF_GELU == STSWIN_GF_GELU, ...
+globals().update(_header()[1])
+
+
 def declared_symbols():
     """Every entry point include/stswin_hip.h declares."""
-    with open(HEADER_PATH) as f:
-        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(?:int|long)\s+(stswin_\w+)\s*\(", text)))
-
-
-def _long_symbols():
-    with open(HEADER_PATH) as f:
-        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
-    return set(re.findall(r"\blong\s+(stswin_\w+)\s*\(", text))
+    return sorted(_header()[0])
 
 
 def load() -> ctypes.CDLL:
-    """dlopen the library and check that it exports the whole declared ABI (works without a GPU)."""
+    """dlopen the library, check that it exports the whole declared ABI and give every entry point the restype and argtypes of its
+    prototype (works without a GPU).  ctypes then converts plain ints / floats / None per parameter and refuses a wrong argument
+    count or a float where an integer is declared."""
     global _lib
     if _lib is not None:
         return _lib
@@ -60,13 +88,14 @@ def load() -> ctypes.CDLL:
         raise StswinHipError(f"{LIB_PATH} not found: run `python __graft_entry__.py` (build()) first; "
                              "stswincl_amd has no CPU or eager fallback")
     lib = ctypes.CDLL(LIB_PATH)
-    missing = [s for s in declared_symbols() if not hasattr(lib, s)]
+    protos = _header()[0]
+    missing = [s for s in sorted(protos) if not hasattr(lib, s)]
     if missing and not os.environ.get("STSWIN_HIP_LIB"):     # (an older build named for an A/B run may lack new entries)
         raise StswinHipError(f"libstswin_hip.so lacks declared symbols: {missing}")
-    longs = _long_symbols()
-    for s in declared_symbols():
+    for s, (restype, argtypes) in protos.items():
         if s not in missing:
-            getattr(lib, s).restype = _c_long if s in longs else _c_int
+            fn = getattr(lib, s)
+            fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
     return lib
 
@@ -109,28 +138,37 @@ def _dt(t: torch.Tensor) -> int:
     raise StswinHipError(f"unsupported dtype {t.dtype}")
 
 
-def _p(t: Optional[torch.Tensor]):
+def _p(t: Optional[torch.Tensor]) -> Optional[int]:
+    """Device address of t for a pointer parameter (None -> NULL)."""
     if t is None:
-        return _c_void_p(0)
+        return None
     if not t.is_cuda:
         raise StswinHipError("stswincl_amd ops need tensors on the GPU (no CPU path exists)")
-    return _c_void_p(t.data_ptr())
+    return t.data_ptr()
 
 
 _RAW_STREAM = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 
 
-def _stream():
+def _stream() -> int:
     # the raw handle of the calling thread's current stream on the current device: torch.cuda.current_stream() builds a Stream
     # object per call (9 us, ~460 calls per training step = 4 ms of host time); the private accessor is 20x cheaper
     if _RAW_STREAM is not None:
-        return _c_void_p(_RAW_STREAM(torch.cuda.current_device()))
-    return _c_void_p(torch.cuda.current_stream().cuda_stream)
+        return _RAW_STREAM(torch.cuda.current_device())
+    return torch.cuda.current_stream().cuda_stream
 
 
 def _ld(t: torch.Tensor) -> int:
     assert t.dim() == 2 and t.stride(1) == 1, "expected a row-major 2-D view"
     return t.stride(0)
+
+
+def _device(d) -> torch.device:
+    """torch.device(d) with "cuda" resolved to the current device: the key of the per-device caches below."""
+    d = torch.device(d)
+    if d.type == "cuda" and d.index is None:
+        d = torch.device("cuda", torch.cuda.current_device())
+    return d
 
 
 # ----------------------------------------------------------------------------------------------- zero arena
@@ -150,10 +188,7 @@ def arena_reset(device=None) -> None:
     if device is None:
         _ARENAS.clear()
     else:
-        device = torch.device(device)
-        if device.type == "cuda" and device.index is None:      # ("cuda" means the current device, as in zeros())
-            device = torch.device("cuda", torch.cuda.current_device())
-        _ARENAS.pop(device, None)
+        _ARENAS.pop(_device(device), None)
 
 
 def zeros(*shape, device) -> torch.Tensor:
@@ -165,9 +200,7 @@ def zeros(*shape, device) -> torch.Tensor:
         n *= int(d)
     if n > _ARENA_MAX_REQUEST or n == 0:
         return torch.zeros(shape, dtype=torch.float32, device=device)
-    device = torch.device(device)
-    if device.type == "cuda" and device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
+    device = _device(device)
     st = _ARENAS.get(device)
     need = (n + 15) // 16 * 16
     if st is None or st[1] + need > _ARENA_FLOATS:
@@ -195,9 +228,7 @@ def note_capture() -> None:
 
 
 def scratch(device, floats: int) -> torch.Tensor:
-    device = torch.device(device)
-    if device.type == "cuda" and device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
+    device = _device(device)
     floats = (int(floats) + 63) // 64 * 64
     t = _SCRATCH.get(device)
     off = _DEFER[1] if _DEFER[0] else 0
@@ -434,7 +465,7 @@ def stem_im2col(img: torch.Tensor, dtype: torch.dtype, Ho: int, Wo: int, ld: int
     F_, c, H, W = img.shape
     assert c == 3 and img.dtype == torch.float32 and img.is_contiguous()
     out = torch.empty(F_ * Ho * Wo, ld, dtype=dtype, device=img.device)
-    _check(load().stswin_stem_im2col(_dt(out), _p(img), _p(out), _c_long(ld), F_, H, W, Ho, Wo, _stream()), "stem_im2col")
+    _check(load().stswin_stem_im2col(_dt(out), _p(img), _p(out), ld, F_, H, W, Ho, Wo, _stream()), "stem_im2col")
     return out
 
 
@@ -477,14 +508,14 @@ def stem_wgrad(dy, A, dw, frames, H, W, accumulate=False):
     assert dw.dtype == torch.float32 and dw.numel() == 64 * 256 and dw.is_contiguous()
     ws = scratch(dy.device, load().stswin_stem_wgrad_scratch(frames, Ho, Wo))
     with _Span("stem_wgrad_bf16", 2.0 * frames * Ho * Wo * 64 * 147):
-        rc = load().stswin_stem_wgrad(_p(dy), _p(A), _p(dw), 1 if accumulate else 0, _p(ws), _c_long(ws.numel()), frames, H, W, _stream())
+        rc = load().stswin_stem_wgrad(_p(dy), _p(A), _p(dw), 1 if accumulate else 0, _p(ws), ws.numel(), frames, H, W, _stream())
     _check(rc, "stem_wgrad")
     return dw
 
 
 def maxpool3x3s2(src, dst, arg, frames, H, W, Ho, Wo, backward=False):
     C = src.shape[1]
-    _check(load().stswin_maxpool3x3s2(_dt(src), _p(src), _c_long(_ld(src)), _p(dst), _c_long(_ld(dst)), _p(arg), frames, H,
+    _check(load().stswin_maxpool3x3s2(_dt(src), _p(src), _ld(src), _p(dst), _ld(dst), _p(arg), frames, H,
                                       W, Ho, Wo, C, 1 if backward else 0, _stream()), "maxpool3x3s2")
     return dst
 
@@ -521,7 +552,7 @@ def conv3x3_c64_wgrad(dy, x, dw, frames, H, W, tapminor=True, accumulate=False):
     need = load().stswin_conv3x3_c64_wgrad_scratch(frames, H, W)
     ws = scratch(x.device, need)
     with _Span("conv3x3_c64_wgrad_bf16", 2.0 * M * 64 * 576):
-        rc = load().stswin_conv3x3_c64_wgrad(_p(dy), _p(x), _p(dw), 1 if tapminor else 0, 1 if accumulate else 0, _p(ws), _c_long(ws.numel()),
+        rc = load().stswin_conv3x3_c64_wgrad(_p(dy), _p(x), _p(dw), 1 if tapminor else 0, 1 if accumulate else 0, _p(ws), ws.numel(),
                                              frames, H, W, _stream())
     _check(rc, "conv3x3_c64_wgrad")
     return dw
@@ -547,7 +578,7 @@ def bn_table_finalize(table: torch.Tensor, M: int, running_mean, running_var, gr
     mean = torch.empty(groups, N, dtype=torch.float32, device=table.device)
     rstd = torch.empty_like(mean)
     _check(load().stswin_bn_table_finalize(_p(table), M, N, groups, unit, _p(mean), _p(rstd), _p(running_mean), _p(running_var),
-                                           _c_float(eps), _c_float(momentum), _stream()), "bn_table_finalize")
+                                           eps, momentum, _stream()), "bn_table_finalize")
     return mean, rstd
 
 
@@ -568,7 +599,7 @@ def gemm_nt(A: torch.Tensor, Bw: torch.Tensor, out: torch.Tensor, *, M: int, a_r
         assert colsum_out is None and stats_out.shape == (2, 2 * ((M + 255) // 256), N) and stats_out.is_contiguous()
         flags |= GF_CS_PARTIAL | GF_CS_SQ
         colsum_out = stats_out
-    elif colsum_out is not None and M >= _CS_PARTIAL_MIN_M and N % 4 == 0 and not (flags & (1 << 19)):
+    elif colsum_out is not None and M >= _CS_PARTIAL_MIN_M and N % 4 == 0 and not (flags & _GF_DEBUG_STAMPS):
         # >= 64 row tiles would each add into the same N addresses: per-block partial sums + one small reduce instead
         cs_table = scratch(A.device, 2 * ((M + 255) // 256) * N)
         flags |= GF_CS_PARTIAL
@@ -589,17 +620,17 @@ def gemm_nt(A: torch.Tensor, Bw: torch.Tensor, out: torch.Tensor, *, M: int, a_r
         if need > 0:
             ws = scratch(A.device, need)
             with _Span(name, 2.0 * M * N * Ktot):
-                rc = load().stswin_gemm_nt_splitk(_p(A), _c_long(_ld(A)), _p(a_rows), _p(Bw), _c_long(_ld(Bw)), _p(out), _c_long(_ld(out)),
-                                                  _p(bias), M, N, Kseg, S, 1 if (flags & GF_RELU) else 0, _p(ws), _c_long(ws.numel()), _stream())
+                rc = load().stswin_gemm_nt_splitk(_p(A), _ld(A), _p(a_rows), _p(Bw), _ld(Bw), _p(out), _ld(out),
+                                                  _p(bias), M, N, Kseg, S, 1 if (flags & GF_RELU) else 0, _p(ws), ws.numel(), _stream())
             if rc != -1008:                  # -1008: not a split-K candidate after all (an `out` column slice that is not 16-byte
                 _check(rc, "gemm_nt_splitk")  # aligned, a row pitch that is not a multiple of 8): the tiled kernels below take it
                 _log_variant("nt", (M, N, Kseg, S), 0)
                 return out
     with _Span(name, 2.0 * M * N * Ktot):
         rc = load().stswin_gemm_nt(
-            _dt(A), _p(A), _c_long(_ld(A)), _p(a_rows), _p(Bw), _c_long(_ld(Bw)), _p(out), _c_long(_ld(out)),
-            _p(c_rows), _p(out2), _c_long(_ld(out2) if out2 is not None else 0), _p(bias), _p(resid),
-            _c_long(_ld(resid) if resid is not None else 0), _p(r_rows), M, N, Kseg, S, _c_float(scale), scale_cols,
+            _dt(A), _p(A), _ld(A), _p(a_rows), _p(Bw), _ld(Bw), _p(out), _ld(out),
+            _p(c_rows), _p(out2), _ld(out2) if out2 is not None else 0, _p(bias), _p(resid),
+            _ld(resid) if resid is not None else 0, _p(r_rows), M, N, Kseg, S, scale, scale_cols,
             flags, _p(cs_table if cs_table is not None else colsum_out), _stream())
     _check(rc, "gemm_nt")
     _log_variant("nt", (M, N, Kseg, S), 0)
@@ -617,8 +648,8 @@ def gemm_nt_qkv_fp8(A: torch.Tensor, Bw: torch.Tensor, *, M: int, a_rows=None, b
     out8 = torch.empty(M, N, dtype=torch.uint8, device=A.device)
     scales = torch.empty(M // rows_per_problem, N // head_dim, dtype=torch.float32, device=A.device)
     with _Span("gemm_nt_bf16" + (f" M={M} N={N} K={K} S=1 a={int(a_rows is not None)} c=0 fl=fp8out" if _SHAPE_NAMES else ""), 2.0 * M * N * K):
-        rc = load().stswin_gemm_nt_qkv_fp8(_p(A), _c_long(_ld(A)), _p(a_rows), _p(Bw), _c_long(_ld(Bw)), _p(out8), _c_long(N), _p(scales),
-                                           _c_long(N // head_dim), _p(bias), M, N, K, _c_float(scale), scale_cols, rows_per_problem, head_dim,
+        rc = load().stswin_gemm_nt_qkv_fp8(_p(A), _ld(A), _p(a_rows), _p(Bw), _ld(Bw), _p(out8), N, _p(scales),
+                                           N // head_dim, _p(bias), M, N, K, scale, scale_cols, rows_per_problem, head_dim,
                                            _stream())
     _check(rc, "gemm_nt_qkv_fp8")
     return out8, scales
@@ -633,6 +664,10 @@ def _log_variant(family: str, shape, fam_id: int) -> None:
 
 
 _WARNED = {}
+# Diagnosis bits of the timeline tools (tools/gemm_timeline.py, tools/attn_qkv_timeline.py), on purpose not in the header: the kernel
+# then writes timestamps through one of its output pointers (colsum, qkv_out, dqkv_q_colsum) instead of results
+_GF_DEBUG_STAMPS = 1 << 19            # in stswin_gemm_nt's flags
+_ATTN_DEBUG_STAMPS = 1 << 30          # in the attention kernels' bias_windows
 _NT_SPLITK = os.environ.get("STSWIN_NO_NT_SPLITK") != "1"                 # (A/B switch)
 _PLAN_ROWS = [1]             # splitk_as_rows: plan the split-K choice for this many times the launch's rows
 
@@ -653,20 +688,9 @@ class splitk_as_rows:
 
     def __exit__(self, *exc):
         _PLAN_ROWS[0] = self.prev
+
+
 _CS_PARTIAL_MIN_M = int(os.environ.get("STSWIN_CS_PARTIAL_MIN_M", "1"))   # (the table + fold path is the deterministic one: always)
-_CS_TABLES = {}
-
-
-def _cs_table(device, floats):
-    """Caller-owned scratch of the STSWIN_GF_CS_PARTIAL column-sum table (one per device, grown on demand; every use is
-    write-then-read on the launch stream)."""
-    t = _CS_TABLES.get(device)
-    if t is None or t.numel() < floats:
-        t = torch.empty(max(floats, 1 << 20), dtype=torch.float32, device=device)
-        _CS_TABLES[device] = t
-    return t
-
-
 _TN_WS = {}
 
 
@@ -679,7 +703,6 @@ def _tn_workspace(device, floats=48 * 1024 * 1024):
     return ws
 
 
-TN_NO_COMBINE = 1 << 26
 _TN_SIDE = {}            # device -> side stream of the deferred combines
 _TN_DEFER = 0            # nesting depth of tn_deferred()
 _TN_PENDING = None       # event of the last combine launched on the side stream (one at a time: the partials share one workspace)
@@ -726,9 +749,6 @@ def tn_join():
         _TN_PENDING = None
 
 
-TN_OUT_TAPMINOR, VAR_TN_TAPMINOR = 1 << 25, 0x4000
-
-
 def gemm_tn(At: torch.Tensor, Bt: torch.Tensor, out_f32: torch.Tensor, *, Mk: int, at_rows=None, bt_rows=None,
             splits: int = 0, bseg: int = 0, atomics: bool = False, overwrite: bool = False, debug_ts: bool = False, tapminor: bool = False):
     """out_f32[i][j] += sum_m At[at_rows[m]][i] * Bt[bt_rows[m]][j]  (fp32); overwrite=True stores instead of adding, so
@@ -746,10 +766,10 @@ def gemm_tn(At: torch.Tensor, Bt: torch.Tensor, out_f32: torch.Tensor, *, Mk: in
     defer = _TN_DEFER > 0 and _TN_DEFER_ON and ws is not None and not debug_ts
     tn_join()                                            # the previous combine still reads the workspace this launch overwrites
     with _Span(name, 2.0 * Mk * Ni * Nj):
-        rc = load().stswin_gemm_tn(_dt(At), _p(At), _c_long(_ld(At)), _p(at_rows), _p(Bt), _c_long(_ld(Bt)),
-                                   _p(bt_rows), _p(out_f32), _c_long((-1 if debug_ts is True else -int(debug_ts)) if debug_ts else _ld(out_f32)), Mk, Ni, Nj,
+        rc = load().stswin_gemm_tn(_dt(At), _p(At), _ld(At), _p(at_rows), _p(Bt), _ld(Bt),
+                                   _p(bt_rows), _p(out_f32), (-1 if debug_ts is True else -int(debug_ts)) if debug_ts else _ld(out_f32), Mk, Ni, Nj,
                                    (splits | TN_NO_COMBINE) if defer else splits, bseg, _p(ws),
-                                   _c_long(ws.numel() if ws is not None else 0), _stream())
+                                   ws.numel() if ws is not None else 0, _stream())
     _check(rc, "gemm_tn")
     _log_variant("tn", (Mk, Ni, Nj, bseg), 1)
     if defer:
@@ -763,8 +783,8 @@ def gemm_tn(At: torch.Tensor, Bt: torch.Tensor, out_f32: torch.Tensor, *, Mk: in
             ev = torch.cuda.Event()
             ev.record(cur)
             side.wait_event(ev)
-            _check(load().stswin_tn_combine(_p(ws), _p(out_f32), _c_long(_ld(out_f32)), Ni, Nj, v >> 16, 1 if (splits & TN_OVERWRITE) else 0,
-                                            1 if v & VAR_TN_SLABS_BF16 else 0, ctypes.c_void_p(side.cuda_stream)), "tn_combine")
+            _check(load().stswin_tn_combine(_p(ws), _p(out_f32), _ld(out_f32), Ni, Nj, v >> 16, 1 if (splits & TN_OVERWRITE) else 0,
+                                            1 if v & VAR_TN_SLABS_BF16 else 0, side.cuda_stream), "tn_combine")
             _TN_PENDING = torch.cuda.Event()
             _TN_PENDING.record(side)
     return out_f32
@@ -779,7 +799,6 @@ class _TnProblem(ctypes.Structure):
                 ("overwrite", ctypes.c_int), ("tapminor", ctypes.c_int)]
 
 
-TN_GROUP_DECLINED = -1050
 LAST_TN_GROUP_SPLITS: list = []      # split counts of the last grouped launch (tests, tools)
 
 
@@ -810,7 +829,7 @@ def gemm_tn_group(problems) -> bool:
     if _SHAPE_NAMES:
         name += " group " + " + ".join(f"{q['out'].shape[0]}x{q['out'].shape[1]}" for q in problems) + f" Mk={problems[0]['Mk']}"
     with _Span(name, flops) as span:
-        rc = load().stswin_gemm_tn_group(0, n, arr, _p(ws), _c_long(ws.numel()), sp, _stream())
+        rc = load().stswin_gemm_tn_group(0, n, arr, _p(ws), ws.numel(), sp, _stream())
         if rc == TN_GROUP_DECLINED:
             span.cancel()
     if rc == TN_GROUP_DECLINED:
@@ -819,16 +838,6 @@ def gemm_tn_group(problems) -> bool:
     LAST_TN_GROUP_SPLITS[:] = list(sp)
     _log_variant("tn_group", (n, problems[0]["Mk"]) + tuple(sp), 1)
     return True
-
-
-# kernel-variant codes of stswin_last_variant (include/stswin_hip.h)
-VAR_F32 = 100
-(VAR_NT_RING256_REGEPI, VAR_NT_RING256_LDSEPI, VAR_NT_RING256_NOPIPE, VAR_NT_STREAM, VAR_NT_DUO, VAR_NT_RING256x128_PP,
- VAR_NT_MID, VAR_NT_256x64, VAR_NT_128x64, VAR_NT_128x128, VAR_NT_128x128_W4, VAR_NT_ROWS, VAR_NT_SPLITK) = range(1, 14)
-VAR_TN_RING_PLAIN, VAR_TN_RING_ATROWS, VAR_TN_RING_BTROWS, VAR_TN_RING_BSEG = 20, 21, 22, 23
-VAR_TN_128x128, VAR_TN_128x128_W4, VAR_TN_ROWS = 30, 31, 32
-VAR_TN_SLABS_F32, VAR_TN_SLABS_BF16 = 0x1000, 0x2000
-VAR_TN_FUSED = 0x8000        # the split-K partials were combined inside the GEMM launch
 
 
 def last_tn_tapminor() -> bool:
@@ -848,7 +857,7 @@ def last_variant(family: int) -> dict:
 def vec_gather(v: torch.Tensor, imap: torch.Tensor, fill: float = 0.0) -> torch.Tensor:
     """out[i] = v[imap[i]] (fill where imap[i] < 0); v fp32 contiguous, imap int32."""
     out = torch.empty(imap.numel(), dtype=torch.float32, device=v.device)
-    _check(load().stswin_vec_gather(_p(v), _p(imap), _p(out), imap.numel(), _c_float(fill), _stream()), "vec_gather")
+    _check(load().stswin_vec_gather(_p(v), _p(imap), _p(out), imap.numel(), fill, _stream()), "vec_gather")
     return out
 
 
@@ -872,7 +881,7 @@ def colsum(y: torch.Tensor, out_f32: torch.Tensor, M: Optional[int] = None):
     M = y.shape[0] if M is None else M
     lib = load()
     ws = scratch(y.device, lib.stswin_colsum_scratch(M, y.shape[1]))
-    _check(lib.stswin_colsum(_dt(y), _p(y), _c_long(_ld(y)), _p(out_f32), M, y.shape[1], _p(ws), _stream()), "colsum")
+    _check(lib.stswin_colsum(_dt(y), _p(y), _ld(y), _p(out_f32), M, y.shape[1], _p(ws), _stream()), "colsum")
     return out_f32
 
 
@@ -886,8 +895,8 @@ def layernorm_fwd(x, gamma, beta, *, M, rows=None, S=1, Cseg=None, eps=1e-5, sav
         y = torch.empty(M, S * Cseg, dtype=x.dtype, device=x.device)
     mean = torch.empty(M, dtype=torch.float32, device=x.device) if save_stats else None
     rstd = torch.empty(M, dtype=torch.float32, device=x.device) if save_stats else None
-    rc = load().stswin_layernorm_fwd(_dt(x), _p(x), _c_long(_ld(x)), _p(rows), S, Cseg, _p(y), _c_long(_ld(y)),
-                                     _p(gamma), _p(beta), _p(mean), _p(rstd), M, _c_float(eps), _stream())
+    rc = load().stswin_layernorm_fwd(_dt(x), _p(x), _ld(x), _p(rows), S, Cseg, _p(y), _ld(y),
+                                     _p(gamma), _p(beta), _p(mean), _p(rstd), M, eps, _stream())
     _check(rc, "layernorm_fwd")
     return y, mean, rstd
 
@@ -902,13 +911,13 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, dgamma, dbeta, *, M, rows=None, S=1,
     ws = scratch(x.device, load().stswin_layernorm_bwd_scratch(M, S * Cseg))
     if add is not None:
         assert not accumulate and add.dtype == x.dtype
-        rc = load().stswin_layernorm_bwd_add(_dt(x), _p(dy), _c_long(_ld(dy)), _p(x), _c_long(_ld(x)), _p(rows), S, Cseg,
-                                             _p(gamma), _p(mean), _p(rstd), _p(add), _c_long(_ld(add)), _p(dx), _c_long(_ld(dx)),
+        rc = load().stswin_layernorm_bwd_add(_dt(x), _p(dy), _ld(dy), _p(x), _ld(x), _p(rows), S, Cseg,
+                                             _p(gamma), _p(mean), _p(rstd), _p(add), _ld(add), _p(dx), _ld(dx),
                                              _p(dgamma), _p(dbeta), M, _p(dxsum), _p(ws), _stream())
         _check(rc, "layernorm_bwd_add")
         return dx
-    rc = load().stswin_layernorm_bwd(_dt(x), _p(dy), _c_long(_ld(dy)), _p(x), _c_long(_ld(x)), _p(rows), S, Cseg,
-                                     _p(gamma), _p(mean), _p(rstd), _p(dx), _c_long(_ld(dx)), _p(dgamma), _p(dbeta), M,
+    rc = load().stswin_layernorm_bwd(_dt(x), _p(dy), _ld(dy), _p(x), _ld(x), _p(rows), S, Cseg,
+                                     _p(gamma), _p(mean), _p(rstd), _p(dx), _ld(dx), _p(dgamma), _p(dbeta), M,
                                      1 if accumulate else 0, _p(dxsum), _p(ws), _stream())
     _check(rc, "layernorm_bwd")
     return dx
@@ -969,11 +978,11 @@ def win_attn_fwd(qkv, biasT, maskT, *, nB_, nW, T, ws, heads, C, bias_index=None
     if fp8:
         if qkv.dtype != torch.bfloat16:
             raise StswinHipError("fp8 attention quantises bf16 q / k / v")
-        rc = load().stswin_win_attn_fwd_fp8(_p(qkv), _c_long(_ld(qkv)), _p(out), _c_long(_ld(out)), _p(biasT), _p(maskT), nB_, nW, T, ws,
+        rc = load().stswin_win_attn_fwd_fp8(_p(qkv), _ld(qkv), _p(out), _ld(out), _p(biasT), _p(maskT), nB_, nW, T, ws,
                                             heads, C, _bias_windows(biasT, maskT, nW, bias_index), _p(bias_index), _stream())
         _check(rc, "win_attn_fwd_fp8")
         return out
-    rc = load().stswin_win_attn_fwd(_dt(qkv), _p(qkv), _c_long(_ld(qkv)), _p(out), _c_long(_ld(out)), _p(biasT),
+    rc = load().stswin_win_attn_fwd(_dt(qkv), _p(qkv), _ld(qkv), _p(out), _ld(out), _p(biasT),
                                     _p(maskT), nB_, nW, T, ws, heads, C, _bias_windows(biasT, maskT, nW, bias_index), _p(bias_index),
                                     _stream())
     _check(rc, "win_attn_fwd")
@@ -985,7 +994,7 @@ def win_attn_fwd_f8(qkv8, scales, biasT, maskT, *, nB_, nW, T, ws, heads, C, bia
     assert qkv8.dtype == torch.uint8 and qkv8.is_contiguous() and scales.dtype == torch.float32 and scales.is_contiguous()
     out = torch.empty(qkv8.shape[0], C, dtype=torch.bfloat16, device=qkv8.device)
     with _Span("attn_fwd_f8", 4.0 * nB_ * heads * (T * ws * ws) ** 2 * (C // heads)):
-        rc = load().stswin_win_attn_fwd_f8(_p(qkv8), _c_long(qkv8.shape[1]), _p(scales), _c_long(scales.shape[1]), _p(out), _c_long(_ld(out)),
+        rc = load().stswin_win_attn_fwd_f8(_p(qkv8), qkv8.shape[1], _p(scales), scales.shape[1], _p(out), _ld(out),
                                            _p(biasT), _p(maskT), nB_, nW, T, ws, heads, C, _bias_windows(biasT, maskT, nW, bias_index),
                                            _p(bias_index), _stream())
     _check(rc, "win_attn_fwd_f8")
@@ -1001,10 +1010,10 @@ def win_attn_bwd_f8(qkv8, scales, dout, biasT, maskT, dbiasT, *, nB_, nW, T, ws,
         raise StswinHipError(f"win_attn_bwd_f8: bad geometry ({need})")
     sc = scratch(qkv8.device, need)
     with _Span("attn_bwd_f8", 10.0 * nB_ * heads * (T * ws * ws) ** 2 * (C // heads)):
-        rc = lib.stswin_win_attn_bwd_f8(_p(qkv8), _c_long(qkv8.shape[1]), _p(scales), _c_long(scales.shape[1]), _p(dout), _c_long(_ld(dout)),
-                                        _p(dqkv), _c_long(_ld(dqkv)), _p(biasT), _p(maskT), _p(dbiasT), _p(colsum_out), nB_, nW, T, ws, heads, C,
-                                        _c_float(scale), _bias_windows(biasT, maskT, nW, bias_index), _p(bias_index), _p(sc),
-                                        _c_long(sc.numel()), _stream())
+        rc = lib.stswin_win_attn_bwd_f8(_p(qkv8), qkv8.shape[1], _p(scales), scales.shape[1], _p(dout), _ld(dout),
+                                        _p(dqkv), _ld(dqkv), _p(biasT), _p(maskT), _p(dbiasT), _p(colsum_out), nB_, nW, T, ws, heads, C,
+                                        scale, _bias_windows(biasT, maskT, nW, bias_index), _p(bias_index), _p(sc),
+                                        sc.numel(), _stream())
     _check(rc, "win_attn_bwd_f8")
     return dqkv
 
@@ -1017,16 +1026,16 @@ def win_attn_qkv_fwd(x, rmap, w, bqkv, biasT, *, nB_, nW, T, ws, heads, C, scale
     out = torch.empty(rows, C, dtype=x.dtype, device=x.device)
     qkv = torch.empty(rows, 3 * C, dtype=x.dtype, device=x.device) if want_qkv else None
     if debug_ts is not None:                     # tools/attn_qkv_timeline.py: int64 [256][8][8] stamp buffer in place of qkv_out
-        rc = load().stswin_win_attn_qkv_fwd(_p(x), _c_long(_ld(x)), _c_long(x.shape[0]), _p(rmap), _p(w), _c_long(_ld(w)), _p(bqkv), _p(debug_ts), _c_long(0),
-                                            _p(out), _c_long(_ld(out)), _p(biasT), nB_, nW, T, ws, heads, C, _c_float(scale),
-                                            _bias_windows(biasT, None, nW, bias_index) | (1 << 30), _p(bias_index), _stream())
+        rc = load().stswin_win_attn_qkv_fwd(_p(x), _ld(x), x.shape[0], _p(rmap), _p(w), _ld(w), _p(bqkv), _p(debug_ts), 0,
+                                            _p(out), _ld(out), _p(biasT), nB_, nW, T, ws, heads, C, scale,
+                                            _bias_windows(biasT, None, nW, bias_index) | _ATTN_DEBUG_STAMPS, _p(bias_index), _stream())
         _check(rc, "win_attn_qkv_fwd")
         return out, None
     name = "attn_qkv_fwd_bf16"
     with _Span(name, 2.0 * rows * 3 * C * C + 4.0 * nB_ * heads * (T * ws * ws) ** 2 * (C // heads)):
-        rc = load().stswin_win_attn_qkv_fwd(_p(x), _c_long(_ld(x)), _c_long(x.shape[0]), _p(rmap), _p(w), _c_long(_ld(w)), _p(bqkv), _p(qkv),
-                                            _c_long(_ld(qkv) if qkv is not None else 0), _p(out), _c_long(_ld(out)), _p(biasT), nB_, nW, T,
-                                            ws, heads, C, _c_float(scale), _bias_windows(biasT, None, nW, bias_index), _p(bias_index),
+        rc = load().stswin_win_attn_qkv_fwd(_p(x), _ld(x), x.shape[0], _p(rmap), _p(w), _ld(w), _p(bqkv), _p(qkv),
+                                            _ld(qkv) if qkv is not None else 0, _p(out), _ld(out), _p(biasT), nB_, nW, T,
+                                            ws, heads, C, scale, _bias_windows(biasT, None, nW, bias_index), _p(bias_index),
                                             _stream())
     _check(rc, "win_attn_qkv_fwd")
     return out, qkv
@@ -1045,10 +1054,10 @@ def win_attn_bwd(qkv, dout, biasT, maskT, dbiasT, *, nB_, nW, T, ws, heads, C, s
     if need < 0:
         raise StswinHipError(f"win_attn_bwd: bad geometry ({need})")
     sc = scratch(qkv.device, need)
-    rc = load().stswin_win_attn_bwd(_dt(qkv), _p(qkv), _c_long(_ld(qkv)), _p(dout), _c_long(_ld(dout)), _p(dqkv),
-                                    _c_long(_ld(dqkv)), _p(biasT), _p(maskT), _p(dbiasT), _p(colsum_out), nB_, nW, T, ws, heads, C,
-                                    _c_float(scale), _bias_windows(biasT, maskT, nW, bias_index) | ((1 << 30) if debug_ts else 0),
-                                    _p(bias_index), _p(sc), _c_long(sc.numel()), _stream())
+    rc = load().stswin_win_attn_bwd(_dt(qkv), _p(qkv), _ld(qkv), _p(dout), _ld(dout), _p(dqkv),
+                                    _ld(dqkv), _p(biasT), _p(maskT), _p(dbiasT), _p(colsum_out), nB_, nW, T, ws, heads, C,
+                                    scale, _bias_windows(biasT, maskT, nW, bias_index) | (_ATTN_DEBUG_STAMPS if debug_ts else 0),
+                                    _p(bias_index), _p(sc), sc.numel(), _stream())
     _check(rc, "win_attn_bwd")
     return dqkv
 
@@ -1064,7 +1073,7 @@ def colstats(x, groups=1, squares=True, M=None, unit=0):
     need = lib.stswin_colstats_scratch(_dt(x), M, C, groups, unit)
     if need < 0:
         raise StswinHipError(f"colstats: bad geometry ({need})")
-    _check(lib.stswin_colstats(_dt(x), _p(x), _c_long(_ld(x)), _p(s), _p(ss), M, C, groups, unit, _p(scratch(x.device, need)), _stream()),
+    _check(lib.stswin_colstats(_dt(x), _p(x), _ld(x), _p(s), _p(ss), M, C, groups, unit, _p(scratch(x.device, need)), _stream()),
            "colstats")
     return s, ss
 
@@ -1075,16 +1084,16 @@ def bn_finalize(x, s, ss, running_mean, running_var, groups=1, eps=1e-5, momentu
     C = x.shape[1]
     mean = torch.empty(groups, C, dtype=torch.float32, device=x.device)
     rstd = torch.empty(groups, C, dtype=torch.float32, device=x.device)
-    _check(load().stswin_bn_finalize(_dt(x), _p(None if raw else x), _c_long(_ld(x)), _p(s), _p(ss), _p(mean), _p(rstd), _p(running_mean),
-                                     _p(running_var), M, C, groups, _c_float(eps), _c_float(momentum), unit, _stream()),
+    _check(load().stswin_bn_finalize(_dt(x), _p(None if raw else x), _ld(x), _p(s), _p(ss), _p(mean), _p(rstd), _p(running_mean),
+                                     _p(running_var), M, C, groups, eps, momentum, unit, _stream()),
            "bn_finalize")
     return mean, rstd
 
 
 def bn_apply(x, mean, rstd, gamma, beta, out, resid=None, groups=1, relu=True, M=None, unit=0):
     M = x.shape[0] if M is None else M
-    _check(load().stswin_bn_apply(_dt(x), _p(x), _c_long(_ld(x)), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(resid),
-                                  _c_long(_ld(resid) if resid is not None else 0), _p(out), _c_long(_ld(out)), M,
+    _check(load().stswin_bn_apply(_dt(x), _p(x), _ld(x), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(resid),
+                                  _ld(resid) if resid is not None else 0, _p(out), _ld(out), M,
                                   x.shape[1], groups, 1 if relu else 0, unit, _stream()), "bn_apply")
     return out
 
@@ -1102,10 +1111,10 @@ def bn_bwd(dy, x, y, mean, rstd, gamma, dx, dresid=None, groups=1, relu=True, tr
     need = lib.stswin_bn_bwd_scratch(_dt(x), M, C, groups, unit) if phase != 2 else 0
     if need < 0:
         raise StswinHipError(f"bn_bwd: bad geometry ({need})")
-    _check(lib.stswin_bn_bwd(_dt(x), _p(dy), _c_long(_ld(dy)), _p(x), _c_long(_ld(x)), _p(y),
-                                _c_long(_ld(y) if y is not None else 0), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(s1), _p(s2),
-                                _p(dx), _c_long(_ld(dx)), _p(dresid), _c_long(_ld(dresid) if dresid is not None else 0), M, C,
-                                groups, 1 if relu else 0, 1 if training else 0, phase, _c_long(rows_total), unit, _p(group_sums),
+    _check(lib.stswin_bn_bwd(_dt(x), _p(dy), _ld(dy), _p(x), _ld(x), _p(y),
+                                _ld(y) if y is not None else 0, _p(mean), _p(rstd), _p(gamma), _p(beta), _p(s1), _p(s2),
+                                _p(dx), _ld(dx), _p(dresid), _ld(dresid) if dresid is not None else 0, M, C,
+                                groups, 1 if relu else 0, 1 if training else 0, phase, rows_total, unit, _p(group_sums),
                                 _p(scratch(x.device, need) if phase != 2 else None), _stream()), "bn_bwd")
     return s1, s2
 
@@ -1116,28 +1125,28 @@ def bn_relu_pool(x, mean, rstd, gamma, beta, frames, H, W, groups=1, unit=0):
     Hp, Wp = (H - 1) // 2 + 1, (W - 1) // 2 + 1
     out = torch.empty(frames * Hp * Wp, C, dtype=x.dtype, device=x.device)
     arg = torch.empty(frames * Hp * Wp, C, dtype=torch.uint8, device=x.device)
-    _check(load().stswin_bn_relu_pool(_dt(x), _p(x), _c_long(_ld(x)), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(out), _c_long(_ld(out)),
+    _check(load().stswin_bn_relu_pool(_dt(x), _p(x), _ld(x), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(out), _ld(out),
                                       _p(arg), frames, H, W, C, groups, unit, _stream()), "bn_relu_pool")
     return out, arg
 
 
 def rows_broadcast(v, out, groups, scale=1.0, accumulate=False, M=None):
     M = out.shape[0] if M is None else M
-    _check(load().stswin_rows_broadcast(_dt(out), _p(v), _p(out), _c_long(_ld(out)), M, v.shape[1], groups,
-                                        _c_float(scale), 1 if accumulate else 0, _stream()), "rows_broadcast")
+    _check(load().stswin_rows_broadcast(_dt(out), _p(v), _p(out), _ld(out), M, v.shape[1], groups,
+                                        scale, 1 if accumulate else 0, _stream()), "rows_broadcast")
     return out
 
 
 def bilinear(src, dst, frames, h, w, H, W, backward=False):
     """forward: src [F*h*w][C] -> dst [F*H*W][C]; backward: src = d(out) [F*H*W][C] -> dst = d(in) [F*h*w][C]."""
     C = dst.shape[1]
-    _check(load().stswin_bilinear(_dt(src), _p(src), _c_long(_ld(src)), _p(dst), _c_long(_ld(dst)), frames, h, w, H, W, C,
+    _check(load().stswin_bilinear(_dt(src), _p(src), _ld(src), _p(dst), _ld(dst), frames, h, w, H, W, C,
                                   1 if backward else 0, _stream()), "bilinear")
     return dst
 
 
 def logits_upsample(tokens, nchw, frames, h, w, H, W, nc, backward=False):
-    _check(load().stswin_logits_upsample(_dt(tokens), _p(tokens), _c_long(_ld(tokens)), _p(nchw), frames, h, w, H, W, nc,
+    _check(load().stswin_logits_upsample(_dt(tokens), _p(tokens), _ld(tokens), _p(nchw), frames, h, w, H, W, nc,
                                          1 if backward else 0, _stream()), "logits_upsample")
 
 
@@ -1146,22 +1155,19 @@ def ce_fwd(logits, labels, ignore_index, thresh):
     HW = logits[0, 0].numel()
     loss = torch.empty(F_ * HW, dtype=torch.float32, device=logits.device)
     stats = zeros(4, device=logits.device)          # [count, #labels outside [0, nc), 64-bit fixed-point sum]: include/stswin_hip.h
-    _check(load().stswin_ce_fwd(_dt(logits), _p(logits), _p(labels), _p(loss), _p(stats), F_, _c_long(HW), nc, ignore_index,
-                                _c_float(thresh), _stream()), "ce_fwd")
+    _check(load().stswin_ce_fwd(_dt(logits), _p(logits), _p(labels), _p(loss), _p(stats), F_, HW, nc, ignore_index,
+                                thresh, _stream()), "ce_fwd")
     return loss, stats
-
-
-_OHEM_WORK_BYTES = 3 * 2048 * 12 + 48
 
 
 def ohem_select(loss, stats, n_min: int, thresh: float):
     """(value [1], sel [4]) of OhemCELoss2D's selection (losses.py:35-39) on the device: no sort, no host sync.
     sel = (cut, weight above the cut, top-n_min branch taken, weight at the cut): include/stswin_hip.h."""
-    work = torch.empty(_OHEM_WORK_BYTES // 4, dtype=torch.int32, device=loss.device)
+    work = torch.empty(OHEM_WORK_BYTES // 4, dtype=torch.int32, device=loss.device)
     value = torch.empty((), dtype=torch.float32, device=loss.device)
     sel = torch.empty(4, dtype=torch.float32, device=loss.device)
-    _check(load().stswin_ohem_select(_p(loss), _c_long(loss.numel()), _c_long(n_min), _c_float(thresh), _p(stats), _p(work),
-                                     _c_long(_OHEM_WORK_BYTES), _p(value), _p(sel), _stream()), "ohem_select")
+    _check(load().stswin_ohem_select(_p(loss), loss.numel(), n_min, thresh, _p(stats), _p(work),
+                                     OHEM_WORK_BYTES, _p(value), _p(sel), _stream()), "ohem_select")
     return value, sel
 
 
@@ -1169,7 +1175,7 @@ def ce_bwd(logits, labels, loss, sel, gscale, ignore_index):
     F_, nc = logits.shape[:2]
     HW = logits[0, 0].numel()
     d = torch.empty_like(logits)
-    _check(load().stswin_ce_bwd(_dt(logits), _p(logits), _p(labels), _p(loss), _p(sel), _p(gscale), _p(d), F_, _c_long(HW),
+    _check(load().stswin_ce_bwd(_dt(logits), _p(logits), _p(labels), _p(loss), _p(sel), _p(gscale), _p(d), F_, HW,
                                 nc, ignore_index, _stream()), "ce_bwd")
     return d
 
@@ -1183,7 +1189,7 @@ def contrast_fwd(q, keys, lq, lks, N, HW):
     K5 = (_c_void_p * 5)(*[k.data_ptr() for k in keys])
     L5 = (_c_void_p * 5)(*[l.data_ptr() for l in lks])
     with _Span("contrast_fwd_bf16" if q.dtype == torch.bfloat16 else "contrast_fwd_f32", 2.0 * N * HW * 5 * HW * C):
-        rc = load().stswin_contrast_fwd(_dt(q), _p(q), _c_long(_ld(q)), K5, _c_long(_ld(keys[0])), _p(lq), L5, _p(pos),
+        rc = load().stswin_contrast_fwd(_dt(q), _p(q), _ld(q), K5, _ld(keys[0]), _p(lq), L5, _p(pos),
                                         _p(tot), N, HW, C, _stream())
     _check(rc, "contrast_fwd")
     return pos, tot
@@ -1220,9 +1226,9 @@ def contrast_bank_fwd(Q, lq, bank, lb, *, q_sets, q_block, bank_block, gmap, inv
     name = "contrast_bank_fwd_bf16" if Q.dtype == torch.bfloat16 else "contrast_bank_fwd_f32"
     fn = load().stswin_contrast_bank_fwd_unit if unit_rows else load().stswin_contrast_bank_fwd     # unit_rows: L2-normalised Q / bank rows
     with _Span(name, 2.0 * M * groups * bank_block * C):
-        rc = fn(_dt(Q), _p(Q), _c_long(_ld(Q)), _p(lq), M, C, q_sets, q_block, _p(bank),
-                                             _c_long(bank.stride(1)), _p(lb), maps, seg, bank_block, groups, gm, _c_float(inv_tau),
-                                             _p(pos), _p(tot), _p(rowmax), _p(lse), _p(ws), _c_long(ws.numel()), _stream())
+        rc = fn(_dt(Q), _p(Q), _ld(Q), _p(lq), M, C, q_sets, q_block, _p(bank),
+                                             bank.stride(1), _p(lb), maps, seg, bank_block, groups, gm, inv_tau,
+                                             _p(pos), _p(tot), _p(rowmax), _p(lse), _p(ws), ws.numel(), _stream())
     _check(rc, "contrast_bank_fwd")
     return pos, tot, rowmax, lse
 
@@ -1235,7 +1241,7 @@ def contrast_class_sums(bank, lb, bank_block, ncls):
     need = lib.stswin_contrast_class_sums_scratch(maps, seg, bank_block, C, ncls)
     if need < 0:
         raise StswinHipError(f"contrast_class_sums: bad geometry ({need})")
-    _check(lib.stswin_contrast_class_sums(_dt(bank), _p(bank), _c_long(bank.stride(1)), _p(lb), maps, seg, bank_block, C, ncls,
+    _check(lib.stswin_contrast_class_sums(_dt(bank), _p(bank), bank.stride(1), _p(lb), maps, seg, bank_block, C, ncls,
                                           _p(ksum), _p(scratch(bank.device, need)), _stream()), "contrast_class_sums")
     return ksum
 
@@ -1245,7 +1251,7 @@ def contrast_bank_dq(dpos, dneg, cnt, lq, ksum, *, q_sets, q_block, seg, bank_bl
     C, ncls = ksum.shape[3], ksum.shape[2] - 1
     dq = torch.empty(M, C, dtype=torch.float32, device=dpos.device)
     gm = (_c_int * (q_sets * groups))(*[int(v) for row in gmap for v in row])
-    _check(load().stswin_contrast_bank_dq(_p(dpos.contiguous()), _p(dneg.contiguous()), _p(cnt.contiguous()), _p(lq), _p(ksum), _p(dq), _c_long(C), M, C,
+    _check(load().stswin_contrast_bank_dq(_p(dpos.contiguous()), _p(dneg.contiguous()), _p(cnt.contiguous()), _p(lq), _p(ksum), _p(dq), C, M, C,
                                           q_sets, q_block, seg, bank_block, ncls, groups, gm, _stream()), "contrast_bank_dq")
     return dq
 
@@ -1255,7 +1261,7 @@ def rownorm_scatter(X: torch.Tensor, Y: torch.Tensor, views: int, HW: int, sampl
     R, C = X.shape
     assert Y.dtype == X.dtype and Y.shape == (R, C) and X.stride(1) == 1 and Y.stride(1) == 1
     inv = torch.empty(R, dtype=torch.float32, device=X.device) if want_inv else None
-    _check(load().stswin_rownorm_scatter(_dt(X), _p(X), _c_long(X.stride(0)), _p(Y), _c_long(Y.stride(0)), _p(inv), R, C, views, HW, samples,
+    _check(load().stswin_rownorm_scatter(_dt(X), _p(X), X.stride(0), _p(Y), Y.stride(0), _p(inv), R, C, views, HW, samples,
                                          _stream()), "rownorm_scatter")
     return inv
 
@@ -1264,7 +1270,7 @@ def rownorm_scatter_bwd(X: torch.Tensor, inv: torch.Tensor, dY: torch.Tensor, vi
     R, C = X.shape
     assert dY.dtype == torch.float32 and dY.shape == (R, C) and dY.stride(1) == 1
     dX = torch.empty(R, C, dtype=X.dtype, device=X.device)
-    _check(load().stswin_rownorm_scatter_bwd(_dt(X), _p(X), _c_long(X.stride(0)), _p(inv), _p(dY), _c_long(dY.stride(0)), _p(dX), _c_long(C), R, C,
+    _check(load().stswin_rownorm_scatter_bwd(_dt(X), _p(X), X.stride(0), _p(inv), _p(dY), dY.stride(0), _p(dX), C, R, C,
                                              views, HW, samples, _stream()), "rownorm_scatter_bwd")
     return dX
 
@@ -1410,13 +1416,13 @@ def clip_assemble(ring: torch.Tensor, fresh: Optional[torch.Tensor], clips: Opti
     if n_store > n_fresh:
         raise StswinHipError(f"clip_assemble: {n_store} stores but {n_fresh} fresh frames")
     _check(load().stswin_clip_assemble(_dt(ring), _p(ring), _p(fresh), _p(clips), _p(table), B, n_store, ring.shape[0], n_fresh,
-                                       _c_long(frame), _stream()), "clip_assemble")
+                                       frame, _stream()), "clip_assemble")
 
 
 def optim_tick(kind: int, counter: torch.Tensor, hyper: torch.Tensor, a: float, b: float) -> None:
     """Advance a device-resident step counter (int32 [1]) and derive the step's scalars into hyper (fp32 [4]); include/stswin_hip.h."""
     assert counter.dtype == torch.int32 and hyper.dtype == torch.float32 and hyper.numel() >= 4 and counter.is_cuda and hyper.is_cuda
-    _check(load().stswin_optim_tick(int(kind), _p(counter), _p(hyper), ctypes.c_double(a), ctypes.c_double(b), _stream()), "optim_tick")
+    _check(load().stswin_optim_tick(int(kind), _p(counter), _p(hyper), a, b, _stream()), "optim_tick")
 
 
 def multi_tensor(mode, ps, gs, ms=None, vs=None, lr=0.0, b1=0.0, b2=0.0, eps=0.0, wd=0.0, c1=1.0, c2=1.0, hyper=None):
@@ -1434,11 +1440,11 @@ def multi_tensor(mode, ps, gs, ms=None, vs=None, lr=0.0, b1=0.0, b2=0.0, eps=0.0
         arr = lambda ts: (_c_void_p * k)(*[t.data_ptr() for t in ts[lo:hi]]) if ts is not None else None  # noqa: E731
         ns = (_c_int * k)(*[t.numel() for t in ps[lo:hi]])
         if hyper is not None:
-            _check(lib.stswin_multi_tensor_dev(mode, k, arr(ps), arr(gs), arr(ms), arr(vs), ns, _p(hyper), _c_float(b1), _c_float(b2),
-                                               _c_float(eps), _c_float(wd), 1 if (mode == 1 and c1 != 0.0) else 0, st), "multi_tensor_dev")
+            _check(lib.stswin_multi_tensor_dev(mode, k, arr(ps), arr(gs), arr(ms), arr(vs), ns, _p(hyper), b1, b2,
+                                               eps, wd, 1 if (mode == 1 and c1 != 0.0) else 0, st), "multi_tensor_dev")
         else:
-            _check(lib.stswin_multi_tensor(mode, k, arr(ps), arr(gs), arr(ms), arr(vs), ns, _c_float(lr), _c_float(b1),
-                                           _c_float(b2), _c_float(eps), _c_float(wd), _c_float(c1), _c_float(c2), st),
+            _check(lib.stswin_multi_tensor(mode, k, arr(ps), arr(gs), arr(ms), arr(vs), ns, lr, b1,
+                                           b2, eps, wd, c1, c2, st),
                    "multi_tensor")
 
 
@@ -1459,12 +1465,12 @@ def multi_tensor_lars(ps, gs, ms, norms, *, lr, momentum, wd, trust_coef, eps, f
         if norms is None or norms.numel() < need:
             norms = scratch(ps[lo].device, need)
         if hyper is not None:          # the learning rate from device memory (hyper[0])
-            _check(lib.stswin_multi_tensor_lars_dev(k, arr(ps), arr(gs), arr(ms), ns, _p(norms), _c_long(norms.numel()), _p(hyper),
-                                                    _c_float(momentum), _c_float(wd), _c_float(trust_coef), _c_float(eps), 1 if first else 0,
+            _check(lib.stswin_multi_tensor_lars_dev(k, arr(ps), arr(gs), arr(ms), ns, _p(norms), norms.numel(), _p(hyper),
+                                                    momentum, wd, trust_coef, eps, 1 if first else 0,
                                                     1 if adaptive else 0, st), "multi_tensor_lars_dev")
             continue
-        _check(lib.stswin_multi_tensor_lars(k, arr(ps), arr(gs), arr(ms), ns, _p(norms), _c_long(norms.numel()), _c_float(lr), _c_float(momentum),
-                                            _c_float(wd), _c_float(trust_coef), _c_float(eps), 1 if first else 0,
+        _check(lib.stswin_multi_tensor_lars(k, arr(ps), arr(gs), arr(ms), ns, _p(norms), norms.numel(), lr, momentum,
+                                            wd, trust_coef, eps, 1 if first else 0,
                                             1 if adaptive else 0, st), "multi_tensor_lars")
 
 
@@ -1472,7 +1478,7 @@ def proxy_collective(src: torch.Tensor, dst: torch.Tensor, workgroups: int, pass
     """Measurement stand-in for an RCCL all-reduce of a bucket (include/stswin_hip.h; tools/overlap_proxy.py): `workgroups` workgroups hold
     their compute units while they copy src -> dst `passes` times, on the current stream."""
     assert src.numel() * src.element_size() == dst.numel() * dst.element_size() and src.is_contiguous() and dst.is_contiguous()
-    _check(load().stswin_proxy_collective(_p(src), _p(dst), _c_long(src.numel() * src.element_size()), workgroups, passes, _stream()),
+    _check(load().stswin_proxy_collective(_p(src), _p(dst), src.numel() * src.element_size(), workgroups, passes, _stream()),
            "proxy_collective")
 
 
@@ -1506,8 +1512,8 @@ def calibrate(device=None, seconds: float = 0.1) -> dict:
     src = torch.empty(n, dtype=torch.uint8, device=dev)
     dst = torch.empty(n, dtype=torch.uint8, device=dev)
     src.zero_()
-    _check(lib.stswin_calib_copy(_p(src), _p(dst), _c_long(n), st), "calib_copy")
-    tc = min(timed(lambda: lib.stswin_calib_copy(_p(src), _p(dst), _c_long(n), st)) for _ in range(3))
+    _check(lib.stswin_calib_copy(_p(src), _p(dst), n, st), "calib_copy")
+    tc = min(timed(lambda: lib.stswin_calib_copy(_p(src), _p(dst), n, st)) for _ in range(3))
     del src, dst
     return {"mfma_bf16_tflops": tflops, "mfma_probe_ms": t * 1e3, "copy_tbps": 2.0 * n / tc / 1e12, "copy_probe_ms": tc * 1e3}
 

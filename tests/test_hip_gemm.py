@@ -100,7 +100,7 @@ def test_gemm_nt_colsum_partial_table(m, n, k, flags, monkeypatch):
     seed = torch.randn(n, device="cuda")
     cs_tab = seed.clone()
     assert m >= hip._CS_PARTIAL_MIN_M
-    hip._cs_table(a.device, 1).fill_(float("nan"))          # stale table contents must not leak into the sums
+    hip.scratch(a.device, 2 * ((m + 255) // 256) * n).fill_(float("nan"))      # the table gemm_nt hands the kernel: stale contents must not leak into the sums
     hip.gemm_nt(a, w, out, M=m, flags=flags, colsum_out=cs_tab)
     # the sums are taken in fp32 before the bf16 rounding of the stored values
     ref = seed + F.linear(a.float(), w.float()).sum(0)

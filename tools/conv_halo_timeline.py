@@ -15,7 +15,7 @@ def wgrad(lib, x, dy, f, h, w):
     need = lib.stswin_conv3x3_c64_wgrad_scratch(f, h, w)
     ws = torch.empty(need, dtype=torch.float32, device="cuda")
     for _ in range(3):
-        rc = lib.stswin_conv3x3_c64_wgrad(hip._p(dy), hip._p(x), hip._p(ts), 1, 2, hip._p(ws), hip._c_long(ws.numel()), f, h, w, hip._stream())
+        rc = lib.stswin_conv3x3_c64_wgrad(hip._p(dy), hip._p(x), hip._p(ts), 1, 2, hip._p(ws), ws.numel(), f, h, w, hip._stream())
         assert rc == 0
     torch.cuda.synchronize()
     t = ts.cpu().double() / 100.0
