@@ -568,6 +568,43 @@ int stswin_frame_ingest_planes(const unsigned char* in, unsigned char* tmp, floa
 int stswin_clip_assemble(int dtype, void* ring, const void* fresh, void* clips, const int* table, int B, int n_store, int slots,
                          int n_fresh, long frame_elems, void* stream);
 
+/* ---- training input (stswincl_amd/augment.py): the transform of seg18/dataset/Endovis2018_new.py:61-107, 145-182 (random scale,
+ * pad, crop, flips, brightness / contrast, rotate, / 255.) on uint8 clips [B][T][Hs][Ws][3] and uint8 labels [B][Hs][Ws], in two
+ * stages.  Integer arithmetic until the last table lookup: every output is defined bit for bit.  What is random is drawn on the
+ * host and arrives as one row per sample of each stage's int32 table (device memory, row stride table_stride words).  No allocation, no
+ * synchronisation, no memset: every output element is written by a kernel on the caller's stream.
+ *
+ * stswin_augment_crop: scale + pad + crop + flip.  Pillow's separable BILINEAR (as stswin_frame_ingest: taps [first, first + n),
+ * int32 weights of 22 fraction bits, uint8 intermediate, out = clip((2^21 + sum u * k) >> 22, 0, 255)) evaluated for the Wc columns
+ * and Hc rows of the crop window only.  tmp is the caller's uint8 intermediate [B][T][Hs][Wc][3]; crop [B][T][Hc][Wc][3] and
+ * label_crop [B][Hc][Wc] are the outputs.  A sample's table row, in words (stswin_augment_crop_table_stride gives the length):
+ *     r0, r1, flags, 0        the horizontal pass covers source rows [r0, r1); flags: 1 = horizontal flip, 2 = vertical flip
+ *     hbounds [Wc][2]         (first tap, taps) per window column; taps = 0: padding (the pixel is 0); an unscaled axis has one
+ *     hcoef   [Wc][ksize]      tap of weight 2^22 per index
+ *     vbounds [Hc][2], vcoef [Hc][ksize]     the same per window row
+ *     lx [Wc], ly [Hc]        the label's source column / row (Pillow NEAREST), < 0: padding (label 0)
+ * The flips are applied at the store: window pixel (y, x) is written to (flags & 2 ? Hc-1-y : y, flags & 1 ? Wc-1-x : x).
+ *
+ * stswin_augment_finish: value table + rotate + convert.  crop / label_crop as above -> images fp32 [B][T][3][Hc][Wc] and labels
+ * int64 [B][Hc][Wc].  A sample's table row (stswin_augment_finish_table_stride words):
+ *     flags, 0, 0, 0          1 = rotate
+ *     colx [Wc], coly [Wc], rowx [Hc], rowy [Hc]     int32 positions with 10 fraction bits
+ *     bc [64]                 the sample's uint8 -> uint8 value table (256 bytes; identity when unused), applied to every source
+ *                             pixel before the interpolation
+ * Rotation: the source position of output (y, x) is X = (rowx[y] + colx[x]) >> 5, Y = (rowy[y] + coly[x]) >> 5 in 1/32 pixel;
+ * with fx = X & 31, fy = Y & 31 the weights are (32-fx | fx) x (32-fy | fy) over the pixels (X >> 5 | +1, Y >> 5 | +1), indices
+ * reflected (reflect-101), out = (sum w v + 512) >> 10; the label reads the pixel ((X + 16) >> 5, (Y + 16) >> 5), reflected.
+ * Without the flag the sample copies through.  Then plane c of the image is lut[c * (lut_planes ? 256 : 0) + v] (fp32 [256] or
+ * [3][256]) and the label is label_lut[l] (int64 [256]). */
+long stswin_augment_crop_table_stride(int Hc, int Wc, int ksize);
+int stswin_augment_crop(const unsigned char* frames, const unsigned char* labels, unsigned char* tmp, unsigned char* crop,
+                        unsigned char* label_crop, const int* table, long table_stride, int ksize, int B, int T, int Hs, int Ws,
+                        int Hc, int Wc, void* stream);
+long stswin_augment_finish_table_stride(int Hc, int Wc);
+int stswin_augment_finish(const unsigned char* crop, const unsigned char* label_crop, float* images, long* labels_out,
+                          const int* table, long table_stride, const float* lut, int lut_planes, const long* label_lut, int B,
+                          int T, int Hc, int Wc, void* stream);
+
 /* ---- f2: multi-tensor optimizer / EMA step, up to 48 fp32 tensors per launch (host arrays of device pointers).
  * mode 0 = torch.optim.Adam (seg18/train_swin.py:122; c1 = 1 - b1^t, c2 = sqrt(1 - b2^t)), 1 = torch.optim.SGD with
  * momentum b1 (train_CL_ft_mswin_sgd_minput.py:147-162; c1 != 0 marks the first step: buf = grad), 2 = EMA

@@ -1280,3 +1280,187 @@ extern "C" int stswin_clip_assemble(int dtype, void* ring, const void* fresh, vo
   STSWIN_CHECK_LAUNCH();
   return 0;
 }
+
+// ---------------------------------------------------------------------------------------------------
+// Training input (stswincl_amd/augment.py): the transform of seg18/dataset/Endovis2018_new.py:61-107, 145-182 on uint8 clips and
+// labels, in two stages.  Integer arithmetic only until the last table lookup; everything a sample needs that is not a pixel comes
+// from its row of a host-made int32 table (layouts in include/stswin_hip.h).  Table values that would leave a source are clamped:
+// a wrong table gives wrong pixels, never a wild read.
+//
+// Stage 1, scale + pad + crop + flip: Pillow's BILINEAR as the ingest kernels above compute it, for the crop window only.  The
+// horizontal pass writes the window's columns of the source rows [r0, r1) that the window's rows read into the uint8 intermediate
+// tmp [B][T][Hs][Wc][3]; the vertical pass writes the crop [B][T][Hc][Wc][3] at the flipped address.  A padded column or row has
+// no taps and comes out as (2^21) >> 22 = 0, ImageOps.expand(fill=0).  The label takes Pillow's NEAREST source index per column /
+// row (< 0: padding, label 0).
+// ---------------------------------------------------------------------------------------------------
+#define AUG1_HEAD 4      // r0, r1, flags (1 = horizontal flip, 2 = vertical flip), 0
+#define AUG2_HEAD 4      // flags (1 = rotate), 0, 0, 0
+
+// grid (Hs * Wc / 256, B * T): one thread per (source row, window column) of a frame
+__global__ __launch_bounds__(256) void augment_hpass_kernel(const unsigned char* __restrict__ in, unsigned char* __restrict__ tmp,
+                                                             const int* __restrict__ table, long tstride, int ksize, int T, int Hs,
+                                                             int Ws, int Wc) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= Hs * Wc) return;
+  const int f = blockIdx.y;
+  const int* tab = table + (long)(f / T) * tstride;
+  const int row = i / Wc, j = i - row * Wc;
+  if (row < tab[0] || row >= tab[1]) return;
+  int xmin = tab[AUG1_HEAD + 2 * j], nk = tab[AUG1_HEAD + 2 * j + 1];
+  xmin = xmin < 0 ? 0 : (xmin > Ws ? Ws : xmin);
+  nk = nk > ksize ? ksize : nk;
+  nk = nk > Ws - xmin ? Ws - xmin : nk;
+  const int* k = tab + AUG1_HEAD + 2 * Wc + (long)j * ksize;
+  const unsigned char* src = in + (((long)f * Hs + row) * Ws + xmin) * 3;
+  int s0 = 1 << 21, s1 = 1 << 21, s2 = 1 << 21;
+  for (int x = 0; x < nk; ++x) {
+    const int w = k[x];
+    s0 += (int)src[3 * x] * w;
+    s1 += (int)src[3 * x + 1] * w;
+    s2 += (int)src[3 * x + 2] * w;
+  }
+  unsigned char* dst = tmp + (((long)f * Hs + row) * Wc + j) * 3;
+  dst[0] = (unsigned char)pil_clip8(s0);
+  dst[1] = (unsigned char)pil_clip8(s1);
+  dst[2] = (unsigned char)pil_clip8(s2);
+}
+
+// grid (Hc * Wc / 256, B * T): one thread per crop pixel of a frame; a sample's first frame also writes its label crop
+__global__ __launch_bounds__(256) void augment_vpass_kernel(const unsigned char* __restrict__ tmp, const unsigned char* __restrict__ labels,
+                                                             unsigned char* __restrict__ crop, unsigned char* __restrict__ label_crop,
+                                                             const int* __restrict__ table, long tstride, int ksize, int T, int Hs,
+                                                             int Ws, int Hc, int Wc) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= Hc * Wc) return;
+  const int f = blockIdx.y, b = f / T;
+  const int* tab = table + (long)b * tstride;
+  const int y = i / Wc, x = i - y * Wc;
+  const int* vb = tab + AUG1_HEAD + (2 + ksize) * Wc;
+  int ymin = vb[2 * y], nk = vb[2 * y + 1];
+  ymin = ymin < 0 ? 0 : (ymin > Hs ? Hs : ymin);
+  nk = nk > ksize ? ksize : nk;
+  nk = nk > Hs - ymin ? Hs - ymin : nk;
+  const int* k = vb + 2 * Hc + (long)y * ksize;
+  const unsigned char* src = tmp + (((long)f * Hs + ymin) * Wc + x) * 3;
+  int s0 = 1 << 21, s1 = 1 << 21, s2 = 1 << 21;
+  for (int r = 0; r < nk; ++r) {
+    const unsigned char* s = src + (long)r * Wc * 3;
+    const int w = k[r];
+    s0 += (int)s[0] * w;
+    s1 += (int)s[1] * w;
+    s2 += (int)s[2] * w;
+  }
+  const int flags = tab[2];
+  const int xo = (flags & 1) ? Wc - 1 - x : x, yo = (flags & 2) ? Hc - 1 - y : y;
+  unsigned char* dst = crop + (((long)f * Hc + yo) * Wc + xo) * 3;
+  dst[0] = (unsigned char)pil_clip8(s0);
+  dst[1] = (unsigned char)pil_clip8(s1);
+  dst[2] = (unsigned char)pil_clip8(s2);
+  if (f - b * T == 0) {
+    const int* lx = vb + (2 + ksize) * Hc;
+    const int sx = lx[x], sy = lx[Wc + y];
+    const bool inside = sx >= 0 && sx < Ws && sy >= 0 && sy < Hs;
+    label_crop[((long)b * Hc + yo) * Wc + xo] = inside ? labels[((long)b * Hs + sy) * Ws + sx] : (unsigned char)0;
+  }
+}
+
+extern "C" long stswin_augment_crop_table_stride(int Hc, int Wc, int ksize) {
+  return AUG1_HEAD + (long)(2 + ksize) * (Hc + Wc) + Hc + Wc;
+}
+
+extern "C" int stswin_augment_crop(const unsigned char* frames, const unsigned char* labels, unsigned char* tmp, unsigned char* crop,
+                                   unsigned char* label_crop, const int* table, long table_stride, int ksize, int B, int T, int Hs,
+                                   int Ws, int Hc, int Wc, void* stream) {
+  if (B <= 0 || T <= 0 || Hs <= 0 || Ws <= 0 || Hc <= 0 || Wc <= 0 || ksize <= 0) return -1811;
+  if (frames == nullptr || labels == nullptr || tmp == nullptr || crop == nullptr || label_crop == nullptr || table == nullptr)
+    return -1812;
+  if (table_stride < stswin_augment_crop_table_stride(Hc, Wc, ksize)) return -1813;
+  if ((long)Hs * Wc > (1L << 30) || (long)Hc * Wc > (1L << 30) || (long)B * T > 65535) return -1814;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(augment_hpass_kernel, dim3((unsigned)((Hs * Wc + 255) / 256), (unsigned)(B * T)), dim3(256), 0, st, frames, tmp,
+                     table, table_stride, ksize, T, Hs, Ws, Wc);
+  STSWIN_CHECK_LAUNCH();
+  hipLaunchKernelGGL(augment_vpass_kernel, dim3((unsigned)((Hc * Wc + 255) / 256), (unsigned)(B * T)), dim3(256), 0, st, tmp, labels,
+                     crop, label_crop, table, table_stride, ksize, T, Hs, Ws, Hc, Wc);
+  STSWIN_CHECK_LAUNCH();
+  return 0;
+}
+
+// Stage 2, value table + rotate + convert.  The sample's uint8 -> uint8 table (brightness / contrast; identity when unused) is
+// applied to every source pixel BEFORE the interpolation, the reference's order.  Rotation: the source position of output (y, x)
+// in 1/32 pixel is ((rowx[y] + colx[x]) >> 5, (rowy[y] + coly[x]) >> 5) from the host's 10-bit tables (the rounding term is in
+// the row tables); weights (32 - fx | fx) x (32 - fy | fy), out = (sum w v + 512) >> 10, reflect-101 border; the label takes the
+// nearest source pixel ((X + 16) >> 5, (Y + 16) >> 5).  A sample without rotation copies through.  Then byte -> fp32 through
+// lut[c * lut_stride + v] into planes, label -> int64 through label_lut[256].
+DEVI int reflect101(int i, int n) {
+  if (n == 1) return 0;
+  const int period = 2 * (n - 1);
+  i %= period;
+  if (i < 0) i += period;
+  return i >= n ? period - i : i;
+}
+
+// grid (Hc * Wc / 256, B): one thread per output pixel of a sample, all T frames and the label
+__global__ __launch_bounds__(256) void augment_finish_kernel(const unsigned char* __restrict__ crop, const unsigned char* __restrict__ label_crop,
+                                                              float* __restrict__ images, long* __restrict__ labels_out,
+                                                              const int* __restrict__ table, long tstride, const float* __restrict__ lut,
+                                                              int lut_stride, const long* __restrict__ label_lut, int T, int Hc, int Wc) {
+  __shared__ int bc_words[64];
+  const int b = blockIdx.y;
+  const int* tab = table + (long)b * tstride;
+  if (threadIdx.x < 64) bc_words[threadIdx.x] = tab[AUG2_HEAD + 2 * (Wc + Hc) + threadIdx.x];
+  __syncthreads();
+  const unsigned char* bc = (const unsigned char*)bc_words;
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  const int plane = Hc * Wc;
+  if (p >= plane) return;
+  const int y = p / Wc, x = p - y * Wc;
+  const unsigned char* lab = label_crop + (long)b * plane;
+  if (!(tab[0] & 1)) {
+    for (int t = 0; t < T; ++t) {
+      const unsigned char* s = crop + (((long)b * T + t) * plane + p) * 3;
+      float* o = images + ((long)b * T + t) * 3 * plane + p;
+      o[0] = lut[bc[s[0]]];
+      o[plane] = lut[lut_stride + bc[s[1]]];
+      o[2 * (long)plane] = lut[2 * lut_stride + bc[s[2]]];
+    }
+    labels_out[(long)b * plane + p] = label_lut[lab[p]];
+    return;
+  }
+  const int* colx = tab + AUG2_HEAD;
+  const int* rowx = colx + 2 * Wc;
+  const int X = (rowx[y] + colx[x]) >> 5, Y = (rowx[Hc + y] + colx[Wc + x]) >> 5;
+  const int fx = X & 31, fy = Y & 31;
+  const int x0 = reflect101(X >> 5, Wc), x1 = reflect101((X >> 5) + 1, Wc);
+  const int y0 = reflect101(Y >> 5, Hc), y1 = reflect101((Y >> 5) + 1, Hc);
+  const int w00 = (32 - fx) * (32 - fy), w01 = fx * (32 - fy), w10 = (32 - fx) * fy, w11 = fx * fy;
+  const int o00 = (y0 * Wc + x0) * 3, o01 = (y0 * Wc + x1) * 3, o10 = (y1 * Wc + x0) * 3, o11 = (y1 * Wc + x1) * 3;
+  for (int t = 0; t < T; ++t) {
+    const unsigned char* s = crop + ((long)b * T + t) * plane * 3;
+    float* o = images + ((long)b * T + t) * 3 * plane + p;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const int v = (w00 * bc[s[o00 + c]] + w01 * bc[s[o01 + c]] + w10 * bc[s[o10 + c]] + w11 * bc[s[o11 + c]] + 512) >> 10;
+      o[(long)c * plane] = lut[c * lut_stride + v];
+    }
+  }
+  const int nx = reflect101((X + 16) >> 5, Wc), ny = reflect101((Y + 16) >> 5, Hc);
+  labels_out[(long)b * plane + p] = label_lut[lab[ny * Wc + nx]];
+}
+
+extern "C" long stswin_augment_finish_table_stride(int Hc, int Wc) { return AUG2_HEAD + 2L * (Hc + Wc) + 64; }
+
+extern "C" int stswin_augment_finish(const unsigned char* crop, const unsigned char* label_crop, float* images, long* labels_out,
+                                     const int* table, long table_stride, const float* lut, int lut_planes, const long* label_lut,
+                                     int B, int T, int Hc, int Wc, void* stream) {
+  if (B <= 0 || T <= 0 || Hc <= 0 || Wc <= 0) return -1815;
+  if (crop == nullptr || label_crop == nullptr || images == nullptr || labels_out == nullptr || table == nullptr || lut == nullptr ||
+      label_lut == nullptr)
+    return -1816;
+  if (table_stride < stswin_augment_finish_table_stride(Hc, Wc)) return -1817;
+  if ((long)Hc * Wc > (1L << 28) || B > 65535) return -1818;
+  hipLaunchKernelGGL(augment_finish_kernel, dim3((unsigned)((Hc * Wc + 255) / 256), (unsigned)B), dim3(256), 0, (hipStream_t)stream,
+                     crop, label_crop, images, labels_out, table, table_stride, lut, lut_planes ? 256 : 0, label_lut, T, Hc, Wc);
+  STSWIN_CHECK_LAUNCH();
+  return 0;
+}

@@ -1419,6 +1419,73 @@ def clip_assemble(ring: torch.Tensor, fresh: Optional[torch.Tensor], clips: Opti
                                        frame, _stream()), "clip_assemble")
 
 
+def tensor_form(t, dtype, shape, what: str, fn: str, device=None) -> torch.Tensor:
+    """t must be a contiguous GPU tensor of this dtype and shape (None in the shape: any extent)."""
+    form = f"contiguous {str(dtype).replace('torch.', '')} [" + "][".join("n" if s is None else str(s) for s in shape) + "] on the GPU"
+    if not isinstance(t, torch.Tensor):
+        raise StswinHipError(f"{fn}: {what} must be a {form}, got {type(t).__name__}")
+    ok = t.is_cuda and t.dtype == dtype and t.dim() == len(shape) and t.is_contiguous() and \
+        all(s is None or s == d for s, d in zip(shape, t.shape)) and (device is None or t.device == device)
+    if not ok:
+        raise StswinHipError(f"{fn}: {what} must be a {form}, got {t.dtype} {tuple(t.shape)} on {t.device}"
+                             + ("" if t.is_contiguous() else " (not contiguous)"))
+    return t
+
+
+def augment_crop_table_stride(Hc: int, Wc: int, ksize: int) -> int:
+    return int(load().stswin_augment_crop_table_stride(Hc, Wc, ksize))
+
+
+def augment_finish_table_stride(Hc: int, Wc: int) -> int:
+    return int(load().stswin_augment_finish_table_stride(Hc, Wc))
+
+
+def augment_crop(frames: torch.Tensor, labels: torch.Tensor, tmp: torch.Tensor, crop: torch.Tensor, label_crop: torch.Tensor,
+                 table: torch.Tensor, ksize: int):
+    """Stage 1 of the training transform: uint8 clips [B][T][Hs][Ws][3] and labels [B][Hs][Ws] -> uint8 crops `crop` [B][T][Hc][Wc][3]
+    and `label_crop` [B][Hc][Wc], scaled (Pillow BILINEAR / NEAREST), padded, cropped and flipped by the per-sample int32 `table`
+    [B][stride] (include/stswin_hip.h, stswin_augment_crop); tmp = uint8 with >= B*T*Hs*Wc*3 bytes."""
+    fn = "augment_crop"
+    tensor_form(frames, torch.uint8, (None, None, None, None, 3), "frames", fn)
+    B, T, Hs, Ws, _ = frames.shape
+    dev = frames.device
+    tensor_form(labels, torch.uint8, (B, Hs, Ws), "labels", fn, dev)
+    tensor_form(crop, torch.uint8, (B, T, None, None, 3), "crop", fn, dev)
+    Hc, Wc = crop.shape[2:4]
+    tensor_form(label_crop, torch.uint8, (B, Hc, Wc), "label_crop", fn, dev)
+    tensor_form(table, torch.int32, (B, None), "table", fn, dev)
+    if table.shape[1] < augment_crop_table_stride(Hc, Wc, ksize):
+        raise StswinHipError(f"{fn}: table rows must hold >= {augment_crop_table_stride(Hc, Wc, ksize)} words, got {table.shape[1]}")
+    if not isinstance(tmp, torch.Tensor) or not tmp.is_cuda or tmp.dtype != torch.uint8 or not tmp.is_contiguous() or \
+            tmp.numel() < B * T * Hs * Wc * 3 or tmp.device != dev:
+        raise StswinHipError(f"{fn}: tmp must be contiguous uint8 on the GPU with >= {B * T * Hs * Wc * 3} bytes")
+    _check(load().stswin_augment_crop(_p(frames), _p(labels), _p(tmp), _p(crop), _p(label_crop), _p(table), table.shape[1], ksize, B, T,
+                                      Hs, Ws, Hc, Wc, _stream()), fn)
+    return crop, label_crop
+
+
+def augment_finish(crop: torch.Tensor, label_crop: torch.Tensor, images: torch.Tensor, labels_out: torch.Tensor, table: torch.Tensor,
+                   lut: torch.Tensor, label_lut: torch.Tensor):
+    """Stage 2: uint8 crops [B][T][Hc][Wc][3] and label crops [B][Hc][Wc] -> fp32 `images` [B][T][3][Hc][Wc] and int64 `labels_out`
+    [B][Hc][Wc]: the sample's value table, the fixed-point rotation, then lut (fp32 [256] or [3][256]) and label_lut (int64 [256]);
+    per-sample int32 `table` [B][stride] (include/stswin_hip.h, stswin_augment_finish)."""
+    fn = "augment_finish"
+    tensor_form(crop, torch.uint8, (None, None, None, None, 3), "crop", fn)
+    B, T, Hc, Wc, _ = crop.shape
+    dev = crop.device
+    tensor_form(label_crop, torch.uint8, (B, Hc, Wc), "label_crop", fn, dev)
+    tensor_form(images, torch.float32, (B, T, 3, Hc, Wc), "images", fn, dev)
+    tensor_form(labels_out, torch.int64, (B, Hc, Wc), "labels_out", fn, dev)
+    tensor_form(table, torch.int32, (B, None), "table", fn, dev)
+    if table.shape[1] < augment_finish_table_stride(Hc, Wc):
+        raise StswinHipError(f"{fn}: table rows must hold >= {augment_finish_table_stride(Hc, Wc)} words, got {table.shape[1]}")
+    tensor_form(lut, torch.float32, (3, 256) if isinstance(lut, torch.Tensor) and lut.dim() == 2 else (256,), "lut ([256] or [3][256])", fn, dev)
+    tensor_form(label_lut, torch.int64, (256,), "label_lut", fn, dev)
+    _check(load().stswin_augment_finish(_p(crop), _p(label_crop), _p(images), _p(labels_out), _p(table), table.shape[1], _p(lut),
+                                        1 if lut.dim() == 2 else 0, _p(label_lut), B, T, Hc, Wc, _stream()), fn)
+    return images, labels_out
+
+
 def optim_tick(kind: int, counter: torch.Tensor, hyper: torch.Tensor, a: float, b: float) -> None:
     """Advance a device-resident step counter (int32 [1]) and derive the step's scalars into hyper (fp32 [4]); include/stswin_hip.h."""
     assert counter.dtype == torch.int32 and hyper.dtype == torch.float32 and hyper.numel() >= 4 and counter.is_cuda and hyper.is_cuda

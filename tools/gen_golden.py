@@ -668,6 +668,74 @@ def gen_cata_metrics():
     save("cata_metrics.npz", **res)
 
 
+def gen_random_scale():
+    """The training geometry: the REFERENCE's endovis2018._random_scale (seg18/dataset/Endovis2018_new.py:145-182: random scale with
+    Pillow BILINEAR / NEAREST, pad, random crop) on the seeded clips of tests/augment_ref.py at a small geometry - crop 64 x 80, base
+    width 84, source 64 x 80, T = 4.  Per seed: `random.seed(seed)`, then the sizes it resized to, the three values it drew, and its
+    crops and mask.  The instance is built without __init__ (which reads the dataset's files); the modules the file imports and
+    this machine lacks are empty stubs - `_random_scale` uses random, numpy and Pillow only."""
+    import random
+    from PIL import Image
+    import augment_ref as ar
+    stubs = ["torchvision", "torchvision.transforms", "torchvision.transforms.functional", "albumentations", "cv2", "tqdm"]
+    saved = {n: sys.modules.get(n) for n in stubs}
+    for n in stubs:
+        m = types.ModuleType(n)
+        m.__path__ = []
+        sys.modules[n] = m
+    sys.modules["torchvision"].transforms = sys.modules["torchvision.transforms"]
+    sys.modules["torchvision.transforms"].functional = sys.modules["torchvision.transforms.functional"]
+    sys.modules["tqdm"].tqdm = lambda it, *a, **k: it
+    _purge(["dataset"])
+    sys.path[:] = [p for p in sys.path if not p.startswith(REF)]
+    sys.path.insert(0, os.path.join(REF, "seg18"))
+    try:
+        mod = importlib.import_module("dataset.Endovis2018_new")
+    finally:
+        for n, m in saved.items():
+            if m is None:
+                sys.modules.pop(n, None)
+            else:
+                sys.modules[n] = m
+    ds = object.__new__(mod.endovis2018)
+    src, crop, base_w, t = (64, 80), (64, 80), 84, 4
+    ds.base_size = {"h": 68, "w": base_w}
+    ds.crop_size = {"h": crop[0], "w": crop[1]}
+    seeds = [1, 2, 3, 5, 8, 13]
+    res = dict(seeds=np.array(seeds), source=np.array(src), crop=np.array(crop), base_w=np.array(base_w), t=np.array(t))
+    kinds = set()
+    real_resize, real_randint = Image.Image.resize, random.randint
+    for seed in seeds:
+        frames, label = ar.seeded_clip(seed, t, *src)
+        sizes, draws = [], []
+
+        def resize(self, size, *a, **k):
+            sizes.append(tuple(size))
+            return real_resize(self, size, *a, **k)
+
+        def randint(lo, hi):
+            draws.append(real_randint(lo, hi))
+            return draws[-1]
+
+        Image.Image.resize, random.randint = resize, randint
+        try:
+            random.seed(seed)
+            imgs, mask = ds._random_scale([Image.fromarray(f) for f in frames], Image.fromarray(label))
+        finally:
+            Image.Image.resize, random.randint = real_resize, real_randint
+        assert len(draws) == 3 and len(set(sizes)) == 1 and len(sizes) == t + 1
+        (ow, oh), (long_size, x1, y1) = sizes[0], draws
+        kinds.add("up" if ow > src[1] else "down" if ow < src[1] else "same")
+        if ow < crop[1] or oh < crop[0]:
+            kinds.add("pad")
+        res[f"{seed}/geometry"] = np.array([long_size, ow, oh, x1, y1])
+        res[f"{seed}/crops"] = np.stack(imgs).astype(np.uint8)
+        res[f"{seed}/mask"] = np.asarray(mask).astype(np.uint8)
+        print(f"  seed {seed}: long {long_size} -> {ow} x {oh}, crop at ({x1}, {y1})")
+    assert {"up", "down", "pad"} <= kinds, kinds
+    save("random_scale.npz", **res)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default=None)
@@ -682,6 +750,10 @@ def main():
     if want("cata_metrics"):
         gen_cata_metrics()
     if a.only == "cata_metrics":
+        return
+    if want("random_scale"):
+        gen_random_scale()
+    if a.only == "random_scale":
         return
     swin, base, aspp_mod, losses = import_seg()
     if want("index_maps"):
