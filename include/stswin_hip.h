@@ -605,6 +605,30 @@ int stswin_augment_finish(const unsigned char* crop, const unsigned char* label_
                           const int* table, long table_stride, const float* lut, int lut_planes, const long* label_lut, int B,
                           int T, int Hc, int Wc, void* stream);
 
+/* ---- contrastive pre-training input (stswincl_amd/contrast/views.py): the six RandomResizedCropCoord + RandomHorizontalFlipCoord +
+ * ToTensor + Normalize pipelines of pixcontrast_18/contrast/data/dataset.py:43-70 (contrast/data/transform.py:20-87,
+ * transform_coord.py:81-224) on the uint8 frames [F][Hs][Ws][3] and uint8 labels [L][Hs][Ws] of a batch as they are stored.
+ * stswin_contrast_views writes V = views x samples output view-samples: images fp32 [V][4][3][H][W] and masks fp32 [V][1][H][W]
+ * (the form stswin_labels_resize reads).  Pillow's crop + separable BILINEAR resize as stswin_augment_crop computes it (taps
+ * [first, first + n), int32 weights of 22 fraction bits, out = clip((2^21 + sum u * k) >> 22, 0, 255), an unscaled axis has one tap of
+ * weight 2^22): the horizontal pass writes rows [r0, r1) of the four frames into the caller's uint8 tmp [V][4][Hs][W][3], the vertical
+ * pass stores plane c as lut[c][v] (lut fp32 [3][256]) at the flipped address, and mask (y, x) = float(label[ly[y]][lx[x]]) (Pillow
+ * NEAREST).  A view-sample's row of the int32 device table (row stride table_stride words, stswin_contrast_views_table_stride gives
+ * the length):
+ *     r0, r1, flags, label    source rows [r0, r1) of the horizontal pass; flags: 1 = horizontal flip, 2 = vertical flip; label: index
+ *                             into labels [L]
+ *     frame [4]               indices into frames [F] of the clip's four frames, in output order (views may share frames)
+ *     hbounds [W][2], hcoef [W][ksize], vbounds [H][2], vcoef [H][ksize]     (first tap, taps) and weights per output column / row,
+ *                             in source coordinates
+ *     lx [W], ly [H]          the label's source column / row
+ * ksize <= 16.  Window pixel (y, x) is written to (flags & 2 ? H-1-y : y, flags & 1 ? W-1-x : x).  Frame, label, tap and label
+ * coordinates outside their source are clamped into it (the host wrapper refuses them).  No allocation, no synchronisation, no
+ * memset: two launches on the caller's stream write every output element. */
+long stswin_contrast_views_table_stride(int H, int W, int ksize);
+int stswin_contrast_views(const unsigned char* frames, const unsigned char* labels, unsigned char* tmp, float* images, float* masks,
+                          const int* table, long table_stride, const float* lut, int ksize, int V, int F, int L, int Hs, int Ws,
+                          int H, int W, void* stream);
+
 /* ---- f2: multi-tensor optimizer / EMA step, up to 48 fp32 tensors per launch (host arrays of device pointers).
  * mode 0 = torch.optim.Adam (seg18/train_swin.py:122; c1 = 1 - b1^t, c2 = sqrt(1 - b2^t)), 1 = torch.optim.SGD with
  * momentum b1 (train_CL_ft_mswin_sgd_minput.py:147-162; c1 != 0 marks the first step: buf = grad), 2 = EMA

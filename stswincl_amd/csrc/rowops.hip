@@ -1145,6 +1145,25 @@ DEVI int pil_clip8(int ss) {
   return ss < 0 ? 0 : (ss > 255 ? 255 : ss);
 }
 
+// the tap loop of one pass for the three channels of a pixel: s_c = 2^21 + sum_x src[x * step + c] * k[x * kstep], x < nk (src: the
+// first tap's pixel, step: bytes between two taps).  Every resampling kernel of this file accumulates through it.
+DEVI void pil_taps3(const unsigned char* src, long step, const int* k, int kstep, int nk, int& s0, int& s1, int& s2) {
+  s0 = s1 = s2 = 1 << 21;
+  for (int x = 0; x < nk; ++x) {
+    const unsigned char* s = src + x * step;
+    const int w = k[x * kstep];
+    s0 += (int)s[0] * w;
+    s1 += (int)s[1] * w;
+    s2 += (int)s[2] * w;
+  }
+}
+
+DEVI void pil_store3(unsigned char* dst, int s0, int s1, int s2) {
+  dst[0] = (unsigned char)pil_clip8(s0);
+  dst[1] = (unsigned char)pil_clip8(s1);
+  dst[2] = (unsigned char)pil_clip8(s2);
+}
+
 // one thread per output pixel (row, xx) of the horizontal pass, three channels
 __global__ __launch_bounds__(256) void ingest_hpass_kernel(const unsigned char* __restrict__ in, unsigned char* __restrict__ out,
                                                             const int* __restrict__ bounds, const int* __restrict__ coef, int ksize,
@@ -1155,18 +1174,9 @@ __global__ __launch_bounds__(256) void ingest_hpass_kernel(const unsigned char* 
   const int xx = (int)(i - row * W);
   const int xmin = bounds[2 * xx], nk = bounds[2 * xx + 1];
   const int* k = coef + (long)xx * ksize;
-  const unsigned char* src = in + (row * Ws + xmin) * 3;
-  int s0 = 1 << 21, s1 = 1 << 21, s2 = 1 << 21;
-  for (int x = 0; x < nk; ++x) {
-    const int w = k[x];
-    s0 += (int)src[3 * x] * w;
-    s1 += (int)src[3 * x + 1] * w;
-    s2 += (int)src[3 * x + 2] * w;
-  }
-  unsigned char* dst = out + i * 3;
-  dst[0] = (unsigned char)pil_clip8(s0);
-  dst[1] = (unsigned char)pil_clip8(s1);
-  dst[2] = (unsigned char)pil_clip8(s2);
+  int s0, s1, s2;
+  pil_taps3(in + (row * Ws + xmin) * 3, 3, k, 1, nk, s0, s1, s2);
+  pil_store3(out + i * 3, s0, s1, s2);
 }
 
 // one thread per output pixel (frame, yy, x): the vertical pass (bounds == NULL: the height is unchanged, no pass) + the table
@@ -1189,14 +1199,8 @@ __global__ __launch_bounds__(256) void ingest_vpass_kernel(const unsigned char* 
   } else {
     const int ymin = bounds[2 * yy], nk = bounds[2 * yy + 1];
     const int* k = coef + (long)yy * ksize;
-    int s0 = 1 << 21, s1 = 1 << 21, s2 = 1 << 21;
-    for (int y = 0; y < nk; ++y) {
-      const unsigned char* s = src + ((long)(ymin + y) * W + x) * 3;
-      const int w = k[y];
-      s0 += (int)s[0] * w;
-      s1 += (int)s[1] * w;
-      s2 += (int)s[2] * w;
-    }
+    int s0, s1, s2;
+    pil_taps3(src + ((long)ymin * W + x) * 3, (long)W * 3, k, 1, nk, s0, s1, s2);
     v0 = pil_clip8(s0); v1 = pil_clip8(s1); v2 = pil_clip8(s2);
   }
   float* o = out + (long)f * 3 * plane + p;
@@ -1311,18 +1315,9 @@ __global__ __launch_bounds__(256) void augment_hpass_kernel(const unsigned char*
   nk = nk > ksize ? ksize : nk;
   nk = nk > Ws - xmin ? Ws - xmin : nk;
   const int* k = tab + AUG1_HEAD + 2 * Wc + (long)j * ksize;
-  const unsigned char* src = in + (((long)f * Hs + row) * Ws + xmin) * 3;
-  int s0 = 1 << 21, s1 = 1 << 21, s2 = 1 << 21;
-  for (int x = 0; x < nk; ++x) {
-    const int w = k[x];
-    s0 += (int)src[3 * x] * w;
-    s1 += (int)src[3 * x + 1] * w;
-    s2 += (int)src[3 * x + 2] * w;
-  }
-  unsigned char* dst = tmp + (((long)f * Hs + row) * Wc + j) * 3;
-  dst[0] = (unsigned char)pil_clip8(s0);
-  dst[1] = (unsigned char)pil_clip8(s1);
-  dst[2] = (unsigned char)pil_clip8(s2);
+  int s0, s1, s2;
+  pil_taps3(in + (((long)f * Hs + row) * Ws + xmin) * 3, 3, k, 1, nk, s0, s1, s2);
+  pil_store3(tmp + (((long)f * Hs + row) * Wc + j) * 3, s0, s1, s2);
 }
 
 // grid (Hc * Wc / 256, B * T): one thread per crop pixel of a frame; a sample's first frame also writes its label crop
@@ -1341,21 +1336,11 @@ __global__ __launch_bounds__(256) void augment_vpass_kernel(const unsigned char*
   nk = nk > ksize ? ksize : nk;
   nk = nk > Hs - ymin ? Hs - ymin : nk;
   const int* k = vb + 2 * Hc + (long)y * ksize;
-  const unsigned char* src = tmp + (((long)f * Hs + ymin) * Wc + x) * 3;
-  int s0 = 1 << 21, s1 = 1 << 21, s2 = 1 << 21;
-  for (int r = 0; r < nk; ++r) {
-    const unsigned char* s = src + (long)r * Wc * 3;
-    const int w = k[r];
-    s0 += (int)s[0] * w;
-    s1 += (int)s[1] * w;
-    s2 += (int)s[2] * w;
-  }
+  int s0, s1, s2;
+  pil_taps3(tmp + (((long)f * Hs + ymin) * Wc + x) * 3, (long)Wc * 3, k, 1, nk, s0, s1, s2);
   const int flags = tab[2];
   const int xo = (flags & 1) ? Wc - 1 - x : x, yo = (flags & 2) ? Hc - 1 - y : y;
-  unsigned char* dst = crop + (((long)f * Hc + yo) * Wc + xo) * 3;
-  dst[0] = (unsigned char)pil_clip8(s0);
-  dst[1] = (unsigned char)pil_clip8(s1);
-  dst[2] = (unsigned char)pil_clip8(s2);
+  pil_store3(crop + (((long)f * Hc + yo) * Wc + xo) * 3, s0, s1, s2);
   if (f - b * T == 0) {
     const int* lx = vb + (2 + ksize) * Hc;
     const int sx = lx[x], sy = lx[Wc + y];
@@ -1461,6 +1446,110 @@ extern "C" int stswin_augment_finish(const unsigned char* crop, const unsigned c
   if ((long)Hc * Wc > (1L << 28) || B > 65535) return -1818;
   hipLaunchKernelGGL(augment_finish_kernel, dim3((unsigned)((Hc * Wc + 255) / 256), (unsigned)B), dim3(256), 0, (hipStream_t)stream,
                      crop, label_crop, images, labels_out, table, table_stride, lut, lut_planes ? 256 : 0, label_lut, T, Hc, Wc);
+  STSWIN_CHECK_LAUNCH();
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Contrastive pre-training input (stswincl_amd/contrast/views.py): the six RandomResizedCropCoord + RandomHorizontalFlipCoord +
+// ToTensor + Normalize pipelines of pixcontrast_18/contrast/data/dataset.py:43-70 on the uint8 frames and labels as they are
+// stored.  One table row per output view-sample names its four source frames and its label, so views that share frames read them
+// in place; the crop + resize is the resampler above for the crop's taps, and the vertical pass writes the fp32 planes and the
+// fp32 mask itself: no uint8 crop goes through memory.  Every index a table supplies is clamped into its source: a wrong table
+// gives wrong pixels, never a wild read.
+// ---------------------------------------------------------------------------------------------------
+#define CV_HEAD 8        // r0, r1, flags (1 = horizontal flip, 2 = vertical flip), label index, four frame indices
+#define CV_MAX_KSIZE 16
+#define CV_HROWS 8       // source rows per block of the horizontal pass
+
+DEVI int cv_clamp(int v, int n) { return v < 0 ? 0 : (v >= n ? n - 1 : v); }
+
+// grid (W / 256, Hs / CV_HROWS, V * 4): a block takes 256 output columns of CV_HROWS source rows of one frame of a view.  The
+// columns' weights go through LDS once per block ([tap][column]: conflict-free for any ksize); the rows outside [r0, r1) - a
+// block-uniform test - are not computed.
+__global__ __launch_bounds__(256) void contrast_views_hpass_kernel(const unsigned char* __restrict__ frames, unsigned char* __restrict__ tmp,
+                                                                    const int* __restrict__ table, long tstride, int ksize, int F,
+                                                                    int Hs, int Ws, int W) {
+  __shared__ int sk[CV_MAX_KSIZE * 256];
+  const int u = blockIdx.z;
+  const int* tab = table + (long)(u >> 2) * tstride;
+  int ra = blockIdx.y * CV_HROWS, rb = ra + CV_HROWS;
+  const int r0 = tab[0] < 0 ? 0 : tab[0], r1 = tab[1] > Hs ? Hs : tab[1];
+  ra = ra < r0 ? r0 : ra;
+  rb = rb > r1 ? r1 : rb;
+  if (ra >= rb) return;
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= W) return;
+  int xmin = tab[CV_HEAD + 2 * j], nk = tab[CV_HEAD + 2 * j + 1];
+  xmin = xmin < 0 ? 0 : (xmin > Ws ? Ws : xmin);
+  nk = nk > ksize ? ksize : nk;
+  nk = nk > Ws - xmin ? Ws - xmin : nk;
+  const int* k = tab + CV_HEAD + 2 * W + (long)j * ksize;
+  for (int x = 0; x < nk; ++x) sk[x * 256 + threadIdx.x] = k[x];          // (a thread reads only the words it wrote itself: no barrier)
+  const int f = cv_clamp(tab[4 + (u & 3)], F);
+  const unsigned char* src = frames + ((long)f * Hs * Ws + xmin) * 3;
+  unsigned char* dst = tmp + ((long)u * Hs * W + j) * 3;
+  for (int row = ra; row < rb; ++row) {
+    int s0, s1, s2;
+    pil_taps3(src + (long)row * Ws * 3, 3, sk + threadIdx.x, 256, nk, s0, s1, s2);
+    pil_store3(dst + (long)row * W * 3, s0, s1, s2);
+  }
+}
+
+// grid (W / 256, H, V * 4): a block takes 256 columns of one output row of one frame of a view, so the row's taps and weights are
+// block-uniform (scalar loads, no per-thread table reads); it stores the three fp32 planes at the flipped address, and the view's
+// first frame also stores the mask.
+__global__ __launch_bounds__(256) void contrast_views_vpass_kernel(const unsigned char* __restrict__ tmp, const unsigned char* __restrict__ labels,
+                                                                    float* __restrict__ images, float* __restrict__ masks,
+                                                                    const int* __restrict__ table, long tstride, const float* __restrict__ lut,
+                                                                    int ksize, int L, int Hs, int Ws, int H, int W) {
+  const int x = blockIdx.x * 256 + threadIdx.x;
+  if (x >= W) return;
+  const int y = blockIdx.y, u = blockIdx.z, v = u >> 2;
+  const int* tab = table + (long)v * tstride;
+  const int* vb = tab + CV_HEAD + (long)(2 + ksize) * W;
+  int ymin = vb[2 * y], nk = vb[2 * y + 1];
+  ymin = ymin < 0 ? 0 : (ymin > Hs ? Hs : ymin);
+  nk = nk > ksize ? ksize : nk;
+  nk = nk > Hs - ymin ? Hs - ymin : nk;
+  int s0, s1, s2;
+  pil_taps3(tmp + (((long)u * Hs + ymin) * W + x) * 3, (long)W * 3, vb + 2 * H + (long)y * ksize, 1, nk, s0, s1, s2);
+  const int flags = tab[2];
+  const int xo = (flags & 1) ? W - 1 - x : x, yo = (flags & 2) ? H - 1 - y : y;
+  const long plane = (long)H * W, p = (long)yo * W + xo;
+  float* o = images + (long)u * 3 * plane + p;
+  o[0] = lut[pil_clip8(s0)];
+  o[plane] = lut[256 + pil_clip8(s1)];
+  o[2 * plane] = lut[512 + pil_clip8(s2)];
+  if ((u & 3) == 0) {
+    const int* lx = vb + (long)(2 + ksize) * H;
+    const int sx = cv_clamp(lx[x], Ws), sy = cv_clamp(lx[W + y], Hs), l = cv_clamp(tab[3], L);
+    masks[(long)v * plane + p] = (float)labels[((long)l * Hs + sy) * Ws + sx];
+  }
+}
+
+extern "C" long stswin_contrast_views_table_stride(int H, int W, int ksize) {
+  return CV_HEAD + (long)(2 + ksize) * (H + W) + H + W;
+}
+
+extern "C" int stswin_contrast_views(const unsigned char* frames, const unsigned char* labels, unsigned char* tmp, float* images,
+                                     float* masks, const int* table, long table_stride, const float* lut, int ksize, int V, int F,
+                                     int L, int Hs, int Ws, int H, int W, void* stream) {
+  if (V <= 0 || F <= 0 || L <= 0 || Hs <= 0 || Ws <= 0 || H <= 0 || W <= 0 || ksize <= 0) return -1821;
+  if (frames == nullptr || labels == nullptr || tmp == nullptr || images == nullptr || masks == nullptr || table == nullptr ||
+      lut == nullptr)
+    return -1822;
+  if (ksize > CV_MAX_KSIZE) return -1823;
+  if (table_stride < stswin_contrast_views_table_stride(H, W, ksize)) return -1824;
+  if ((long)V * 4 > 65535 || H > 65535 || (long)Hs > 65535L * CV_HROWS || (long)Hs * Ws > (1L << 28) || (long)H * W > (1L << 28))
+    return -1825;
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned gx = (unsigned)((W + 255) / 256);
+  hipLaunchKernelGGL(contrast_views_hpass_kernel, dim3(gx, (unsigned)((Hs + CV_HROWS - 1) / CV_HROWS), (unsigned)(V * 4)), dim3(256), 0,
+                     st, frames, tmp, table, table_stride, ksize, F, Hs, Ws, W);
+  STSWIN_CHECK_LAUNCH();
+  hipLaunchKernelGGL(contrast_views_vpass_kernel, dim3(gx, (unsigned)H, (unsigned)(V * 4)), dim3(256), 0, st, tmp, labels, images, masks,
+                     table, table_stride, lut, ksize, L, Hs, Ws, H, W);
   STSWIN_CHECK_LAUNCH();
   return 0;
 }

@@ -1486,6 +1486,37 @@ def augment_finish(crop: torch.Tensor, label_crop: torch.Tensor, images: torch.T
     return images, labels_out
 
 
+def contrast_views_table_stride(H: int, W: int, ksize: int) -> int:
+    return int(load().stswin_contrast_views_table_stride(H, W, ksize))
+
+
+def contrast_views(frames: torch.Tensor, labels: torch.Tensor, tmp: torch.Tensor, images: torch.Tensor, masks: torch.Tensor,
+                   table: torch.Tensor, lut: torch.Tensor, ksize: int):
+    """The contrastive pre-training views: uint8 frames [F][Hs][Ws][3] and labels [L][Hs][Ws] -> fp32 `images` [V][4][3][H][W] and fp32
+    `masks` [V][1][H][W], each view-sample cropped, resized (Pillow BILINEAR / NEAREST), flipped and converted through lut fp32
+    [3][256] by its row of the int32 `table` [V][stride], which also names its four frames and its label (include/stswin_hip.h,
+    stswin_contrast_views); tmp = uint8 with >= V*4*Hs*W*3 bytes.  The frame and label indices are the caller's to check (they live
+    in device memory; the kernel clamps them)."""
+    fn = "contrast_views"
+    tensor_form(frames, torch.uint8, (None, None, None, 3), "frames", fn)
+    F_, Hs, Ws, _ = frames.shape
+    dev = frames.device
+    tensor_form(labels, torch.uint8, (None, Hs, Ws), "labels", fn, dev)
+    tensor_form(images, torch.float32, (None, 4, 3, None, None), "images", fn, dev)
+    V, _, _, H, W = images.shape
+    tensor_form(masks, torch.float32, (V, 1, H, W), "masks", fn, dev)
+    tensor_form(table, torch.int32, (V, None), "table", fn, dev)
+    if table.shape[1] < contrast_views_table_stride(H, W, ksize):
+        raise StswinHipError(f"{fn}: table rows must hold >= {contrast_views_table_stride(H, W, ksize)} words, got {table.shape[1]}")
+    tensor_form(lut, torch.float32, (3, 256), "lut", fn, dev)
+    if not isinstance(tmp, torch.Tensor) or not tmp.is_cuda or tmp.dtype != torch.uint8 or not tmp.is_contiguous() or \
+            tmp.numel() < V * 4 * Hs * W * 3 or tmp.device != dev:
+        raise StswinHipError(f"{fn}: tmp must be contiguous uint8 on the GPU with >= {V * 4 * Hs * W * 3} bytes")
+    _check(load().stswin_contrast_views(_p(frames), _p(labels), _p(tmp), _p(images), _p(masks), _p(table), table.shape[1], _p(lut), ksize,
+                                        V, F_, labels.shape[0], Hs, Ws, H, W, _stream()), fn)
+    return images, masks
+
+
 def optim_tick(kind: int, counter: torch.Tensor, hyper: torch.Tensor, a: float, b: float) -> None:
     """Advance a device-resident step counter (int32 [1]) and derive the step's scalars into hyper (fp32 [4]); include/stswin_hip.h."""
     assert counter.dtype == torch.int32 and hyper.dtype == torch.float32 and hyper.numel() >= 4 and counter.is_cuda and hyper.is_cuda
