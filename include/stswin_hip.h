@@ -475,9 +475,20 @@ int stswin_contrast_fwd(int dtype, const void* Q, long ldq, const void* const* K
  *     [b bank_block, (b+1) bank_block) of that map (bank_block = seg / nblk, or = seg when nblk = 1).
  * Writes pos[m][g] = sum_p S[m][p] [lq[m] == lb[p]], all[m][g] = sum_p S[m][p] over the visible rows of group g (fp32 [M][groups]) and,
  * if not NULL, rowmax[m] / lse[m] = max / log-sum-exp of inv_tau * S[m][p] over the visible rows of ALL groups (the InfoNCE
- * denominator; monitoring and hard-negative statistics - the reference loss itself is linear in S).  C <= 256, a multiple of 64
- * (bf16) / 32 (fp32).  workspace: caller-owned fp32 scratch, >= 4 M groups floats (more lets the launcher split long bank segments
- * over workgroups; the partials are combined in a fixed order, so results are deterministic). */
+ * denominator; monitoring and hard-negative statistics - the reference loss itself is linear in S).  C: bf16 64, 128, 192 or 256;
+ * fp32 32, 64, 128 or 256 (the kernel is instantiated per C / 32 in {1, 2, 4, 8}: fp32 96, 160, 192 and 224 are refused with -1516,
+ * like every refusal before anything is launched).  Q rows need 16-byte alignment (ldq a multiple of 8 (bf16) / 4 (fp32) elements),
+ * bank rows likewise.  workspace: caller-owned fp32 scratch, >= 4 M groups floats (more lets the launcher split long bank segments
+ * over workgroups; the partials are combined in a fixed order, so results are deterministic).
+ *
+ * LABELS must lie in [0, ncls) (ncls <= 63 for stswin_contrast_class_sums, <= 64 for stswin_label_counts).  The reference's F.one_hot
+ * raises outside that range (PixPro_swin_v5.py:54), so it defines nothing there, and the kernels of this section DIFFER there:
+ *   - the forward (stswin_contrast_fwd, stswin_contrast_bank_fwd / _unit) compares the raw int32 labels: -3 matches -3 and nothing else;
+ *   - stswin_label_counts clamps query and bank labels to [0, ncls - 1] before counting: -3 counts as class 0, ncls + 5 as ncls - 1;
+ *   - stswin_contrast_class_sums adds a bank row with such a label to the total (slot ncls) only, and stswin_contrast_bank_dq gives a
+ *     query with such a label an all-zero class row.
+ * For such labels the gradient of class_sums + bank_dq is therefore NOT the derivative of the forward's sums, and cnt is not the
+ * size of the forward's positive set.  Callers keep labels in range. */
 int stswin_contrast_bank_fwd(int dtype, const void* Q, long ldq, const int* lq, int M, int C, int q_sets, int q_block,
                              const void* bank, long ldb, const int* lb, int maps, int seg, int bank_block, int groups,
                              const int* gmap /* host memory, [q_sets][groups] */, float inv_tau, float* pos, float* all,
@@ -492,8 +503,8 @@ int stswin_contrast_bank_fwd_unit(int dtype, const void* Q, long ldq, const int*
 /* Backward to the queries (keys are no-grad, PixPro_swin_v5.py:366): the masked sums are linear in the scores, so
  * dq[m] = sum_g dpos[m][g] Kcls[map(g)][blk][lq[m]] + dneg[m][g] (Ktot[map(g)][blk] - Kcls[..][lq[m]]), where dpos / dneg are the
  * gradients of pos and of neg = all - pos.  class_sums writes ksum [maps][seg / bank_block][ncls + 1][C] fp32 (slot ncls = all
- * rows; zeroed by the call; labels outside [0, ncls) only count in the total); bank_dq combines them per query row into dq
- * fp32 [M][C].  cnt[m][g] (fp32) = number of visible rows of group g with label lq[m]: where it equals bank_block the negative
+ * rows; zeroed by the call; 1 <= ncls <= 63, C % 4 == 0, C <= 512; labels outside [0, ncls) only count in the total); bank_dq
+ * combines them per query row into dq fp32 [M][C] (seg / bank_block = the number of query blocks or 1, else -1532).  cnt[m][g] (fp32) = number of visible rows of group g with label lq[m]: where it equals bank_block the negative
  * set is empty and its term is skipped, so the gradient is exactly zero like the reference's masked products (:103-113). */
 int stswin_contrast_class_sums(int dtype, const void* bank, long ldb, const int* lb, int maps, int seg, int bank_block, int C,
                                int ncls, float* ksum, float* scratch /* >= stswin_contrast_class_sums_scratch(...) floats */, void* stream);
@@ -512,8 +523,9 @@ int stswin_contrast_bank_dq(const float* dpos, const float* dneg, const float* c
  * stswin_labels_resize: `maps` (<= 8) float label maps [N][1][Hs][Ws] -> int32 lb[maps][N * h * w], nearest neighbour with ATen's index
  *   rule (F.interpolate(mode='nearest') + .to(int32), ConsistencyLoss.forward :590-593).
  * stswin_label_counts: cnt[m][g] = number of rows of bank block blk(m) of map gmap[set(m)][g] whose label equals lq[m] (labels clamped
- *   to [0, ncls - 1]): the row sums of posMask (:48-57, :116-118) from per-block class histograms (hist: int scratch
- *   [maps][seg / bank_block][ncls]).
+ *   to [0, ncls - 1]; 1 <= ncls <= 64): the row sums of posMask (:48-57, :116-118) from per-block class histograms (hist: int scratch
+ *   [maps][seg / bank_block][ncls]).  Block geometry as stswin_contrast_bank_fwd: M % (q_sets q_block) == 0 and seg / bank_block equal
+ *   to the number of query blocks M / (q_sets q_block) or to 1, else -1543 before anything is launched.
  * stswin_pair_loss / _bwd: loss = sum over the query sets of mean(-log(e^P / (e^P + e^N) + 1e-6)), P = sum_g pos_g / (sum_g cnt_g + 1e-6),
  *   N = sum_g (all_g - pos_g) / (visible - cnt_g + 1e-6) (:119-129); one workgroup, fixed-order sums (deterministic); the backward gives
  *   d loss / d pos and d loss / d (all - pos). */

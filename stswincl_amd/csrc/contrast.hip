@@ -824,17 +824,19 @@ extern "C" int stswin_label_counts(const int* lq, const int* lb, int M, int maps
                                    float* cnt /* [M][groups] */, void* stream) {
   if (M <= 0) return 0;
   if (ncls < 1 || ncls > 64 || groups < 1 || groups > CB_MAX_GROUPS || q_sets < 1 || q_sets > 2 || bank_block < 1 || seg % bank_block ||
-      M % q_sets)
+      q_block < 1 || M % (q_sets * q_block))
     return -1543;
   const int nb = seg / bank_block;
+  // count_gather indexes hist[map][block of the query row]: the bank must have one block per query block, or a single one for all
+  // (the geometry stswin_contrast_bank_dq refuses with -1532) - checked, like gmap, before anything is launched
+  if (nb != 1 && nb != M / (q_sets * q_block)) return -1543;
+  for (int i = 0; i < q_sets * groups; ++i)
+    if (gmap[i] < 0 || gmap[i] >= maps) return -1543;
   hipLaunchKernelGGL(label_hist_kernel, dim3((unsigned)nb, (unsigned)maps), dim3(256), 0, (hipStream_t)stream, lb, seg, bank_block, ncls, hist);
   CountArgs a;
   a.lq = lq; a.hist = hist; a.cnt = cnt; a.M = M; a.q_sets = q_sets; a.q_block = q_block; a.nb = nb; a.ncls = ncls; a.groups = groups;
   for (int s = 0; s < 2; ++s)
-    for (int g = 0; g < CB_MAX_GROUPS; ++g) {
-      a.gmap[s][g] = (s < q_sets && g < groups) ? gmap[s * groups + g] : 0;
-      if (a.gmap[s][g] < 0 || a.gmap[s][g] >= maps) return -1543;
-    }
+    for (int g = 0; g < CB_MAX_GROUPS; ++g) a.gmap[s][g] = (s < q_sets && g < groups) ? gmap[s * groups + g] : 0;
   hipLaunchKernelGGL(count_gather_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
   STSWIN_CHECK_LAUNCH();
   return 0;
