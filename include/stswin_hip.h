@@ -554,6 +554,17 @@ int stswin_upsample_argmax(int dtype, const void* logits, unsigned char* labels,
  * cleared: the caller zeroes it once per evaluation.  Integer atomics only (exact, independent of order). */
 int stswin_upsample_argmax_cm(int dtype, const void* logits, unsigned char* labels, const long* gt, unsigned long long* cm, int ncm,
                               int align_corners, int frames, int nc, int h, int w, int H, int W, void* stream);
+/* ---- colour overlay of a label map (stswincl_amd/utils/visualize.py, VideoSegmenter(out="overlay")): labels uint8 [n][H][W],
+ * frames uint8 [n][H][W][3] (HWC RGB) or NULL (every source byte 0), table uint8 [256][4] = (r, g, b, a) per label value, out uint8
+ * [n][H][W][3].  Per pixel and channel, with s the frame byte and (c, a) the table entry of the pixel's label:
+ *     out = (a c + (255 - a) s + 127) / 255        (integer division: a = 255 gives c, a = 0 gives s, both exactly)
+ * edge_alpha = -1: no outlines; 0 .. 255: a pixel whose label differs from that of its left, right, upper or lower neighbour inside
+ * the same frame (no wrap to the next row, no look into the next frame) uses a = edge_alpha with its own colour.  out may alias
+ * frames (a thread reads only the frame bytes of the pixels it writes), not labels.  Any pointer alignment, any W: pointers that are
+ * all 8-byte aligned take the body with 8 pixels per thread, others the byte body.  Integer arithmetic only.
+ * Errors: -1415 n, H or W <= 0; -1416 labels, table or out NULL; -1417 edge_alpha outside -1 .. 255. */
+int stswin_labels_overlay(const unsigned char* labels, const unsigned char* frames, const unsigned char* table, unsigned char* out,
+                          int n, int H, int W, int edge_alpha, void* stream);
 
 /* ---- video inference (stswincl_amd/video.py), the evaluation loop of seg18/test.py:147-175 over the clips of
  * seg18/dataset/Endovis2018_new.py:109-127.

@@ -1131,6 +1131,153 @@ extern "C" int stswin_upsample_argmax_cm(int dtype, const void* logits, unsigned
   return 0;
 }
 
+// Colour overlay of a label map (the picture seg18/test.py:162-169 and segcata/utils/cadis_visualization.py:86-113 make on the host):
+// out = (a c + (255 - a) s + 127) / 255 per channel, (c, a) = table[label], s = the frame byte (0 without frames); a pixel whose label
+// differs from a left / right / upper / lower neighbour of its own frame takes a = edge_alpha (>= 0).  One pass over 7 bytes per pixel.
+// The pixels of all frames are one flat run p = (f H + y) W + x.  The wide body gives a thread OV_PPT = 8 consecutive pixels: one
+// 8-byte label load, three 8-byte frame loads, three 8-byte stores (3 * 8 p is a multiple of 8), so it needs labels, frames and out
+// 8-byte aligned and nothing of W: a group may straddle rows and frames, x and y are carried per pixel.  The rows above and below are
+// read as 8 unaligned bytes each and the two flat neighbours of the group as single bytes, all through the cache (the same lines the
+// neighbouring threads load as their own labels); a neighbour that does not exist is never compared, so what is loaded for it does not
+// matter, but no load leaves [0, N).  The last N % 8 pixels, and every pixel when a pointer is not 8-byte aligned, take the byte body.
+// The table goes to LDS byte by byte (any alignment) as r | g << 8 | b << 16 | a << 24.
+#define OV_PPT 8
+
+template <typename IT>
+__device__ __forceinline__ void overlay_pixel(const unsigned char* labels, const unsigned char* frames, const unsigned* tab,
+                                              unsigned char* out, IT p, int H, int W, int edge_alpha) {
+  const unsigned l = labels[p];
+  const unsigned e = tab[l];
+  unsigned a = e >> 24;
+  if (edge_alpha >= 0) {
+    const IT row = p / (IT)W;
+    const int x = (int)(p - row * (IT)W), y = (int)(row % (IT)H);
+    const bool edge = (x > 0 && labels[p - 1] != l) || (x < W - 1 && labels[p + 1] != l) ||
+                      (y > 0 && labels[p - (IT)W] != l) || (y < H - 1 && labels[p + (IT)W] != l);
+    if (edge) a = (unsigned)edge_alpha;
+  }
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const unsigned s = frames ? frames[3 * p + c] : 0u;
+    out[3 * p + c] = (unsigned char)((a * ((e >> (8 * c)) & 255u) + (255u - a) * s + 127u) / 255u);
+  }
+}
+
+__device__ __forceinline__ void overlay_load_table(const unsigned char* table, unsigned* tab) {
+  const unsigned char* t = table + 4 * threadIdx.x;            // 256 threads, 256 entries
+  tab[threadIdx.x] = (unsigned)t[0] | ((unsigned)t[1] << 8) | ((unsigned)t[2] << 16) | ((unsigned)t[3] << 24);
+  __syncthreads();
+}
+
+template <typename IT>
+__global__ __launch_bounds__(256) void labels_overlay_wide_kernel(const unsigned char* labels, const unsigned char* frames,
+                                                                  const unsigned char* table, unsigned char* out, IT N, int H, int W,
+                                                                  int edge_alpha) {
+  __shared__ unsigned tab[256];
+  overlay_load_table(table, tab);
+  const IT p = ((IT)blockIdx.x * 256 + threadIdx.x) * OV_PPT;
+  if (p >= N) return;
+  if (p + OV_PPT > N) {                                        // the one partial group
+    for (IT q = p; q < N; ++q) overlay_pixel<IT>(labels, frames, tab, out, q, H, W, edge_alpha);
+    return;
+  }
+  const uint2 lw = *reinterpret_cast<const uint2*>(labels + p);
+  unsigned l[OV_PPT], a[OV_PPT], e[OV_PPT];
+#pragma unroll
+  for (int i = 0; i < OV_PPT; ++i) {
+    l[i] = ((i < 4 ? lw.x : lw.y) >> (8 * (i & 3))) & 255u;
+    e[i] = tab[l[i]];
+    a[i] = e[i] >> 24;
+  }
+  if (edge_alpha >= 0) {
+    uint2 uw = make_uint2(0u, 0u), dw = make_uint2(0u, 0u);
+    if (p >= (IT)W) {
+      __builtin_memcpy(&uw, labels + (p - (IT)W), 8);
+    } else {                                                   // frame 0, row 0 (and the start of row 1 when W < 8)
+      unsigned long long v = 0;
+      for (int i = 0; i < OV_PPT; ++i)
+        if (p + i >= (IT)W) v |= (unsigned long long)labels[p + i - (IT)W] << (8 * i);
+      uw = make_uint2((unsigned)v, (unsigned)(v >> 32));
+    }
+    if (p + (IT)W + OV_PPT <= N) {
+      __builtin_memcpy(&dw, labels + (p + (IT)W), 8);
+    } else {                                                   // the last row of the last frame
+      unsigned long long v = 0;
+      for (int i = 0; i < OV_PPT; ++i)
+        if (p + i + (IT)W < N) v |= (unsigned long long)labels[p + i + (IT)W] << (8 * i);
+      dw = make_uint2((unsigned)v, (unsigned)(v >> 32));
+    }
+    const unsigned left = p > 0 ? labels[p - 1] : 0u, right = p + OV_PPT < N ? labels[p + OV_PPT] : 0u;
+    const IT row = p / (IT)W;
+    int x = (int)(p - row * (IT)W), y = (int)(row % (IT)H);
+#pragma unroll
+    for (int i = 0; i < OV_PPT; ++i) {
+      const unsigned up = ((i < 4 ? uw.x : uw.y) >> (8 * (i & 3))) & 255u, dn = ((i < 4 ? dw.x : dw.y) >> (8 * (i & 3))) & 255u;
+      const unsigned lf = i ? l[i ? i - 1 : 0] : left, rt = i < OV_PPT - 1 ? l[i < OV_PPT - 1 ? i + 1 : 0] : right;
+      const bool edge = (x > 0 && lf != l[i]) || (x < W - 1 && rt != l[i]) || (y > 0 && up != l[i]) || (y < H - 1 && dn != l[i]);
+      if (edge) a[i] = (unsigned)edge_alpha;
+      if (++x == W) {
+        x = 0;
+        if (++y == H) y = 0;
+      }
+    }
+  }
+  unsigned s[6] = {0u, 0u, 0u, 0u, 0u, 0u};                    // 24 frame bytes
+  if (frames) {
+    const uint2* fp = reinterpret_cast<const uint2*>(frames + 3 * p);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const uint2 v = fp[k];
+      s[2 * k] = v.x;
+      s[2 * k + 1] = v.y;
+    }
+  }
+  unsigned o[6] = {0u, 0u, 0u, 0u, 0u, 0u};
+#pragma unroll
+  for (int j = 0; j < 3 * OV_PPT; ++j) {
+    const int i = j / 3, c = j % 3;
+    const unsigned sb = (s[j >> 2] >> (8 * (j & 3))) & 255u;
+    o[j >> 2] |= ((a[i] * ((e[i] >> (8 * c)) & 255u) + (255u - a[i]) * sb + 127u) / 255u) << (8 * (j & 3));
+  }
+  uint2* op = reinterpret_cast<uint2*>(out + 3 * p);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) op[k] = make_uint2(o[2 * k], o[2 * k + 1]);
+}
+
+template <typename IT>
+__global__ __launch_bounds__(256) void labels_overlay_byte_kernel(const unsigned char* labels, const unsigned char* frames,
+                                                                  const unsigned char* table, unsigned char* out, IT N, int H, int W,
+                                                                  int edge_alpha) {
+  __shared__ unsigned tab[256];
+  overlay_load_table(table, tab);
+  const IT p = (IT)blockIdx.x * 256 + threadIdx.x;
+  if (p < N) overlay_pixel<IT>(labels, frames, tab, out, p, H, W, edge_alpha);
+}
+
+extern "C" int stswin_labels_overlay(const unsigned char* labels, const unsigned char* frames, const unsigned char* table,
+                                     unsigned char* out, int n, int H, int W, int edge_alpha, void* stream) {
+  if (n <= 0 || H <= 0 || W <= 0) return -1415;
+  if (labels == nullptr || table == nullptr || out == nullptr) return -1416;
+  if (edge_alpha < -1 || edge_alpha > 255) return -1417;
+  const long N = (long)n * H * W;
+  const bool wide = (((uintptr_t)labels | (uintptr_t)frames | (uintptr_t)out) & 7) == 0;
+  const bool small = 3 * N + OV_PPT + W < (1L << 31);        // every index the kernels form fits 32 bits
+  const long threads = wide ? (N + OV_PPT - 1) / OV_PPT : N;
+  const long blocks = (threads + 255) / 256;
+  if (blocks > 0x7fffffffL) return -1415;
+  dim3 grid((unsigned)blocks);
+  hipStream_t st = (hipStream_t)stream;
+  if (wide) {
+    if (small) hipLaunchKernelGGL(labels_overlay_wide_kernel<unsigned>, grid, dim3(256), 0, st, labels, frames, table, out, (unsigned)N, H, W, edge_alpha);
+    else hipLaunchKernelGGL(labels_overlay_wide_kernel<long>, grid, dim3(256), 0, st, labels, frames, table, out, N, H, W, edge_alpha);
+  } else {
+    if (small) hipLaunchKernelGGL(labels_overlay_byte_kernel<unsigned>, grid, dim3(256), 0, st, labels, frames, table, out, (unsigned)N, H, W, edge_alpha);
+    else hipLaunchKernelGGL(labels_overlay_byte_kernel<long>, grid, dim3(256), 0, st, labels, frames, table, out, N, H, W, edge_alpha);
+  }
+  STSWIN_CHECK_LAUNCH();
+  return 0;
+}
+
 
 // ----------------------------------------------------------------------------------------- statistics from a GEMM epilogue
 // A convolution GEMM launched with STSWIN_GF_CS_PARTIAL | STSWIN_GF_CS_SQ leaves per-128-row-block column sums and sums of

@@ -1359,6 +1359,42 @@ def upsample_argmax_cm(logits, H, W, gt=None, cm=None, align_corners=True, label
     return out
 
 
+def _same_memory(a: torch.Tensor, b: torch.Tensor) -> bool:
+    """True when the bytes of two contiguous tensors overlap."""
+    a0, b0 = a.data_ptr(), b.data_ptr()
+    return a0 < b0 + b.numel() * b.element_size() and b0 < a0 + a.numel() * a.element_size()
+
+
+def labels_overlay(labels: torch.Tensor, table: torch.Tensor, frames: Optional[torch.Tensor] = None, edge_alpha: Optional[int] = None,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint8 labels [n][H][W] -> uint8 RGB [n][H][W][3]: the colour table[label] = (r, g, b, a) (uint8 [256][4],
+    utils.visualize.overlay_table) blended onto uint8 HWC `frames` [n][H][W][3] (None: onto black), out = (a c + (255 - a) s + 127) / 255
+    per channel.  edge_alpha 0 .. 255 gives pixels whose label differs from a 4-neighbour's that alpha (outlines), None none.  `out`
+    may be `frames` (in place), never memory of `labels`; returns out (include/stswin_hip.h, stswin_labels_overlay)."""
+    if labels.dtype != torch.uint8 or labels.dim() != 3 or not labels.is_contiguous():
+        raise StswinHipError(f"labels_overlay: labels must be contiguous uint8 [n][H][W], got {labels.dtype} {tuple(labels.shape)}")
+    n, H, W = labels.shape
+    if n <= 0 or H <= 0 or W <= 0:
+        raise StswinHipError(f"labels_overlay: empty labels {tuple(labels.shape)}")
+    if table.dtype != torch.uint8 or tuple(table.shape) != (256, 4) or not table.is_contiguous() or table.device != labels.device:
+        raise StswinHipError(f"labels_overlay: table must be contiguous uint8 [256][4] on {labels.device}, got {table.dtype} "
+                             f"{tuple(table.shape)} on {table.device}")
+    for t, what in ((frames, "frames"), (out, "out")):
+        if t is not None and (t.dtype != torch.uint8 or tuple(t.shape) != (n, H, W, 3) or not t.is_contiguous() or t.device != labels.device):
+            raise StswinHipError(f"labels_overlay: {what} must be contiguous uint8 [{n}][{H}][{W}][3] on {labels.device}, got {t.dtype} "
+                                 f"{tuple(t.shape)} on {t.device}")
+    if edge_alpha is None:
+        edge_alpha = -1
+    elif not isinstance(edge_alpha, int) or not 0 <= edge_alpha <= 255:
+        raise StswinHipError(f"labels_overlay: edge_alpha must be None or an int 0 .. 255, got {edge_alpha!r}")
+    if out is None:
+        out = torch.empty(n, H, W, 3, dtype=torch.uint8, device=labels.device)
+    elif _same_memory(out, labels):
+        raise StswinHipError("labels_overlay: out shares memory with labels (only frames may be overwritten in place)")
+    _check(load().stswin_labels_overlay(_p(labels), _p(frames), _p(table), _p(out), n, H, W, edge_alpha, _stream()), "labels_overlay")
+    return out
+
+
 def _int_table(t: Optional[torch.Tensor], rows: int, what: str):
     if t is None:
         raise StswinHipError(f"frame_ingest: the {what} table is missing")

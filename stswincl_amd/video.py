@@ -284,7 +284,7 @@ class _Pinned:
 class VideoSegmenter:
     """Segment video sequences with an eval-mode TswinPlus, one result per frame, each frame's ResNet features computed once.
 
-    seg = VideoSegmenter(model, batch=1, out="logits" | "labels", out_size=None, graph=False)
+    seg = VideoSegmenter(model, batch=1, out="logits" | "labels" | "overlay", out_size=None, graph=False)
 
     push(frames, gt=None) takes uint8 RGB frames [n][Hs][Ws][3] (or one [Hs][Ws][3]; torch tensor on the model's GPU or the CPU, or
     a numpy array) and returns [(frame_index, result), ...] for the frames whose clip is now complete.  finish() runs what is
@@ -311,13 +311,26 @@ class VideoSegmenter:
     label, CATA_new_512.py:237) that pools all frames of all sequences, as cata_test.py does: reset() keeps it, reset_metrics() clears
     it, confusion_matrix() returns it as float64 numpy (utils.cata_metrics.ConfusionMatrix.get_confusion_matrix()).
 
+    out="overlay" (palette=None, alpha=128, transparent=None, edge_alpha=255): the result is uint8 [Hs][Ws][3], the pushed frame itself
+    with the protocol's labels blended in (hip.labels_overlay: colour table utils.visualize.overlay_table(palette or
+    default_palette(), alpha, transparent), outlines of edge_alpha where the label changes, None for none).  `transparent` labels show
+    the frame unchanged: default (0,), the background, for endovis18 and (classes - 1,), the remapped ignore label, for cadis.  out_size
+    is the frame size (another one raises at the first push).  With gt: (overlay, dice, iou) for endovis18, the overlay alone for cadis,
+    counted as for out="labels".  The segmenter keeps the GPU uint8 copy of a frame from its ResNet pass until its own clip's result
+    (frames f < 4 wait several steps; a frame pushed as a GPU tensor is referenced, not copied, as it is until its ResNet pass for
+    every output form: leave it unchanged until its result has come back); under graph=True the captured step ends with the label
+    and the overlay launch on the static frame buffer, and the result is a view of the graph's output buffer as above.
+
     Runs under torch.no_grad().  Refuses (StswinHipError): a model in train mode, a model or frames not on the GPU, a frame size
     that differs from the earlier frames'."""
 
     def __init__(self, model, batch: int = 1, out: str = "logits", out_size: Optional[Sequence[int]] = None, graph: bool = False,
-                 protocol: str = "endovis18", metric_classes: Optional[int] = None, align_corners: Optional[bool] = None):
-        if out not in ("logits", "labels"):
-            raise StswinHipError(f"out must be 'logits' or 'labels', got {out!r}")
+                 protocol: str = "endovis18", metric_classes: Optional[int] = None, align_corners: Optional[bool] = None,
+                 palette=None, alpha: int = 128, transparent: Optional[Sequence[int]] = None, edge_alpha: Optional[int] = 255):
+        if out not in ("logits", "labels", "overlay"):
+            raise StswinHipError(f"out must be 'logits', 'labels' or 'overlay', got {out!r}")
+        if out != "overlay" and (palette is not None or transparent is not None):
+            raise StswinHipError("palette and transparent belong to out='overlay'")
         if graph and batch != 1:
             raise StswinHipError("graph replay runs the online step: batch must be 1")
         _check_rule(protocol)
@@ -335,6 +348,8 @@ class VideoSegmenter:
         self.protocol = protocol
         self.cadis = protocol == "cadis"
         default_size = CADIS_SIZE if self.cadis else self.size
+        if out == "overlay":
+            default_size = None           # the frame size, known at the first push
         self.out_size = tuple(out_size) if out_size is not None else default_size
         self.align_corners = True if align_corners is None and not self.cadis else bool(align_corners)
         self.metric_classes = None
@@ -343,6 +358,19 @@ class VideoSegmenter:
             if not 1 <= self.metric_classes <= 64:
                 raise StswinHipError(f"metric_classes must be 1 .. 64, got {self.metric_classes}")
         self._cm = None
+        self._table = None
+        if out == "overlay":
+            from .utils.visualize import default_palette, overlay_table
+            if transparent is None:       # the background, or the remapped ignore label
+                transparent = (model.classifier[-1].out_channels - 1,) if self.cadis else (0,)
+            if edge_alpha is not None and (not isinstance(edge_alpha, int) or not 0 <= edge_alpha <= 255):
+                raise StswinHipError(f"edge_alpha must be None or an int 0 .. 255, got {edge_alpha!r}")
+            try:
+                table = overlay_table(default_palette() if palette is None else palette, alpha, transparent)
+            except ValueError as e:
+                raise StswinHipError(f"out='overlay': {e}") from e
+            self._table = torch.from_numpy(table).to(self.device)       # persistent: a captured graph reads it
+        self.edge_alpha = edge_alpha
         self.graph = graph
         self.planner = ClipPlanner(batch, rule=protocol)
         self.frame_shape = None
@@ -359,6 +387,7 @@ class VideoSegmenter:
     def reset(self) -> None:
         self.planner.reset()
         self._frames = {}                 # frame index -> (uint8 tensor [k][Hs][Ws][3], GPU or CPU, row) until its ResNet pass
+        self._kept = {}                   # out="overlay": frame index -> GPU uint8 [1][Hs][Ws][3] from its ResNet pass until its clip's result
         self._gt = {}
 
     def reset_metrics(self) -> None:
@@ -417,6 +446,12 @@ class VideoSegmenter:
             raise StswinHipError(f"frames must be uint8 RGB [n][Hs][Ws][3], got {tuple(frames.shape)}")
         shape = tuple(frames.shape[1:3])
         if self.frame_shape is None:
+            if self.out == "overlay":
+                if self.out_size is None:
+                    self.out_size = shape
+                elif self.out_size != shape:
+                    raise StswinHipError(f"out='overlay' blends onto the pushed frame: out_size {self.out_size} differs from the frame "
+                                         f"size {shape}")
             self.frame_shape = shape
         elif shape != self.frame_shape:
             raise StswinHipError(f"frame size {shape} differs from the earlier frames' {self.frame_shape}")
@@ -441,7 +476,9 @@ class VideoSegmenter:
         return self._pinned.upload(np.asarray(values, dtype=np.int32), dst)
 
     def _ingest_new(self, new: List[int]) -> torch.Tensor:
-        """The new frames' fp32 images [n][3][H][W]: one ingest launch per run of rows of one pushed tensor."""
+        """The new frames' fp32 images [n][3][H][W]: one ingest launch per run of rows of one pushed tensor.  out="overlay" keeps the
+        device tensor that the ingest read, one view per frame, for the frame's own clip: the copy made of CPU frames, the pushed
+        tensor itself for GPU frames."""
         out = torch.empty(len(new), 3, *self.size, dtype=torch.float32, device=self.device)
         j = 0
         while j < len(new):
@@ -450,13 +487,18 @@ class VideoSegmenter:
             while j + k < len(new) and self._frames[new[j + k]][0] is src and self._frames[new[j + k]][1] == r0 + k:
                 self._frames.pop(new[j + k])
                 k += 1
-            ingest(self._put_frames(src, r0, k), self.size, out[j:j + k], self.protocol)
+            dev = self._put_frames(src, r0, k)
+            ingest(dev, self.size, out[j:j + k], self.protocol)
+            if self._table is not None:
+                for i in range(k):
+                    self._kept[new[j + i]] = dev[i:i + 1]
             j += k
         return out
 
-    def _compute(self, img: Optional[torch.Tensor], table: torch.Tensor, B: int, n_new: int, labels: bool = False):
+    def _compute(self, img: Optional[torch.Tensor], table: torch.Tensor, B: int, n_new: int, labels: bool = False, frames=None):
         """ResNet on the new frames' images, clip assembly, Swin / ASPP / head: -> logits (B, nc, H, W) (and with labels = True the
-        labels (B, *out_size)).  Every launch on the current stream, no host synchronisation (graph-capturable)."""
+        labels (B, *out_size), or for out="overlay" the overlay (B, *out_size, 3) on `frames`, one uint8 [1][Hs][Ws][3] per clip).
+        Every launch on the current stream, no host synchronisation (graph-capturable)."""
         m = self.model
         hip.arena_reset(self.device)
         h, w = self.size[0] // 8, self.size[1] // 8
@@ -478,8 +520,16 @@ class VideoSegmenter:
         hip.clip_assemble(self._ring, tok, clips, table, B, n_new)
         logits = m.forward_frame_tokens(clips, h, w, self.size[0], self.size[1])
         if labels:
-            return logits, self._labels(logits)
+            lab = self._labels(logits)
+            return logits, lab if self._table is None else self._overlay(lab, frames)
         return logits, None
+
+    def _overlay(self, labels: torch.Tensor, frames) -> torch.Tensor:
+        """labels (B, *out_size) blended onto the clips' own frames: one launch per clip (the frames live in separate tensors)."""
+        out = torch.empty(*labels.shape, 3, dtype=torch.uint8, device=self.device)
+        for b, fr in enumerate(frames):
+            hip.labels_overlay(labels[b:b + 1], self._table, fr, self.edge_alpha, out[b:b + 1])
+        return out
 
     def _labels(self, logits: torch.Tensor, gt: Optional[torch.Tensor] = None, want: bool = True) -> Optional[torch.Tensor]:
         if not self.cadis:
@@ -506,14 +556,15 @@ class VideoSegmenter:
 
     def _run(self, st: Step):
         B, n_new = len(st.clips), len(st.new)
-        want_labels = self.out == "labels" and not any(g in self._gt for g in st.clips)
+        want_labels = self.out != "logits" and not any(g in self._gt for g in st.clips)
         if self.graph and self._steady(st):
-            logits, labels, replayed = self._run_graph(st, want_labels)
+            logits, labels, replayed, frames = self._run_graph(st, want_labels)
         else:
             img = self._ingest_new(st.new) if n_new else None
-            logits, labels = self._compute(img, self._upload_table(st.table()), B, n_new, want_labels)
+            frames = [self._kept.pop(g) for g in st.clips] if self._table is not None else None
+            logits, labels = self._compute(img, self._upload_table(st.table()), B, n_new, want_labels, frames)
             replayed = False
-        return self._results(st.clips, logits, labels), replayed
+        return self._results(st.clips, logits, labels, frames), replayed
 
     def _run_graph(self, st: Step, want_labels: bool):
         src, r = self._frames.pop(st.new[0])
@@ -522,13 +573,14 @@ class VideoSegmenter:
             # first steady-state step (or first of the other output form): one eager warm-up on the static buffers (on a side stream,
             # as graph.py's GraphedStep does), then the capture; this step's result is the warm-up's
             u8 = torch.empty(1, *self.frame_shape, 3, dtype=torch.uint8, device=self.device)
+            frames = [u8] if self._table is not None else None     # the steady step's clip is the new frame's: blend onto the static buffer
             table = torch.empty(T + 1, dtype=torch.int32, device=self.device)
             self._put_frames(src, r, 1, u8)
             self._upload_table(st.table(), table)
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
-                logits, labels = self._compute(ingest(u8, self.size, protocol=self.protocol), table, 1, 1, want_labels)
+                logits, labels = self._compute(ingest(u8, self.size, protocol=self.protocol), table, 1, 1, want_labels, frames)
                 logits = logits.clone()
             torch.cuda.current_stream().wait_stream(side)
             torch.cuda.synchronize()
@@ -536,34 +588,39 @@ class VideoSegmenter:
             graph = torch.cuda.CUDAGraph()
             autocast = torch.is_autocast_enabled()
             with torch.cuda.graph(graph):
-                out, out_labels = self._compute(ingest(u8, self.size, protocol=self.protocol), table, 1, 1, want_labels)
+                out, out_labels = self._compute(ingest(u8, self.size, protocol=self.protocol), table, 1, 1, want_labels, frames)
             self._g = (graph, u8, table, out, out_labels, want_labels, autocast)
-            return logits, labels, False
+            return logits, labels, False, frames
         graph, u8, table, out, out_labels, _, autocast = g
         if torch.is_autocast_enabled() != autocast:
             raise StswinHipError("autocast differs from the state the step was captured under: make a new VideoSegmenter")
         self._put_frames(src, r, 1, u8)
         self._upload_table(st.table(), table)
         graph.replay()
-        return out, out_labels, True
+        return out, out_labels, True, [u8] if self._table is not None else None
 
-    def _results(self, clips: List[int], logits: torch.Tensor, labels: Optional[torch.Tensor]) -> List[Tuple[int, object]]:
+    def _results(self, clips: List[int], logits: torch.Tensor, labels: Optional[torch.Tensor], frames=None) -> List[Tuple[int, object]]:
+        """`labels`: the step's labels (out="overlay": its overlays), or None when some clip has ground truth or out="logits"."""
         if labels is not None:
             return [(g, labels[b]) for b, g in enumerate(clips)]
         res = []
+
+        def final(b, lab):                    # labels (1, *out_size) -> the result form of out="labels" | "overlay"
+            return lab[0] if self._table is None else self._overlay(lab, frames[b:b + 1])[0]
+
         for b, g in enumerate(clips):
             gt = self._gt.pop(g, None)
             lg = logits[b]
             if gt is None:
-                res.append((g, lg if self.out == "logits" else self._labels(logits[b:b + 1])[0]))
+                res.append((g, lg if self.out == "logits" else final(b, self._labels(logits[b:b + 1]))))
                 continue
             if self.cadis:
-                lab = self._labels(logits[b:b + 1], gt, want=self.out == "labels")
-                res.append((g, lg if self.out == "logits" else lab[0]))
+                lab = self._labels(logits[b:b + 1], gt, want=self.out != "logits")
+                res.append((g, lg if self.out == "logits" else final(b, lab)))
                 continue
             from .utils.EndoMetric import predict_and_score
             lab, dices, ious = predict_and_score(logits[b:b + 1], self.out_size, gt)
-            res.append((g, (lg if self.out == "logits" else lab[0], dices[0], ious[0])))
+            res.append((g, (lg if self.out == "logits" else final(b, lab), dices[0], ious[0])))
         return res
 
 
