@@ -610,7 +610,7 @@ int stswin_clip_assemble(int dtype, void* ring, const void* fresh, void* clips, 
  *
  * stswin_augment_finish: value table + rotate + convert.  crop / label_crop as above -> images fp32 [B][T][3][Hc][Wc] and labels
  * int64 [B][Hc][Wc].  A sample's table row (stswin_augment_finish_table_stride words):
- *     flags, 0, 0, 0          1 = rotate
+ *     flags, key0, key1, noise     flags: 1 = rotate; words 1 .. 3 belong to stswin_augment_noise (this stage never reads them)
  *     colx [Wc], coly [Wc], rowx [Hc], rowy [Hc]     int32 positions with 10 fraction bits
  *     bc [64]                 the sample's uint8 -> uint8 value table (256 bytes; identity when unused), applied to every source
  *                             pixel before the interpolation
@@ -618,7 +618,24 @@ int stswin_clip_assemble(int dtype, void* ring, const void* fresh, void* clips, 
  * with fx = X & 31, fy = Y & 31 the weights are (32-fx | fx) x (32-fy | fy) over the pixels (X >> 5 | +1, Y >> 5 | +1), indices
  * reflected (reflect-101), out = (sum w v + 512) >> 10; the label reads the pixel ((X + 16) >> 5, (Y + 16) >> 5), reflected.
  * Without the flag the sample copies through.  Then plane c of the image is lut[c * (lut_planes ? 256 : 0) + v] (fp32 [256] or
- * [3][256]) and the label is label_lut[l] (int64 [256]). */
+ * [3][256]) and the label is label_lut[l] (int64 [256]).
+ *
+ * stswin_augment_noise: CaDIS's Gaussian noise (segcata/dataset/CATA_new_512.py:178-183: skimage random_noise(mode='gaussian',
+ * var=0.001, clip=True), stored as (255 * clip(u / 255. + n, 0, 1)).astype('uint8')), between the two stages, in place on stage 1's
+ * crop taken as [B][sample_bytes] (sample_bytes = T Hc Wc 3, a multiple of 4).  For a byte u that expression is
+ * clamp(u + floor(255 n), 0, 255): an integer offset K with the law P(K <= k) = Phi((k + 1) / (255 sqrt(var))), which the host
+ * states as n_thr ascending uint32 thresholds thr (device memory) and k_min.  `table` is the stage-2 table above: a sample with
+ * noise != 0 is switched on and (key0, key1) is its 64-bit key, low word first; a sample with noise == 0 is not written at all.
+ * Per byte i of a noisy sample:
+ *     w[0..3] = Philox4x32-10(counter = (i >> 2, 0, 0, 0), key = (key0, key1))        r = w[i & 3]
+ *     K       = k_min + #{ j < n_thr : thr[j] <= r }
+ *     out     = clamp(u + K, 0, 255)
+ * Philox4x32-10 as published (Salmon et al., Random123): multipliers 0xD2511F53 and 0xCD9E8D57, key increments 0x9E3779B9 and
+ * 0xBB67AE85 per round, ten rounds.  The noise of a byte is a function of (key, i) alone - the reference's own stream is unseeded
+ * and cannot be reproduced.  Any pointer alignment: 16-byte accesses where the address allows them, bytes elsewhere.  Integer
+ * arithmetic only; one launch, no allocation, no synchronisation, no memset.
+ * Errors, before anything is launched: -1808 B <= 0, sample_bytes <= 0, not a multiple of 4 or > 2^34; -1809 crop, table or thr
+ * NULL; -1810 n_thr outside 1 .. 1024; -1819 table_stride < stswin_augment_finish_table_stride(1, 1), the shortest stage-2 row. */
 long stswin_augment_crop_table_stride(int Hc, int Wc, int ksize);
 int stswin_augment_crop(const unsigned char* frames, const unsigned char* labels, unsigned char* tmp, unsigned char* crop,
                         unsigned char* label_crop, const int* table, long table_stride, int ksize, int B, int T, int Hs, int Ws,
@@ -627,6 +644,8 @@ long stswin_augment_finish_table_stride(int Hc, int Wc);
 int stswin_augment_finish(const unsigned char* crop, const unsigned char* label_crop, float* images, long* labels_out,
                           const int* table, long table_stride, const float* lut, int lut_planes, const long* label_lut, int B,
                           int T, int Hc, int Wc, void* stream);
+int stswin_augment_noise(unsigned char* crop, const int* table, long table_stride, const unsigned int* thr, int n_thr, int k_min,
+                         int B, long sample_bytes, void* stream);
 
 /* ---- contrastive pre-training input (stswincl_amd/contrast/views.py): the six RandomResizedCropCoord + RandomHorizontalFlipCoord +
  * ToTensor + Normalize pipelines of pixcontrast_18/contrast/data/dataset.py:43-70 (contrast/data/transform.py:20-87,

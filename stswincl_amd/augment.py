@@ -17,6 +17,10 @@ What is exact and what is ours:
   * flips, brightness / contrast, rotation: the reference uses albumentations, whose random stream cannot be reproduced without the
     library; they are drawn from a numpy Generator of ours (sample() documents the order).  Brightness / contrast is the uint8 table
     value_table(); the rotation is fixed-point arithmetic modelled on cv2.warpAffine (rotate_tables()), not pinned to cv2.
+  * Gaussian noise (CaDIS, CATA_new_512.py:178-183: skimage's random_noise(mode='gaussian', var=0.001, clip=True) on half of the
+    clips, stored as (255 * clip(u / 255. + n, 0, 1)).astype('uint8')): for a byte that is clamp(u + floor(255 n), 0, 255), an integer
+    offset with the law of noise_thresholds(), exact.  The stream is ours: Philox4x32-10 keyed by ClipParams.noise and counted by the
+    byte index (the reference's is unseeded and never repeats).  Off unless p_noise is given; the reference's CaDIS value is 0.5.
   * the conversion: float32(u / 255.) (CaDIS: video.cadis_value_table() per plane) and the label table (CaDIS: 255 -> class_num - 1).
 """
 from __future__ import annotations
@@ -40,7 +44,8 @@ _ONE = 1 << video._PRECISION_BITS
 
 @dataclass
 class ClipParams:
-    """One sample's transform.  alpha / beta None: no value table; angle None: no rotation (degrees, positive counter-clockwise)."""
+    """One sample's transform.  alpha / beta None: no value table; angle None: no rotation (degrees, positive counter-clockwise);
+    noise None: no Gaussian noise, else the 64-bit key of the sample's noise stream."""
     long_size: int
     x1: int
     y1: int
@@ -49,6 +54,7 @@ class ClipParams:
     alpha: Optional[float] = None
     beta: Optional[float] = None
     angle: Optional[float] = None
+    noise: Optional[int] = None
 
 
 def geometry(long_size: int, src_hw, crop_hw) -> Tuple[int, int, int, int]:
@@ -134,19 +140,79 @@ def rotate_tables(angle: float, H: int, W: int):
     return tuple(t.astype(np.int32) for t in (colx, coly, rowx, rowy))
 
 
+MAX_THRESHOLDS = 1024   # what stswin_augment_noise keeps in LDS
+
+
+def _phi(z: float) -> float:
+    return 0.5 * (1.0 + math.erf(z / math.sqrt(2.0)))
+
+
+def _law(var: float):
+    """[(k, t_k)] for the k whose threshold lies strictly between 0 and 2^32, strictly ascending: far out in the tails neighbours
+    round to the same value, and there each is moved to one past its outer neighbour's (upwards below 2^31, downwards above), so that
+    every offset in range keeps a probability of at least 2^-32."""
+    s = 255.0 * math.sqrt(var)
+    reach = int(math.ceil(9.0 * s)) + 2                     # Phi(-9) 2^32 < 1e-9: every k further out rounds to 0 or 2^32
+    t = [(k, int(math.floor(_phi((k + 1) / s) * 4294967296.0 + 0.5))) for k in range(-reach, reach + 1)]
+    ks, ts = [k for k, v in t if 0 < v < 1 << 32], [v for _, v in t if 0 < v < 1 << 32]
+    for j in range(1, len(ts)):
+        if ts[j] < 1 << 31:
+            ts[j] = max(ts[j], ts[j - 1] + 1)
+    for j in range(len(ts) - 2, -1, -1):
+        if ts[j] >= 1 << 31:
+            ts[j] = min(ts[j], ts[j + 1] - 1)
+    return list(zip(ks, ts))
+
+
+def noise_thresholds(var: float) -> Tuple[np.ndarray, int]:
+    """The law of the integer offset K = floor(255 n), n ~ N(0, var), at 2^-32 resolution -> (uint32 thr ascending, k_min): with r a
+    uniform 32-bit number K = k_min + #{j : thr[j] <= r}.  P(K <= k) = Phi((k + 1) / s), s = 255 sqrt(var), so the threshold of k is
+    t_k = floor(Phi((k + 1) / s) 2^32 + 0.5) (float64, Phi from math.erf); the k with 0 < t_k < 2^32 are kept and k_min is the first.
+    var = 0.001 (the reference's): 103 thresholds, k_min = -52, mean -0.5, variance s^2 + 1/12.  Strictly ascending: where neighbours
+    far out in the tails round to the same value, each is moved to one past its outer neighbour's (for 0.001 the first two, 1 and 1,
+    become 1 and 2, the last two 2^32 - 2 and 2^32 - 1), so that no offset in range has probability 0."""
+    var = float(var)
+    if not (math.isfinite(var) and var > 0.0):
+        raise StswinHipError(f"noise_var must be a positive number, got {var!r}")
+
+    def fits(v):                                            # (the k within one sigma alone have 2 s distinct thresholds)
+        return 255.0 * math.sqrt(v) <= MAX_THRESHOLDS and len(_law(v)) <= MAX_THRESHOLDS
+
+    if not fits(var):
+        lo, hi = 0.0, min(var, (MAX_THRESHOLDS / 255.0) ** 2)      # the number of thresholds grows with var: bisect for the largest that fits
+        for _ in range(40):
+            mid = 0.5 * (lo + hi)
+            lo, hi = (mid, hi) if fits(mid) else (lo, mid)
+        raise StswinHipError(f"noise_var {var!r} needs more than {MAX_THRESHOLDS} thresholds, which is what the kernel holds: the "
+                             f"largest var that fits is {lo:.6g}")
+    kept = _law(var)
+    return np.array([v for _, v in kept], dtype=np.uint32), kept[0][0]
+
+
 _PROTOCOL_DEFAULTS = {      # (p_hflip, p_vflip, p_bc) of the reference's A.Compose: Endovis2018_new.py:73-78, CATA_new_512.py:211-219
     "endovis18": (0.0, 0.5, 0.5),
     "cadis": (0.5, 0.5, 0.0),
 }
 
 
+def _noise_key(noise) -> Optional[int]:
+    if noise is None:
+        return None
+    key = int(noise)
+    if not 0 <= key < 1 << 64:
+        raise StswinHipError(f"noise must be None or a 64-bit key in [0, 2**64), got {noise!r}")
+    return key
+
+
 class ClipAugmenter:
     """aug = ClipAugmenter(crop=(512, 640), base_w=672, protocol="endovis18" | "cadis", class_num=None, source=None, p_hflip=None,
-                           p_vflip=None, p_bc=None, brightness_limit=0.2, contrast_limit=0.2, p_rotate=0.5, rotate_limit=90.0)
+                           p_vflip=None, p_bc=None, brightness_limit=0.2, contrast_limit=0.2, p_rotate=0.5, rotate_limit=90.0,
+                           p_noise=0.0, noise_var=0.001)
 
     crop = (Hc, Wc), base_w the reference's base_size['w'], source = (Hs, Ws) the stored frames' size (default: the crop size, as
     EndoVis18's Processed_train).  The probabilities default to the protocol's A.Compose; class_num (cadis: required) is the 255 ->
-    class_num - 1 label rule's.
+    class_num - 1 label rule's.  p_noise is the probability of CaDIS's Gaussian noise of variance noise_var (on the / 255. scale); it
+    is 0.0 by default for BOTH protocols - the reference's CaDIS transform uses 0.5, EndoVis18's has none.
 
     sample(B, rng, gen) draws B ClipParams; params(...) makes one explicitly; identity() is the no-augmentation one.
     aug(frames, labels, params, out=None): uint8 frames [B][4][Hs][Ws][3] and uint8 labels [B][Hs][Ws] on the GPU -> (fp32 images
@@ -160,7 +226,7 @@ class ClipAugmenter:
     def __init__(self, crop: Sequence[int] = (512, 640), base_w: int = 672, protocol: str = "endovis18", class_num: Optional[int] = None,
                  source: Optional[Sequence[int]] = None, p_hflip: Optional[float] = None, p_vflip: Optional[float] = None,
                  p_bc: Optional[float] = None, brightness_limit: float = 0.2, contrast_limit: float = 0.2, p_rotate: float = 0.5,
-                 rotate_limit: float = 90.0):
+                 rotate_limit: float = 90.0, p_noise: float = 0.0, noise_var: float = 0.001):
         video._check_rule(protocol)
         self.protocol = protocol
         self.crop = (int(crop[0]), int(crop[1]))
@@ -175,6 +241,8 @@ class ClipAugmenter:
         self.p_bc = d[2] if p_bc is None else float(p_bc)
         self.brightness_limit, self.contrast_limit = float(brightness_limit), float(contrast_limit)
         self.p_rotate, self.rotate_limit = float(p_rotate), float(rotate_limit)
+        self.p_noise, self.noise_var = float(p_noise), float(noise_var)
+        self.noise_law = noise_thresholds(self.noise_var)
         self.long_range = (int(self.base_w * 0.5), int(self.base_w * 2.0))
         if self.long_range[0] < 1:
             raise StswinHipError(f"base_w must be >= 2, got {base_w}")
@@ -184,12 +252,13 @@ class ClipAugmenter:
         self.ksize = max(bilinear_ksize(self.source[1], ow), bilinear_ksize(self.source[0], oh))       # the most taps any scale needs
         self._ws = {}
         self._luts = {}
+        self._thr = {}
         self._pinned = video._Pinned()
 
     # ----------------------------------------------------------------------------------------- parameters
     def params(self, long_size: int, x1: int, y1: int, hflip: bool = False, vflip: bool = False, alpha: Optional[float] = None,
-               beta: Optional[float] = None, angle: Optional[float] = None) -> ClipParams:
-        p = ClipParams(int(long_size), int(x1), int(y1), bool(hflip), bool(vflip), alpha, beta, angle)
+               beta: Optional[float] = None, angle: Optional[float] = None, noise: Optional[int] = None) -> ClipParams:
+        p = ClipParams(int(long_size), int(x1), int(y1), bool(hflip), bool(vflip), alpha, beta, angle, _noise_key(noise))
         self.scaled(p)
         return p
 
@@ -214,7 +283,9 @@ class ClipAugmenter:
         randint(int(base_w * 0.5), int(base_w * 2.0)), x1 = randint(0, w - Wc), y1 = randint(0, h - Hc) - `_random_scale`'s calls in
         its order, so the same seed gives the reference's geometry.  Then from gen (a numpy Generator; default: a fresh default_rng()),
         always seven draws in this order: u_hflip, u_vflip, u_bc, contrast ~ U(-limit, limit), brightness ~ U(-limit, limit), u_rotate,
-        angle ~ U(-limit, limit); a transform applies when its u < p.  This is NOT albumentations' stream."""
+        angle ~ U(-limit, limit); a transform applies when its u < p.  With p_noise != 0 two more follow, always both: u_noise =
+        gen.random() and key = gen.integers(0, 2**64, dtype=uint64); the sample gets the key when u_noise < p_noise.  This is NOT
+        albumentations' stream."""
         rng = random if rng is None else rng
         gen = np.random.default_rng() if gen is None else gen
         out = []
@@ -231,10 +302,15 @@ class ClipAugmenter:
             brightness = gen.uniform(-self.brightness_limit, self.brightness_limit)
             u_rot = gen.random()
             angle = gen.uniform(-self.rotate_limit, self.rotate_limit)
+            noise = None
+            if self.p_noise != 0.0:
+                u_noise = gen.random()
+                key = int(gen.integers(0, 2 ** 64, dtype=np.uint64))
+                noise = key if u_noise < self.p_noise else None
             bc = u[2] < self.p_bc
             out.append(ClipParams(long_size, x1, y1, bool(u[0] < self.p_hflip), bool(u[1] < self.p_vflip),
                                   1.0 + float(contrast) if bc else None, float(brightness) if bc else None,
-                                  float(angle) if u_rot < self.p_rotate else None))
+                                  float(angle) if u_rot < self.p_rotate else None, noise))
         return out
 
     # ----------------------------------------------------------------------------------------- host tables
@@ -272,6 +348,9 @@ class ClipAugmenter:
                 o += c[k].size
             if o != s1:
                 raise StswinHipError(f"stage 1's table row has {o} words, the library expects {s1}")
+            key = _noise_key(p.noise)
+            if key is not None:                                    # (int32 words: the halves' bit patterns)
+                t2[b, 1:4] = np.array([key & 0xffffffff, key >> 32, 1], np.uint32).view(np.int32)
             o = 4
             if p.angle is not None:
                 t2[b, 0] = 1
@@ -306,6 +385,13 @@ class ClipAugmenter:
             if self.protocol == "cadis":
                 lab[255] = self.class_num - 1                      # CATA_new_512.py:237
             t = self._luts[key] = (video._lut(dev, self.protocol), torch.from_numpy(lab).to(dev))
+        return t
+
+    def _thresholds(self, dev):
+        key = str(dev)
+        t = self._thr.get(key)
+        if t is None:
+            t = self._thr[key] = torch.from_numpy(self.noise_law[0].view(np.int32).copy()).to(dev)
         return t
 
     def _check_inputs(self, frames, labels, params):
@@ -378,11 +464,24 @@ class ClipAugmenter:
         lut, label_lut = self._lut(dev)
         return hip.augment_finish(crop, label_crop, images, labels_out, ws["t2"], lut, label_lut)
 
+    def noise_stage(self, crop: torch.Tensor, params: Sequence[ClipParams]) -> torch.Tensor:
+        """The noise pass alone, in place on uint8 crops [B][4][Hc][Wc][3] (only `noise` of params is used); returns crop."""
+        Hc, Wc = self.crop
+        hip.tensor_form(crop, torch.uint8, (None, T, Hc, Wc, 3), "crop", "noise_stage")
+        B, dev = crop.shape[0], crop.device
+        if len(params) != B:
+            raise StswinHipError(f"params must hold one ClipParams per sample: {B}, got {len(params)}")
+        ws = self._upload(B, dev, params)
+        return hip.augment_noise(crop, ws["t2"], self._thresholds(dev), self.noise_law[1])
+
     def __call__(self, frames: torch.Tensor, labels: torch.Tensor, params: Sequence[ClipParams], out=None):
         B = self._check_inputs(frames, labels, params)
         dev = frames.device
         images, labels_out = self._outputs(out, B, dev)
         ws = self._upload(B, dev, params)
         lut, label_lut = self._lut(dev)
+        thr = self._thresholds(dev)
         hip.augment_crop(frames, labels, ws["tmp"], ws["crop"], ws["label_crop"], ws["t1"], self.ksize)
+        if any(p.noise is not None for p in params):
+            hip.augment_noise(ws["crop"], ws["t2"], thr, self.noise_law[1])
         return hip.augment_finish(ws["crop"], ws["label_crop"], images, labels_out, ws["t2"], lut, label_lut)

@@ -1298,7 +1298,7 @@ extern "C" int stswin_clip_assemble(int dtype, void* ring, const void* fresh, vo
 // row (< 0: padding, label 0).
 // ---------------------------------------------------------------------------------------------------
 #define AUG1_HEAD 4      // r0, r1, flags (1 = horizontal flip, 2 = vertical flip), 0
-#define AUG2_HEAD 4      // flags (1 = rotate), 0, 0, 0
+#define AUG2_HEAD 4      // flags (1 = rotate), then key0, key1, noise: read by augment_noise_kernel only
 
 // grid (Hs * Wc / 256, B * T): one thread per (source row, window column) of a frame
 __global__ __launch_bounds__(256) void augment_hpass_kernel(const unsigned char* __restrict__ in, unsigned char* __restrict__ tmp,
@@ -1446,6 +1446,126 @@ extern "C" int stswin_augment_finish(const unsigned char* crop, const unsigned c
   if ((long)Hc * Wc > (1L << 28) || B > 65535) return -1818;
   hipLaunchKernelGGL(augment_finish_kernel, dim3((unsigned)((Hc * Wc + 255) / 256), (unsigned)B), dim3(256), 0, (hipStream_t)stream,
                      crop, label_crop, images, labels_out, table, table_stride, lut, lut_planes ? 256 : 0, label_lut, T, Hc, Wc);
+  STSWIN_CHECK_LAUNCH();
+  return 0;
+}
+
+// Between the stages, CaDIS's Gaussian noise (segcata/dataset/CATA_new_512.py:178-183) in place on stage 1's uint8 crop.  The
+// reference stores (255 * clip(u / 255. + n, 0, 1)).astype('uint8') = clamp(u + floor(255 n), 0, 255): an integer offset K with a
+// fixed discrete law, which the host states as ascending 32-bit thresholds (K = k_min + the number of thresholds <= r for a uniform
+// 32-bit r).  r comes from Philox4x32-10 (Salmon et al., Random123) keyed by the sample's 64-bit key from words 1, 2 of its stage-2
+// table row and counted by the byte index: bytes 4c .. 4c + 3 of a sample take the four words of counter (c, 0, 0, 0).  A byte's
+// noise is therefore a function of (key, byte index) alone: launch geometry, alignment and the path taken do not enter.
+DEVI void philox4x32_10(unsigned c0, unsigned k0, unsigned k1, unsigned (&w)[4]) {
+  unsigned c1 = 0u, c2 = 0u, c3 = 0u;
+#pragma unroll
+  for (int round = 0; round < 10; ++round) {
+    const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+    const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+    c0 = hi1 ^ c1 ^ k0;
+    c1 = lo1;
+    c2 = hi0 ^ c3 ^ k1;
+    c3 = lo0;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  w[0] = c0, w[1] = c1, w[2] = c2, w[3] = c3;
+}
+
+#define AUGN_MAX_THR 1024
+#define AUGN_MIN_STRIDE (AUG2_HEAD + 2L * (1 + 1) + 64)      // stswin_augment_finish_table_stride(1, 1): the shortest stage-2 row
+
+// #{j < n : thr[j] < v}, thr ascending
+DEVI int augn_count_below(const unsigned* thr, int n, unsigned v) {
+  int lo = 0, hi = n;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (thr[mid] < v) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+// clamp(u + k_min + #{j : thr[j] <= r}, 0, 255).  guide[t] = #{j : thr[j] < t << 24} (guide[256] = n), so the top byte of r
+// brackets the count (most brackets hold no or one threshold; the tails of the law, dense near 0 and 2^32, fall into the first and
+// the last); a binary search inside the bracket finishes.  Indices stay inside [0, n) whatever the thresholds hold.
+DEVI unsigned augn_byte(unsigned u, unsigned r, const unsigned* thr, const unsigned short* guide, int k_min) {
+  int lo = guide[r >> 24], hi = guide[(r >> 24) + 1];
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (thr[mid] <= r) lo = mid + 1; else hi = mid;
+  }
+  const int v = (int)u + k_min + lo;
+  return (unsigned)(v < 0 ? 0 : (v > 255 ? 255 : v));
+}
+
+// one 4-byte unit, bytes in memory order (little endian), of counter `unit`
+DEVI unsigned augn_word(unsigned word, unsigned unit, unsigned k0, unsigned k1, const unsigned* thr, const unsigned short* guide,
+                        int k_min) {
+  unsigned w[4];
+  philox4x32_10(unit, k0, k1, w);
+  unsigned out = 0u;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) out |= augn_byte((word >> (8 * j)) & 0xffu, w[j], thr, guide, k_min) << (8 * j);
+  return out;
+}
+
+// grid (blocks per sample, samples): a sample with noise == 0 is left alone.  A sample is `units` 4-byte units.  Those from the
+// first 16-byte aligned address on go four at a time through 16-byte loads and stores (the wide body); the `head` units in front
+// of it and the < 4 behind it, or every unit of a sample whose base is not 4-byte aligned, go byte by byte (the narrow body).
+__global__ __launch_bounds__(256) void augment_noise_kernel(unsigned char* __restrict__ crop, const int* __restrict__ table, long tstride,
+                                                             const unsigned* __restrict__ thr_in, int n_thr, int k_min, int B,
+                                                             long sample_bytes) {
+  __shared__ unsigned thr[AUGN_MAX_THR];
+  __shared__ unsigned short guide[258];
+  for (int j = threadIdx.x; j < n_thr; j += 256) thr[j] = thr_in[j];
+  __syncthreads();
+  for (int t = threadIdx.x; t <= 256; t += 256)
+    guide[t] = (unsigned short)(t == 256 ? n_thr : augn_count_below(thr, n_thr, (unsigned)t << 24));
+  __syncthreads();
+  const long units = sample_bytes >> 2;
+  const long first = (long)blockIdx.x * 256 + threadIdx.x, step = (long)gridDim.x * 256;
+  for (int b = blockIdx.y; b < B; b += gridDim.y) {
+    const int* tab = table + (long)b * tstride;
+    if (tab[3] == 0) continue;
+    const unsigned k0 = (unsigned)tab[1], k1 = (unsigned)tab[2];
+    unsigned char* base = crop + (long)b * sample_bytes;
+    const unsigned long addr = (unsigned long)base;
+    long head = (addr & 3ul) ? units : (long)(((16ul - (addr & 15ul)) & 15ul) >> 2);
+    head = head > units ? units : head;
+    const long nwide = (units - head) >> 2, tail = units - head - 4 * nwide;
+    uint4* wide = (uint4*)(base + 4 * head);
+    for (long i = first; i < nwide; i += step) {
+      uint4 v = wide[i];
+      const unsigned unit = (unsigned)(head + 4 * i);
+      v.x = augn_word(v.x, unit, k0, k1, thr, guide, k_min);
+      v.y = augn_word(v.y, unit + 1u, k0, k1, thr, guide, k_min);
+      v.z = augn_word(v.z, unit + 2u, k0, k1, thr, guide, k_min);
+      v.w = augn_word(v.w, unit + 3u, k0, k1, thr, guide, k_min);
+      wide[i] = v;
+    }
+    for (long i = first; i < head + tail; i += step) {
+      const long unit = i < head ? i : i + 4 * nwide;
+      unsigned char* p = base + 4 * unit;
+      const unsigned word = (unsigned)p[0] | (unsigned)p[1] << 8 | (unsigned)p[2] << 16 | (unsigned)p[3] << 24;
+      const unsigned out = augn_word(word, (unsigned)unit, k0, k1, thr, guide, k_min);
+      p[0] = (unsigned char)out, p[1] = (unsigned char)(out >> 8), p[2] = (unsigned char)(out >> 16), p[3] = (unsigned char)(out >> 24);
+    }
+  }
+}
+
+extern "C" int stswin_augment_noise(unsigned char* crop, const int* table, long table_stride, const unsigned int* thr, int n_thr,
+                                    int k_min, int B, long sample_bytes, void* stream) {
+  if (B <= 0 || sample_bytes <= 0 || (sample_bytes & 3) || sample_bytes > (1L << 34)) return -1808;
+  if (crop == nullptr || table == nullptr || thr == nullptr) return -1809;
+  if (n_thr < 1 || n_thr > AUGN_MAX_THR) return -1810;
+  if (table_stride < AUGN_MIN_STRIDE) return -1819;
+  k_min = k_min < -2048 ? -2048 : (k_min > 2048 ? 2048 : k_min);      // (beyond +-(255 + 1024) every byte clamps the same way)
+  // a thread per 16-byte piece of a sample: the pass is bound by its dependent LDS reads, not by memory, and more waves hide more
+  // of them than longer threads save in table set-up (31.5 MB in 4 samples: 26 us so against 32 us at four pieces per thread)
+  long gx = (((sample_bytes + 15) >> 4) + 255) >> 8;
+  gx = gx > 4096 ? 4096 : gx;
+  hipLaunchKernelGGL(augment_noise_kernel, dim3((unsigned)gx, (unsigned)(B < 65535 ? B : 65535)), dim3(256), 0, (hipStream_t)stream, crop,
+                     table, table_stride, thr, n_thr, k_min, B, sample_bytes);
   STSWIN_CHECK_LAUNCH();
   return 0;
 }

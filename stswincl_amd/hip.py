@@ -1522,6 +1522,31 @@ def augment_finish(crop: torch.Tensor, label_crop: torch.Tensor, images: torch.T
     return images, labels_out
 
 
+def augment_noise(crop: torch.Tensor, table: torch.Tensor, thr: torch.Tensor, k_min: int):
+    """CaDIS's Gaussian noise between the stages, in place: uint8 `crop` [B][...] (any trailing shape; a sample's bytes must be a
+    multiple of 4), the stage-2 int32 `table` [B][stride] whose words 1 .. 3 hold (key low, key high, noise on), and the law as
+    ascending thresholds `thr` (int32 holding the uint32 bit patterns, as torch has no uint32 arithmetic to offer; <= 1024 of them)
+    with `k_min` (include/stswin_hip.h, stswin_augment_noise).  A sample with noise == 0 is not written."""
+    fn = "augment_noise"
+    if not isinstance(crop, torch.Tensor) or crop.dim() < 2:
+        raise StswinHipError(f"{fn}: crop must be a contiguous uint8 [B][...] on the GPU, got {type(crop).__name__}"
+                             + (f" {tuple(crop.shape)}" if isinstance(crop, torch.Tensor) else ""))
+    tensor_form(crop, torch.uint8, (None,) * crop.dim(), "crop", fn)
+    B, dev = crop.shape[0], crop.device
+    sample_bytes = crop.numel() // B if B else 0
+    if B == 0 or sample_bytes == 0 or sample_bytes % 4:
+        raise StswinHipError(f"{fn}: a sample of crop must hold a positive multiple of 4 bytes, got {tuple(crop.shape)}")
+    tensor_form(table, torch.int32, (B, None), "table", fn, dev)
+    if table.shape[1] < augment_finish_table_stride(1, 1):
+        raise StswinHipError(f"{fn}: table rows must hold >= {augment_finish_table_stride(1, 1)} words (stage 2's rows), got {table.shape[1]}")
+    tensor_form(thr, torch.int32, (None,), "thr", fn, dev)
+    if not 1 <= thr.shape[0] <= 1024:
+        raise StswinHipError(f"{fn}: thr must hold 1 .. 1024 thresholds, got {thr.shape[0]}")
+    _check(load().stswin_augment_noise(_p(crop), _p(table), table.shape[1], _p(thr), thr.shape[0], int(k_min), B, sample_bytes,
+                                       _stream()), fn)
+    return crop
+
+
 def contrast_views_table_stride(H: int, W: int, ksize: int) -> int:
     return int(load().stswin_contrast_views_table_stride(H, W, ksize))
 
