@@ -565,6 +565,22 @@ int stswin_upsample_argmax_cm(int dtype, const void* logits, unsigned char* labe
  * Errors: -1415 n, H or W <= 0; -1416 labels, table or out NULL; -1417 edge_alpha outside -1 .. 255. */
 int stswin_labels_overlay(const unsigned char* labels, const unsigned char* frames, const unsigned char* table, unsigned char* out,
                           int n, int H, int W, int edge_alpha, void* stream);
+/* ---- ground truth as the files hold it -> class indices (stswincl_amd/utils/groundtruth.py, VideoSegmenter(gt_table=...)): in uint8
+ * [n][H][W][ch], out [n][H][W] of out_bytes = 1 (uint8, what stswin_labels_overlay reads) or 8 (int64, what stswin_upsample_argmax
+ * and stswin_upsample_argmax_cm read as gt).
+ *   ch = 3 | 4, colour-coded (seg18/dataset/Endovis2018_new.py:130-136): table uint8 [ncolours][4] = (r, g, b, label), 1 <= ncolours
+ *     <= 256.  A pixel takes the label of the LAST row whose (r, g, b) equals its first three channels exactly (the fourth channel
+ *     is not looked at); a pixel that equals no row gets 0 and, when `unmatched` (int32 [n], may be NULL) is given, adds 1 to
+ *     unmatched[its frame].  unmatched is accumulated, never cleared: the caller zeroes it once per evaluation.
+ *   ch = 1, id-coded (segcata/dataset/CATA_new_512.py:97, 237): table uint8 [256], out = table[u]; ncolours is range-checked and
+ *     otherwise unused, unmatched is left alone.
+ * One launch, no scratch buffer, no synchronisation (graph-capturable).  Any pointer alignment, any W: `in` 16-byte (ch = 4) or
+ * 4-byte (ch = 1, 3) aligned together with `out` 4-byte (uint8) or 16-byte (int64) aligned takes the body with 4 pixels per thread,
+ * anything else the byte body.  Integer atomics only (exact, independent of order).
+ * Errors: -1418 n, H or W <= 0; -1419 in, table or out NULL; -1420 ch not 1, 3 or 4; -1421 ncolours outside 1 .. 256; -1422 out_bytes
+ * not 1 or 8; -1423 out overlaps in. */
+int stswin_gt_decode(const unsigned char* in, const unsigned char* table, void* out, int* unmatched, int n, int H, int W, int ch,
+                     int ncolours, int out_bytes, void* stream);
 
 /* ---- video inference (stswincl_amd/video.py), the evaluation loop of seg18/test.py:147-175 over the clips of
  * seg18/dataset/Endovis2018_new.py:109-127.

@@ -1278,6 +1278,163 @@ extern "C" int stswin_labels_overlay(const unsigned char* labels, const unsigned
   return 0;
 }
 
+// Ground truth as the files hold it -> class indices (what seg18/dataset/Endovis2018_new.py:130-136 and segcata/dataset/
+// CATA_new_512.py:97, 237 do on the host).  CH = 3 | 4: the pixel's (r, g, b) is looked up in a table of up to 256 rows (r, g, b,
+// label), the last equal row wins, none gives 0 and counts the pixel as unmatched; CH = 1: out = table[u].  The table sits in LDS, a
+// colour row as r | g << 8 | b << 16 | label << 24, so the search is one broadcast LDS read per row and a compare per pixel.  The
+// pixels of all frames are one flat run.  The wide body gives a thread GT_PPT = 4 consecutive pixels: 16 bytes of RGBA, three dwords
+// of RGB or one dword of ids in, one dword of uint8 or two 16-byte stores of int64 out, so it needs `in` 16-byte (RGBA) or 4-byte
+// aligned and `out` 4-byte (uint8) or 16-byte (int64) aligned, and nothing of W or H * W; the last N % 4 pixels, and every pixel when
+// a pointer is not so aligned, go byte by byte.  Unmatched pixels: a workgroup counts those of the frame its first pixel lies in
+// in LDS and adds them with one atomic if there are any; a pixel of a later frame (a workgroup that straddles a frame border)
+// adds itself.
+#define GT_PPT 4
+
+template <int CH, typename OT, typename IT, bool WIDE>
+__global__ __launch_bounds__(256) void gt_decode_kernel(const unsigned char* in, const unsigned char* table, OT* out, int* unmatched,
+                                                        IT N, IT HW, int ncolours) {
+  constexpr int PPT = WIDE ? GT_PPT : 1;
+  __shared__ unsigned tab[256];
+  __shared__ int missed;
+  if (CH == 1) {
+    tab[threadIdx.x] = table[threadIdx.x];                     // 256 threads, 256 entries
+  } else if ((int)threadIdx.x < ncolours) {
+    const unsigned char* t = table + 4 * threadIdx.x;          // byte by byte: any alignment
+    tab[threadIdx.x] = (unsigned)t[0] | ((unsigned)t[1] << 8) | ((unsigned)t[2] << 16) | ((unsigned)t[3] << 24);
+  }
+  if (threadIdx.x == 0) missed = 0;
+  __syncthreads();
+  const IT first = (IT)blockIdx.x * (256 * PPT);               // the workgroup's first pixel (< N: the grid is ceil(N / (256 PPT)))
+  const IT p = first + (IT)threadIdx.x * PPT;
+  const int cnt = p >= N ? 0 : (N - p >= (IT)PPT ? PPT : (int)(N - p));
+  unsigned k[PPT], lab[PPT];
+  bool miss[PPT];
+#pragma unroll
+  for (int j = 0; j < PPT; ++j) k[j] = 0u;
+  if (WIDE && cnt == PPT) {
+    if (CH == 4) {
+      const uint4 v = *reinterpret_cast<const uint4*>(in + 4 * p);
+      k[0] = v.x & 0xffffffu;
+      k[1 % PPT] = v.y & 0xffffffu;
+      k[2 % PPT] = v.z & 0xffffffu;
+      k[3 % PPT] = v.w & 0xffffffu;
+    } else if (CH == 3) {
+      const unsigned* w = reinterpret_cast<const unsigned*>(in + 3 * p);
+      const unsigned w0 = w[0], w1 = w[1], w2 = w[2];
+      k[0] = w0 & 0xffffffu;
+      k[1 % PPT] = (w0 >> 24) | ((w1 & 0xffffu) << 8);
+      k[2 % PPT] = (w1 >> 16) | ((w2 & 0xffu) << 16);
+      k[3 % PPT] = w2 >> 8;
+    } else {
+      const unsigned w = *reinterpret_cast<const unsigned*>(in + p);
+#pragma unroll
+      for (int j = 0; j < PPT; ++j) k[j] = (w >> (8 * j)) & 255u;
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < PPT; ++j) {
+      if (j < cnt) {
+        const unsigned char* s = in + (IT)CH * (p + j);
+        k[j] = CH == 1 ? (unsigned)s[0] : ((unsigned)s[0] | ((unsigned)s[1 % CH] << 8) | ((unsigned)s[2 % CH] << 16));
+      }
+    }
+  }
+  if (CH == 1) {
+#pragma unroll
+    for (int j = 0; j < PPT; ++j) {
+      lab[j] = tab[k[j]];
+      miss[j] = false;
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < PPT; ++j) {
+      lab[j] = 0u;
+      miss[j] = true;
+    }
+    for (int i = 0; i < ncolours; ++i) {                       // rows in order: a later equal row overwrites
+      const unsigned e = tab[i];
+#pragma unroll
+      for (int j = 0; j < PPT; ++j) {
+        if ((e & 0xffffffu) == k[j]) {
+          lab[j] = e >> 24;
+          miss[j] = false;
+        }
+      }
+    }
+  }
+  if (WIDE && cnt == PPT) {
+    if (sizeof(OT) == 1) {
+      *reinterpret_cast<unsigned*>(out + p) = lab[0] | (lab[1 % PPT] << 8) | (lab[2 % PPT] << 16) | (lab[3 % PPT] << 24);
+    } else {
+      uint4* o = reinterpret_cast<uint4*>(out + p);
+      o[0] = make_uint4(lab[0], 0u, lab[1 % PPT], 0u);
+      o[1] = make_uint4(lab[2 % PPT], 0u, lab[3 % PPT], 0u);
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < PPT; ++j)
+      if (j < cnt) out[p + j] = (OT)lab[j];
+  }
+  if (CH != 1 && unmatched != nullptr) {                       // (uniform: no thread has left the kernel)
+    const IT f0 = first / HW;
+    int mine = 0;
+#pragma unroll
+    for (int j = 0; j < PPT; ++j) {
+      if (j < cnt && miss[j]) {
+        const IT f = (p + j) / HW;
+        if (f == f0) ++mine;
+        else atomicAdd(unmatched + f, 1);
+      }
+    }
+    if (mine) atomicAdd(&missed, mine);
+    __syncthreads();
+    if (threadIdx.x == 0 && missed) atomicAdd(unmatched + f0, missed);
+  }
+}
+
+template <int CH, typename OT>
+static void gt_decode_launch(const unsigned char* in, const unsigned char* table, void* out, int* unmatched, long N, long HW, int ncolours,
+                             bool wide, bool small, dim3 grid, hipStream_t st) {
+  OT* o = (OT*)out;
+  if (wide) {
+    if (small) hipLaunchKernelGGL((gt_decode_kernel<CH, OT, unsigned, true>), grid, dim3(256), 0, st, in, table, o, unmatched, (unsigned)N, (unsigned)HW, ncolours);
+    else hipLaunchKernelGGL((gt_decode_kernel<CH, OT, long, true>), grid, dim3(256), 0, st, in, table, o, unmatched, N, HW, ncolours);
+  } else {
+    if (small) hipLaunchKernelGGL((gt_decode_kernel<CH, OT, unsigned, false>), grid, dim3(256), 0, st, in, table, o, unmatched, (unsigned)N, (unsigned)HW, ncolours);
+    else hipLaunchKernelGGL((gt_decode_kernel<CH, OT, long, false>), grid, dim3(256), 0, st, in, table, o, unmatched, N, HW, ncolours);
+  }
+}
+
+extern "C" int stswin_gt_decode(const unsigned char* in, const unsigned char* table, void* out, int* unmatched, int n, int H, int W,
+                                int ch, int ncolours, int out_bytes, void* stream) {
+  if (n <= 0 || H <= 0 || W <= 0) return -1418;
+  if (in == nullptr || table == nullptr || out == nullptr) return -1419;
+  if (ch != 1 && ch != 3 && ch != 4) return -1420;
+  if (ncolours < 1 || ncolours > 256) return -1421;
+  if (out_bytes != 1 && out_bytes != 8) return -1422;
+  const long HW = (long)H * W, N = (long)n * HW;
+  const uintptr_t i0 = (uintptr_t)in, o0 = (uintptr_t)out;
+  if (i0 < o0 + (uintptr_t)(N * out_bytes) && o0 < i0 + (uintptr_t)(N * ch)) return -1423;
+  const bool wide = (i0 & (ch == 4 ? 15 : 3)) == 0 && (o0 & (out_bytes == 8 ? 15 : 3)) == 0;
+  const bool small = 4 * N + 256 * GT_PPT < (1L << 31);        // every index the kernels form fits 32 bits
+  const long per = 256L * (wide ? GT_PPT : 1);
+  const long blocks = (N + per - 1) / per;
+  if (blocks > 0x7fffffffL) return -1418;
+  dim3 grid((unsigned)blocks);
+  hipStream_t st = (hipStream_t)stream;
+#define GT_LAUNCH(CH_)                                                                                                      \
+  do {                                                                                                                      \
+    if (out_bytes == 8) gt_decode_launch<CH_, long>(in, table, out, unmatched, N, HW, ncolours, wide, small, grid, st); \
+    else gt_decode_launch<CH_, unsigned char>(in, table, out, unmatched, N, HW, ncolours, wide, small, grid, st);         \
+  } while (0)
+  if (ch == 1) GT_LAUNCH(1);
+  else if (ch == 3) GT_LAUNCH(3);
+  else GT_LAUNCH(4);
+#undef GT_LAUNCH
+  STSWIN_CHECK_LAUNCH();
+  return 0;
+}
+
 
 // ----------------------------------------------------------------------------------------- statistics from a GEMM epilogue
 // A convolution GEMM launched with STSWIN_GF_CS_PARTIAL | STSWIN_GF_CS_SQ leaves per-128-row-block column sums and sums of

@@ -1395,6 +1395,43 @@ def labels_overlay(labels: torch.Tensor, table: torch.Tensor, frames: Optional[t
     return out
 
 
+def gt_decode(src: torch.Tensor, table: torch.Tensor, out_dtype: torch.dtype = torch.uint8, unmatched: Optional[torch.Tensor] = None,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Stored ground truth -> class indices [n][H][W] of out_dtype torch.uint8 (what labels_overlay reads) or torch.int64 (what
+    upsample_argmax / upsample_argmax_cm read as gt).  src uint8 [n][H][W][3 | 4] with table uint8 [k][4] = (r, g, b, label), 1 <= k
+    <= 256 (utils.groundtruth.colour_table): the label of the last row equal to the pixel's first three channels, 0 where none is,
+    and such pixels counted per frame into `unmatched` (int32 [n], accumulated, None = not counted).  src uint8 [n][H][W] with table
+    uint8 [256] (utils.groundtruth.remap_table): table[u].  `out` must not share memory with src; returns out
+    (include/stswin_hip.h, stswin_gt_decode)."""
+    if src.dtype != torch.uint8 or src.dim() not in (3, 4) or not src.is_contiguous() or (src.dim() == 4 and src.shape[3] not in (3, 4)):
+        raise StswinHipError(f"gt_decode: src must be contiguous uint8 [n][H][W] or [n][H][W][3 | 4], got {src.dtype} {tuple(src.shape)}")
+    n, H, W = src.shape[:3]
+    ch = 1 if src.dim() == 3 else src.shape[3]
+    if n <= 0 or H <= 0 or W <= 0:
+        raise StswinHipError(f"gt_decode: empty src {tuple(src.shape)}")
+    if out_dtype not in (torch.uint8, torch.int64):
+        raise StswinHipError(f"gt_decode: out_dtype must be torch.uint8 or torch.int64, got {out_dtype}")
+    want = (256,) if ch == 1 else (table.shape[0] if table.dim() == 2 and 1 <= table.shape[0] <= 256 else -1, 4)
+    if table.dtype != torch.uint8 or tuple(table.shape) != want or not table.is_contiguous() or table.device != src.device:
+        form = "[256]" if ch == 1 else "[1 .. 256][4]"
+        raise StswinHipError(f"gt_decode: the table of {ch}-channel ground truth must be contiguous uint8 {form} on {src.device}, got "
+                             f"{table.dtype} {tuple(table.shape)} on {table.device}")
+    if unmatched is not None and (unmatched.dtype != torch.int32 or tuple(unmatched.shape) != (n,) or not unmatched.is_contiguous()
+                                  or unmatched.device != src.device):
+        raise StswinHipError(f"gt_decode: unmatched must be contiguous int32 [{n}] on {src.device}, got {unmatched.dtype} "
+                             f"{tuple(unmatched.shape)} on {unmatched.device}")
+    if out is None:
+        out = torch.empty(n, H, W, dtype=out_dtype, device=src.device)
+    elif out.dtype != out_dtype or tuple(out.shape) != (n, H, W) or not out.is_contiguous() or out.device != src.device:
+        raise StswinHipError(f"gt_decode: out must be contiguous {out_dtype} [{n}][{H}][{W}] on {src.device}, got {out.dtype} "
+                             f"{tuple(out.shape)} on {out.device}")
+    elif _same_memory(out, src):
+        raise StswinHipError("gt_decode: out shares memory with src")
+    _check(load().stswin_gt_decode(_p(src), _p(table), _p(out), _p(unmatched), n, H, W, ch, table.shape[0], out.element_size(),
+                                   _stream()), "gt_decode")
+    return out
+
+
 def _int_table(t: Optional[torch.Tensor], rows: int, what: str):
     if t is None:
         raise StswinHipError(f"frame_ingest: the {what} table is missing")

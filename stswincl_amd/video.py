@@ -321,12 +321,24 @@ class VideoSegmenter:
     every output form: leave it unchanged until its result has come back); under graph=True the captured step ends with the label
     and the overlay launch on the static frame buffer, and the result is a view of the graph's output buffer as above.
 
+    gt_table (utils.groundtruth.colour_table or remap_table; both protocols): gt is then the ground truth as the files hold it, uint8
+    [n][*out_size][3 | 4] colour-coded with a [k][4] table or uint8 [n][*out_size] raw ids with a [256] table, on the CPU or the GPU.
+    The bytes are uploaded as they are and decoded to the int64 index map on the device (hip.gt_decode) when they are pushed; scoring
+    then proceeds as with an int64 gt.  unmatched() is the pooled number of colour-coded pixels that no table row holds.
+
+    scores="deferred" (endovis18): a scored frame's counts go into a device log instead of to the host - no download and no
+    synchronisation per frame - and push returns the labels (logits, overlay) alone, as cadis does; under graph=True the counting
+    launch runs after the replayed step.  endo_scores() downloads the log once and returns utils.EndoMetric.EndoScores: the per-frame
+    lists that scores="frame" (the default) returns, and the reference's val_map aggregates, per sequence too: a sequence's ordinal
+    is the number of earlier sequences that scored a frame since reset_metrics(), which clears the log.
+
     Runs under torch.no_grad().  Refuses (StswinHipError): a model in train mode, a model or frames not on the GPU, a frame size
     that differs from the earlier frames'."""
 
     def __init__(self, model, batch: int = 1, out: str = "logits", out_size: Optional[Sequence[int]] = None, graph: bool = False,
                  protocol: str = "endovis18", metric_classes: Optional[int] = None, align_corners: Optional[bool] = None,
-                 palette=None, alpha: int = 128, transparent: Optional[Sequence[int]] = None, edge_alpha: Optional[int] = 255):
+                 palette=None, alpha: int = 128, transparent: Optional[Sequence[int]] = None, edge_alpha: Optional[int] = 255,
+                 gt_table=None, scores: str = "frame"):
         if out not in ("logits", "labels", "overlay"):
             raise StswinHipError(f"out must be 'logits', 'labels' or 'overlay', got {out!r}")
         if out != "overlay" and (palette is not None or transparent is not None):
@@ -336,6 +348,10 @@ class VideoSegmenter:
         _check_rule(protocol)
         if protocol == "endovis18" and (align_corners is False or metric_classes is not None):
             raise StswinHipError("align_corners=False and metric_classes belong to protocol='cadis'")
+        if scores not in ("frame", "deferred"):
+            raise StswinHipError(f"scores must be 'frame' or 'deferred', got {scores!r}")
+        if scores == "deferred" and protocol != "endovis18":
+            raise StswinHipError("scores='deferred' belongs to protocol='endovis18' (protocol='cadis' pools its counts in confusion_matrix())")
         self.model = model
         self._check_train()
         if any(not p.is_cuda for p in model.parameters()):
@@ -358,6 +374,20 @@ class VideoSegmenter:
             if not 1 <= self.metric_classes <= 64:
                 raise StswinHipError(f"metric_classes must be 1 .. 64, got {self.metric_classes}")
         self._cm = None
+        self.scores = scores
+        self._log = None                  # scores="deferred": int32 [capacity][3][nc] on the device, one row per scored frame ...
+        self._log_rows = []               # ... and per row (sequence ordinal, frame index) on the host
+        self._seq = 0
+        self._seq_logged = False
+        self._gt_table = None
+        self._unmatched = None
+        if gt_table is not None:
+            t = torch.as_tensor(gt_table)
+            if t.dtype != torch.uint8 or not (tuple(t.shape) == (256,) or (t.dim() == 2 and t.shape[1] == 4 and 1 <= t.shape[0] <= 256)):
+                raise StswinHipError("gt_table must be uint8 [1 .. 256][4] (utils.groundtruth.colour_table) or uint8 [256] "
+                                     f"(utils.groundtruth.remap_table), got {t.dtype} {tuple(t.shape)}")
+            self._gt_table = t.contiguous().to(self.device)
+            self._unmatched = torch.zeros(1, dtype=torch.int32, device=self.device)
         self._table = None
         if out == "overlay":
             from .utils.visualize import default_palette, overlay_table
@@ -389,11 +419,55 @@ class VideoSegmenter:
         self._frames = {}                 # frame index -> (uint8 tensor [k][Hs][Ws][3], GPU or CPU, row) until its ResNet pass
         self._kept = {}                   # out="overlay": frame index -> GPU uint8 [1][Hs][Ws][3] from its ResNet pass until its clip's result
         self._gt = {}
+        if self._seq_logged:              # scores="deferred": the sequence that ends here has rows in the log
+            self._seq += 1
+            self._seq_logged = False
 
     def reset_metrics(self) -> None:
-        """protocol="cadis": clear the confusion matrix (reset() keeps it: it pools every sequence of an evaluation)."""
+        """Clear what an evaluation pools and reset() keeps: the confusion matrix (protocol="cadis"), the score log and its sequence
+        ordinal (scores="deferred"), the count of unmatched ground-truth pixels (gt_table)."""
         if self._cm is not None:
             self._cm.zero_()
+        self._log_rows = []
+        self._seq = 0
+        self._seq_logged = False
+        if self._unmatched is not None:
+            self._unmatched.zero_()
+
+    def unmatched(self) -> int:
+        """gt_table: the pixels of colour-coded ground truth pushed so far whose colour no table row holds (they count as class 0),
+        pooled over frames and sequences until reset_metrics().  One download."""
+        if self._gt_table is None:
+            raise StswinHipError("unmatched() belongs to gt_table")
+        return int(self._unmatched.item())
+
+    def endo_scores(self):
+        """scores="deferred": one download of the score log -> utils.EndoMetric.EndoScores over every frame scored since
+        reset_metrics(): the per-frame lists scores="frame" returns, and val_map's aggregates.  Row r of its lists is frame
+        .frames[r] of sequence .sequences[r], rows ordered by sequence and frame."""
+        if self.scores != "deferred":
+            raise StswinHipError("endo_scores() belongs to scores='deferred'")
+        from .utils.EndoMetric import EndoScores
+        n = len(self._log_rows)
+        nc = self.model.classifier[-1].out_channels
+        counts = self._log[:n].cpu().numpy() if n else np.zeros((0, 3, nc), dtype=np.int32)
+        order = sorted(range(n), key=lambda r: self._log_rows[r])      # the log is in release order (frame 4 before frame 1 ...);
+        rows = [self._log_rows[r] for r in order]                      # the reference sums in frame order
+        res = EndoScores.from_counts(counts[order], [s for s, _ in rows])
+        res.frames = [f for _, f in rows]
+        return res
+
+    def _log_counts(self, frame: int, counts: torch.Tensor) -> None:
+        """Append one frame's counts [1][3][nc] to the device log (a device copy; the log doubles when full)."""
+        n = len(self._log_rows)
+        if self._log is None or n == self._log.shape[0]:
+            grown = torch.zeros(max(64, 2 * n), *counts.shape[1:], dtype=torch.int32, device=self.device)
+            if n:
+                grown[:n].copy_(self._log)
+            self._log = grown
+        self._log[n:n + 1].copy_(counts)
+        self._log_rows.append((self._seq, frame))
+        self._seq_logged = True
 
     def confusion_matrix(self) -> np.ndarray:
         """protocol="cadis": the pooled confusion matrix, float64 [metric_classes][metric_classes], rows gt, columns prediction."""
@@ -408,7 +482,9 @@ class VideoSegmenter:
         self._check_train()
         fr = self._as_frames(frames)
         n = fr.shape[0]
-        if gt is not None:
+        if gt is not None and self._gt_table is not None:
+            gt = self._decode_gt(gt, n)
+        elif gt is not None:
             gt = torch.as_tensor(gt)
             if gt.dim() == 2:
                 gt = gt[None]
@@ -435,6 +511,26 @@ class VideoSegmenter:
         return [r for _, r in sorted(res, key=lambda fr: fr[0])]
 
     # ----------------------------------------------------------------------------------------- internals
+    def _decode_gt(self, gt, n: int) -> torch.Tensor:
+        """gt_table: stored ground truth (uint8, colour- or id-coded, CPU or GPU) -> int64 class indices [n][*out_size] on the device:
+        the bytes are uploaded as they are and decoded by one launch (hip.gt_decode), which also pools the unmatched pixels."""
+        gt = torch.as_tensor(gt)
+        colour = self._gt_table.dim() == 2
+        if gt.dim() == (3 if colour else 2):
+            gt = gt[None]
+        want = f"[{n}][{self.out_size[0]}][{self.out_size[1]}]" + ("[3 | 4]" if colour else "") if self.out_size else "of the output size"
+        if (gt.dtype != torch.uint8 or gt.dim() != (4 if colour else 3) or gt.shape[0] != n or tuple(gt.shape[1:3]) != self.out_size
+                or (colour and gt.shape[3] not in (3, 4))):
+            raise StswinHipError(f"with gt_table, gt must be uint8 {want}, got {gt.dtype} {tuple(gt.shape)}")
+        if gt.is_cuda and gt.device != self.device:
+            raise StswinHipError(f"gt on {gt.device}, the model on {self.device}")
+        gt = gt.contiguous()
+        if not gt.is_cuda:
+            gt = self._pinned.upload(gt.numpy(), torch.empty(gt.shape, dtype=torch.uint8, device=self.device))
+        H, W = self.out_size
+        flat = gt.view(1, n * H, W, gt.shape[3]) if colour else gt.view(1, n * H, W)    # one "frame": one pooled unmatched count
+        return hip.gt_decode(flat, self._gt_table, torch.int64, self._unmatched if colour else None).view(n, H, W)
+
     def _as_frames(self, frames) -> torch.Tensor:
         if isinstance(frames, np.ndarray):
             frames = torch.from_numpy(frames)
@@ -616,6 +712,11 @@ class VideoSegmenter:
                 continue
             if self.cadis:
                 lab = self._labels(logits[b:b + 1], gt, want=self.out != "logits")
+                res.append((g, lg if self.out == "logits" else final(b, lab)))
+                continue
+            if self.scores == "deferred":         # the counts stay on the device: no download, no synchronisation
+                lab, counts = hip.upsample_argmax(logits[b:b + 1], *self.out_size, gt)
+                self._log_counts(g, counts)
                 res.append((g, lg if self.out == "logits" else final(b, lab)))
                 continue
             from .utils.EndoMetric import predict_and_score
