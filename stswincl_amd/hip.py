@@ -1621,15 +1621,29 @@ def optim_tick(kind: int, counter: torch.Tensor, hyper: torch.Tensor, a: float, 
     _check(load().stswin_optim_tick(int(kind), _p(counter), _p(hyper), a, b, _stream()), "optim_tick")
 
 
+def _mt_lists(fn: str, ps, **lists) -> None:
+    """The kernels read every list through raw pointers with the parameters' element counts: each tensor must be contiguous fp32 on
+    the parameters' GPU and as long as its parameter (checked before any launch)."""
+    dev = ps[0].device if len(ps) else None
+    f32 = torch.float32
+    for name, ts in (("ps", ps), *lists.items()):
+        if ts is None:
+            continue
+        if len(ts) != len(ps):
+            raise StswinHipError(f"{fn}: {name} holds {len(ts)} tensors for {len(ps)} parameters")
+        for i, (t, p) in enumerate(zip(ts, ps)):
+            if not (t.is_cuda and t.device == dev and t.dtype == f32 and t.is_contiguous() and t.numel() == p.numel()):
+                raise StswinHipError(f"{fn}: {name}[{i}] must be a contiguous float32 tensor of {p.numel()} elements on {dev}, got "
+                                     f"{t.dtype} {tuple(t.shape)} on {t.device}" + ("" if t.is_contiguous() else " (not contiguous)"))
+
+
 def multi_tensor(mode, ps, gs, ms=None, vs=None, lr=0.0, b1=0.0, b2=0.0, eps=0.0, wd=0.0, c1=1.0, c2=1.0, hyper=None):
     """mode 0 Adam / 1 SGD-momentum / 2 EMA over lists of fp32 tensors (chunks of 48 tensors per launch).  hyper (device fp32 [4] =
     {lr, c1, c2, EMA momentum}): read the step-dependent scalars from it instead of lr / c1 / c2 / b1(EMA) - for SGD c1 != 0 still
     marks the first step."""
     lib = load()
     st = _stream()
-    for t in ps:
-        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
-            raise StswinHipError("multi_tensor needs contiguous fp32 GPU tensors")
+    _mt_lists("multi_tensor", ps, gs=gs, ms=ms, vs=vs)
     for lo in range(0, len(ps), 48):
         hi = min(len(ps), lo + 48)
         k = hi - lo
@@ -1646,12 +1660,15 @@ def multi_tensor(mode, ps, gs, ms=None, vs=None, lr=0.0, b1=0.0, b2=0.0, eps=0.0
 
 def multi_tensor_lars(ps, gs, ms, norms, *, lr, momentum, wd, trust_coef, eps, first, adaptive, hyper=None):
     """LARS-scaled SGD-momentum step of one parameter group (lists of contiguous fp32 GPU tensors; chunks of 48 tensors,
-    two launches each: norms, update).  norms: fp32 scratch of >= 96 floats."""
+    three launches each: partial norms, their fold, update).  norms: None, or fp32 scratch that every 48-tensor launch uses in turn
+    when it holds that launch's 2 * tensors + 2 * sum ceil(n / 8192) floats (the launch's [tensors][2] norms come first); a launch
+    that needs more takes the library's scratch instead."""
     lib = load()
     st = _stream()
-    for t in list(ps) + list(gs) + list(ms):
-        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
-            raise StswinHipError("multi_tensor_lars needs contiguous fp32 GPU tensors")
+    _mt_lists("multi_tensor_lars", ps, gs=gs, ms=ms)
+    if norms is not None and not (norms.is_cuda and norms.dtype == torch.float32 and norms.is_contiguous()
+                                  and (not len(ps) or norms.device == ps[0].device)):
+        raise StswinHipError("multi_tensor_lars: norms must be a contiguous float32 tensor on the parameters' GPU")
     for lo in range(0, len(ps), 48):
         hi = min(len(ps), lo + 48)
         k = hi - lo
