@@ -581,6 +581,30 @@ int stswin_labels_overlay(const unsigned char* labels, const unsigned char* fram
  * not 1 or 8; -1423 out overlaps in. */
 int stswin_gt_decode(const unsigned char* in, const unsigned char* table, void* out, int* unmatched, int n, int H, int W, int ch,
                      int ncolours, int out_bytes, void* stream);
+/* ---- frames as a video source delivers them (stswincl_amd/utils/yuv.py, VideoSegmenter(pixel_format=..., out_format="nv12")):
+ * stswin_yuv_to_rgb makes the HWC RGB frame uint8 [n][Hs][Ws][3] that stswin_frame_ingest and stswin_labels_overlay read,
+ * stswin_rgb_to_nv12 turns such a frame into NV12.  Hs (NV12) and Ws are even.
+ *   format 0, nv12: uint8 [n][3 Hs / 2][Ws]; rows 0 .. Hs-1 are luma, rows Hs .. are Hs / 2 rows of Ws / 2 interleaved (U, V) pairs.
+ *   format 1, uyvy: uint8 [n][Hs][Ws][2]; the four bytes of pixel pair (2k, 2k+1) are U, Y0, V, Y1.
+ * matrix is int32 [3][4] in device memory (utils.yuv.to_rgb_matrix / to_yuv_matrix): per output channel three coefficients in
+ * units of 2^-14 and an offset that holds the rounding half.  A triple t gives
+ *     out_c = clamp((m[c][0] t0 + m[c][1] t1 + m[c][2] t2 + m[c][3]) >> 14, 0, 255)      (arithmetic shift: a floor; int32 suffices)
+ * with t = (Y, U, V) -> (R, G, B) for stswin_yuv_to_rgb and t = (R, G, B) -> (Y, U, V) for stswin_rgb_to_nv12.
+ * Chroma of a pixel, C[j][k] one chroma plane:
+ *   chroma 0, replicate: pixel (y, x) uses C[y >> 1][x >> 1] (nv12) or C[y][x >> 1] (uyvy).
+ *   chroma 1, linear (MPEG-2 siting: co-sited with the even columns, vertically centred): nv12 first interpolates vertically,
+ *     row 2j: V[k] = (3 C[j][k] + C[max(j-1, 0)][k] + 2) >> 2, row 2j+1: V[k] = (3 C[j][k] + C[min(j+1, Hs/2 - 1)][k] + 2) >> 2
+ *     (uyvy: V is the row's own chroma); then both formats horizontally, x = 2k: V[k], x = 2k+1: (V[k] + V[min(k+1, Ws/2 - 1)] + 1) >> 1.
+ * stswin_rgb_to_nv12: luma per pixel from its own RGB through row 0; chroma through rows 1 and 2 from the 2 x 2 block's per-channel
+ * mean (sum of four + 2) >> 2.
+ * Each is one launch, no scratch buffer, no synchronisation, no atomics (graph-capturable).  Any pointer alignment, any even size:
+ * Ws % 8 == 0 with the pointers 8-byte (uyvy in: 16-byte) aligned takes the body with 8 pixels per thread and row (nv12: of both luma
+ * rows of a chroma row), anything else the body with 2.  Integer arithmetic only.
+ * Errors (both): -1424 n, Hs or Ws <= 0; -1425 in, matrix or out NULL; -1426 odd Ws, or odd Hs (nv12, stswin_rgb_to_nv12);
+ * -1427 format outside 0 .. 1; -1428 chroma outside 0 .. 1; -1429 out overlaps in (or matrix). */
+int stswin_yuv_to_rgb(const unsigned char* in, const int* matrix, unsigned char* out, int n, int Hs, int Ws, int format, int chroma,
+                      void* stream);
+int stswin_rgb_to_nv12(const unsigned char* in, const int* matrix, unsigned char* out, int n, int Hs, int Ws, void* stream);
 
 /* ---- video inference (stswincl_amd/video.py), the evaluation loop of seg18/test.py:147-175 over the clips of
  * seg18/dataset/Endovis2018_new.py:109-127.

@@ -1435,6 +1435,272 @@ extern "C" int stswin_gt_decode(const unsigned char* in, const unsigned char* ta
   return 0;
 }
 
+// Frames as a video source delivers them (stswincl_amd/utils/yuv.py states the arithmetic): NV12 or UYVY -> the HWC RGB frame that
+// stswin_frame_ingest and stswin_labels_overlay read, and RGB -> NV12.  matrix int32 [3][4]: out_c = clamp((m[c][0] t0 + m[c][1] t1 +
+// m[c][2] t2 + m[c][3]) >> 14, 0, 255) in int32 (|sum| < 2^25).  A thread owns YUV_PPT = 8 (wide body) or 2 (byte body) consecutive
+// pixels of one row, and for NV12 of the two luma rows that share a chroma row, so each (U, V) pair is fetched once: NV12 wide reads
+// two 8-byte luma runs and one 8-byte chroma run (linear: the rows above and below too, and one pair to the right as two bytes), UYVY
+// wide one 16-byte run; each RGB row of 24 bytes leaves as three 8-byte stores.  The wide body needs Ws % 8 == 0 (then every row and
+// every frame starts on the grid) and the pointers 8-byte (UYVY in: 16-byte) aligned; anything else takes the byte body.  Threads are
+// numbered (frame, row pair | row, group) with the group fastest: consecutive lanes read and write consecutive runs.
+#define YUV_PPT 8
+
+__device__ __forceinline__ unsigned yuv_channel(const int* m, int c, int t0, int t1, int t2) {
+  // clamp, then shift: the same value as clamp(v >> 14, 0, 255), the shift being monotonic.  Written the other way round the compiler
+  // packs two results with v_ashr_pk_u8_i32, which writes 16 bits, and ORs a third byte into the stale upper half of that register
+  const int v = m[4 * c] * t0 + m[4 * c + 1] * t1 + m[4 * c + 2] * t2 + m[4 * c + 3];
+  return (unsigned)(min(max(v, 0), (256 << 14) - 1) >> 14);
+}
+
+// NP (U, V) pairs from k0 on, and for LINEAR the pair kn to their right (already clamped to the row), of one NV12 chroma row
+template <bool WIDE, bool LINEAR, int NP>
+__device__ __forceinline__ void nv12_pairs(const unsigned char* row, int k0, int kn, int* u, int* v) {
+  if (WIDE) {
+    const uint2 w = *reinterpret_cast<const uint2*>(row + 2 * k0);
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+      const unsigned d = (i < 2 ? w.x : w.y) >> (16 * (i & 1));
+      u[i] = (int)(d & 255u);
+      v[i] = (int)((d >> 8) & 255u);
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+      u[i] = row[2 * (k0 + i)];
+      v[i] = row[2 * (k0 + i) + 1];
+    }
+  }
+  u[NP] = LINEAR ? (int)row[2 * kn] : 0;
+  v[NP] = LINEAR ? (int)row[2 * kn + 1] : 0;
+}
+
+template <int FMT, bool LINEAR, bool WIDE>
+__global__ __launch_bounds__(256) void yuv_to_rgb_kernel(const unsigned char* __restrict__ in, const int* __restrict__ matrix,
+                                                         unsigned char* __restrict__ out, unsigned total, int Hs, int Ws) {
+  constexpr int PX = WIDE ? YUV_PPT : 2, NP = PX / 2, ROWS = FMT == 0 ? 2 : 1;
+  const unsigned t = blockIdx.x * 256u + threadIdx.x;
+  if (t >= total) return;
+  int m[12];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) m[i] = matrix[i];
+  const unsigned G = (unsigned)(Ws / PX), R = (unsigned)(Hs / ROWS);
+  const unsigned g = t % G, fj = t / G;
+  const int j = (int)(fj % R);
+  const long f = (long)(fj / R);
+  const int k0 = (int)g * NP, kn = min(k0 + NP, Ws / 2 - 1);
+  int y[ROWS][PX], cu[ROWS][NP + 1], cv[ROWS][NP + 1];
+  if (FMT == 0) {
+    const unsigned char* fr = in + f * ((long)Hs * Ws / 2 * 3);
+    const unsigned char* cp = fr + (long)Hs * Ws;
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r) {
+      const unsigned char* lp = fr + (long)(2 * j + r) * Ws + (long)g * PX;
+      if (WIDE) {
+        const uint2 w = *reinterpret_cast<const uint2*>(lp);
+#pragma unroll
+        for (int i = 0; i < PX; ++i) y[r][i] = (int)(((i < 4 ? w.x : w.y) >> (8 * (i & 3))) & 255u);
+      } else {
+#pragma unroll
+        for (int i = 0; i < PX; ++i) y[r][i] = lp[i];
+      }
+    }
+    int u0[NP + 1], v0[NP + 1];
+    nv12_pairs<WIDE, LINEAR, NP>(cp + (long)j * Ws, k0, kn, u0, v0);
+    if (LINEAR) {
+      int ua[NP + 1], va[NP + 1], ub[NP + 1], vb[NP + 1];
+      nv12_pairs<WIDE, true, NP>(cp + (long)max(j - 1, 0) * Ws, k0, kn, ua, va);
+      nv12_pairs<WIDE, true, NP>(cp + (long)min(j + 1, (int)R - 1) * Ws, k0, kn, ub, vb);
+#pragma unroll
+      for (int i = 0; i <= NP; ++i) {
+        cu[0][i] = (3 * u0[i] + ua[i] + 2) >> 2;
+        cv[0][i] = (3 * v0[i] + va[i] + 2) >> 2;
+        cu[ROWS - 1][i] = (3 * u0[i] + ub[i] + 2) >> 2;
+        cv[ROWS - 1][i] = (3 * v0[i] + vb[i] + 2) >> 2;
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i <= NP; ++i) {
+        cu[0][i] = cu[ROWS - 1][i] = u0[i];
+        cv[0][i] = cv[ROWS - 1][i] = v0[i];
+      }
+    }
+  } else {
+    const unsigned char* rp = in + ((f * Hs + j) * Ws) * 2;
+    if (WIDE) {
+      const uint4 w = *reinterpret_cast<const uint4*>(rp + 4L * k0);
+      const unsigned d[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+      for (int i = 0; i < NP; ++i) {
+        cu[0][i] = (int)(d[i % 4] & 255u);
+        y[0][2 * i] = (int)((d[i % 4] >> 8) & 255u);
+        cv[0][i] = (int)((d[i % 4] >> 16) & 255u);
+        y[0][2 * i + 1] = (int)(d[i % 4] >> 24);
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < NP; ++i) {
+        const unsigned char* q = rp + 4L * (k0 + i);
+        cu[0][i] = q[0];
+        y[0][2 * i] = q[1];
+        cv[0][i] = q[2];
+        y[0][2 * i + 1] = q[3];
+      }
+    }
+    cu[0][NP] = LINEAR ? (int)rp[4L * kn] : 0;
+    cv[0][NP] = LINEAR ? (int)rp[4L * kn + 2] : 0;
+  }
+#pragma unroll
+  for (int r = 0; r < ROWS; ++r) {
+    unsigned o[3 * PX / 4 + 1];
+#pragma unroll
+    for (int i = 0; i < 3 * PX / 4 + 1; ++i) o[i] = 0u;
+    unsigned char* op = out + ((f * Hs + (ROWS * j + r)) * Ws + (long)g * PX) * 3;
+#pragma unroll
+    for (int i = 0; i < PX; ++i) {
+      const int k = i >> 1;
+      const int u = (LINEAR && (i & 1)) ? (cu[r][k] + cu[r][k + 1] + 1) >> 1 : cu[r][k];
+      const int v = (LINEAR && (i & 1)) ? (cv[r][k] + cv[r][k + 1] + 1) >> 1 : cv[r][k];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const unsigned b = yuv_channel(m, c, y[r][i], u, v);
+        if (WIDE) o[(3 * i + c) >> 2] |= b << (8 * ((3 * i + c) & 3));
+        else op[3 * i + c] = (unsigned char)b;
+      }
+    }
+    if (WIDE) {
+      uint2* ow = reinterpret_cast<uint2*>(op);
+#pragma unroll
+      for (int q = 0; q < 3 * PX / 8; ++q) ow[q] = make_uint2(o[2 * q], o[2 * q + 1]);
+    }
+  }
+}
+
+// RGB -> NV12: a thread owns the PX pixels of both luma rows of a chroma row: luma per pixel through row 0, the 2 x 2 block's
+// per-channel mean (sum + 2) >> 2 through rows 1 and 2.  Wide: three 8-byte loads per row, an 8-byte luma store per row, one 8-byte
+// chroma store; it needs Ws % 8 == 0 and both pointers 8-byte aligned.
+template <bool WIDE>
+__global__ __launch_bounds__(256) void rgb_to_nv12_kernel(const unsigned char* __restrict__ in, const int* __restrict__ matrix,
+                                                          unsigned char* __restrict__ out, unsigned total, int Hs, int Ws) {
+  constexpr int PX = WIDE ? YUV_PPT : 2, NP = PX / 2;
+  const unsigned t = blockIdx.x * 256u + threadIdx.x;
+  if (t >= total) return;
+  int m[12];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) m[i] = matrix[i];
+  const unsigned G = (unsigned)(Ws / PX), R = (unsigned)(Hs / 2);
+  const unsigned g = t % G, fj = t / G;
+  const int j = (int)(fj % R);
+  const long f = (long)(fj / R);
+  unsigned char* fr = out + f * ((long)Hs * Ws / 2 * 3);
+  int sum[NP][3];
+#pragma unroll
+  for (int k = 0; k < NP; ++k) sum[k][0] = sum[k][1] = sum[k][2] = 0;
+#pragma unroll
+  for (int r = 0; r < 2; ++r) {
+    const long px = (f * Hs + (2 * j + r)) * Ws + (long)g * PX;
+    const unsigned char* ip = in + 3 * px;
+    unsigned char* lp = fr + (long)(2 * j + r) * Ws + (long)g * PX;
+    unsigned s[3 * PX / 4 + 1];
+    if (WIDE) {
+      const uint2* iw = reinterpret_cast<const uint2*>(ip);
+#pragma unroll
+      for (int q = 0; q < 3 * PX / 8; ++q) {
+        const uint2 w = iw[q];
+        s[2 * q] = w.x;
+        s[2 * q + 1] = w.y;
+      }
+    }
+    unsigned yo[PX / 4 + 1];
+#pragma unroll
+    for (int i = 0; i < PX / 4 + 1; ++i) yo[i] = 0u;
+#pragma unroll
+    for (int i = 0; i < PX; ++i) {
+      int c3[3];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        c3[c] = WIDE ? (int)((s[(3 * i + c) >> 2] >> (8 * ((3 * i + c) & 3))) & 255u) : (int)ip[3 * i + c];
+        sum[i >> 1][c] += c3[c];
+      }
+      const unsigned b = yuv_channel(m, 0, c3[0], c3[1], c3[2]);
+      if (WIDE) yo[i >> 2] |= b << (8 * (i & 3));
+      else lp[i] = (unsigned char)b;
+    }
+    if (WIDE) *reinterpret_cast<uint2*>(lp) = make_uint2(yo[0], yo[1 % (PX / 4 + 1)]);
+  }
+  unsigned char* cp = fr + (long)Hs * Ws + (long)j * Ws + (long)g * PX;
+  unsigned co[PX / 4 + 1];
+#pragma unroll
+  for (int i = 0; i < PX / 4 + 1; ++i) co[i] = 0u;
+#pragma unroll
+  for (int k = 0; k < NP; ++k) {
+    const int r_ = (sum[k][0] + 2) >> 2, g_ = (sum[k][1] + 2) >> 2, b_ = (sum[k][2] + 2) >> 2;
+    const unsigned u = yuv_channel(m, 1, r_, g_, b_), v = yuv_channel(m, 2, r_, g_, b_);
+    if (WIDE) {
+      co[k >> 1] |= (u | (v << 8)) << (16 * (k & 1));
+    } else {
+      cp[2 * k] = (unsigned char)u;
+      cp[2 * k + 1] = (unsigned char)v;
+    }
+  }
+  if (WIDE) *reinterpret_cast<uint2*>(cp) = make_uint2(co[0], co[1 % (PX / 4 + 1)]);
+}
+
+static bool yuv_overlap(const void* a, long abytes, const void* b, long bbytes) {
+  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+  return a0 < b0 + (uintptr_t)bbytes && b0 < a0 + (uintptr_t)abytes;
+}
+
+extern "C" int stswin_yuv_to_rgb(const unsigned char* in, const int* matrix, unsigned char* out, int n, int Hs, int Ws, int format,
+                                 int chroma, void* stream) {
+  if (n <= 0 || Hs <= 0 || Ws <= 0) return -1424;
+  if (in == nullptr || matrix == nullptr || out == nullptr) return -1425;
+  if (format < 0 || format > 1) return -1427;
+  if (chroma < 0 || chroma > 1) return -1428;
+  if ((Ws & 1) || (format == 0 && (Hs & 1))) return -1426;
+  const long px = (long)n * Hs * Ws;
+  const long in_bytes = format == 0 ? px / 2 * 3 : px * 2;
+  if (yuv_overlap(in, in_bytes, out, 3 * px) || yuv_overlap(matrix, 48, out, 3 * px)) return -1429;
+  const bool wide = Ws % YUV_PPT == 0 && (((uintptr_t)in & (format == 0 ? 7 : 15)) | ((uintptr_t)out & 7)) == 0;
+  const long threads = px / (format == 0 ? 2 : 1) / (wide ? YUV_PPT : 2);
+  const long blocks = (threads + 255) / 256;
+  if (blocks > 0x7fffffL) return -1424;                          // (every thread number fits 32 bits)
+  dim3 grid((unsigned)blocks);
+  hipStream_t st = (hipStream_t)stream;
+#define YUV_LAUNCH(FMT_, LIN_)                                                                                                 \
+  do {                                                                                                                         \
+    if (wide) hipLaunchKernelGGL((yuv_to_rgb_kernel<FMT_, LIN_, true>), grid, dim3(256), 0, st, in, matrix, out, (unsigned)threads, Hs, Ws); \
+    else hipLaunchKernelGGL((yuv_to_rgb_kernel<FMT_, LIN_, false>), grid, dim3(256), 0, st, in, matrix, out, (unsigned)threads, Hs, Ws);    \
+  } while (0)
+  if (format == 0) {
+    if (chroma) YUV_LAUNCH(0, true);
+    else YUV_LAUNCH(0, false);
+  } else {
+    if (chroma) YUV_LAUNCH(1, true);
+    else YUV_LAUNCH(1, false);
+  }
+#undef YUV_LAUNCH
+  STSWIN_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int stswin_rgb_to_nv12(const unsigned char* in, const int* matrix, unsigned char* out, int n, int Hs, int Ws, void* stream) {
+  if (n <= 0 || Hs <= 0 || Ws <= 0) return -1424;
+  if (in == nullptr || matrix == nullptr || out == nullptr) return -1425;
+  if ((Ws & 1) || (Hs & 1)) return -1426;
+  const long px = (long)n * Hs * Ws;
+  if (yuv_overlap(in, 3 * px, out, px / 2 * 3) || yuv_overlap(matrix, 48, out, px / 2 * 3)) return -1429;
+  const bool wide = Ws % YUV_PPT == 0 && (((uintptr_t)in | (uintptr_t)out) & 7) == 0;
+  const long threads = px / 2 / (wide ? YUV_PPT : 2);
+  const long blocks = (threads + 255) / 256;
+  if (blocks > 0x7fffffL) return -1424;
+  dim3 grid((unsigned)blocks);
+  hipStream_t st = (hipStream_t)stream;
+  if (wide) hipLaunchKernelGGL(rgb_to_nv12_kernel<true>, grid, dim3(256), 0, st, in, matrix, out, (unsigned)threads, Hs, Ws);
+  else hipLaunchKernelGGL(rgb_to_nv12_kernel<false>, grid, dim3(256), 0, st, in, matrix, out, (unsigned)threads, Hs, Ws);
+  STSWIN_CHECK_LAUNCH();
+  return 0;
+}
+
 
 // ----------------------------------------------------------------------------------------- statistics from a GEMM epilogue
 // A convolution GEMM launched with STSWIN_GF_CS_PARTIAL | STSWIN_GF_CS_SQ leaves per-128-row-block column sums and sums of

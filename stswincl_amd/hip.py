@@ -1432,6 +1432,73 @@ def gt_decode(src: torch.Tensor, table: torch.Tensor, out_dtype: torch.dtype = t
     return out
 
 
+YUV_NV12, YUV_UYVY = 0, 1                      # stswin_yuv_to_rgb's `format` (plain integers in the header's comment, not #defines)
+YUV_REPLICATE, YUV_LINEAR = 0, 1               # ... and its `chroma`
+_YUV_FORMATS = {"nv12": YUV_NV12, "uyvy": YUV_UYVY}
+_YUV_CHROMA = {"replicate": YUV_REPLICATE, "linear": YUV_LINEAR}
+
+
+def _yuv_matrix(matrix: torch.Tensor, device, what: str) -> None:
+    if (not isinstance(matrix, torch.Tensor) or matrix.dtype != torch.int32 or tuple(matrix.shape) != (3, 4) or not matrix.is_contiguous()
+            or matrix.device != device):
+        got = f"{matrix.dtype} {tuple(matrix.shape)} on {matrix.device}" if isinstance(matrix, torch.Tensor) else type(matrix).__name__
+        raise StswinHipError(f"{what}: matrix must be contiguous int32 [3][4] on {device} (utils.yuv), got {got}")
+
+
+def yuv_to_rgb(src: torch.Tensor, matrix: torch.Tensor, fmt: str = "nv12", chroma: str = "replicate",
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Raw video frames -> uint8 RGB [n][Hs][Ws][3]: fmt="nv12" src uint8 [n][3 Hs / 2][Ws] (luma rows, then rows of (U, V) pairs),
+    fmt="uyvy" src uint8 [n][Hs][Ws][2] (U, Y0, V, Y1 per pixel pair), Hs (nv12) and Ws even.  matrix int32 [3][4] on the device
+    (utils.yuv.to_rgb_matrix); chroma="replicate" | "linear" as utils.yuv.yuv_to_rgb defines them, which this equals byte for byte.
+    `out` must not share memory with src; returns out (include/stswin_hip.h, stswin_yuv_to_rgb)."""
+    if fmt not in _YUV_FORMATS:
+        raise StswinHipError(f"yuv_to_rgb: fmt must be one of {sorted(_YUV_FORMATS)}, got {fmt!r}")
+    if chroma not in _YUV_CHROMA:
+        raise StswinHipError(f"yuv_to_rgb: chroma must be one of {sorted(_YUV_CHROMA)}, got {chroma!r}")
+    if not isinstance(src, torch.Tensor) or src.dtype != torch.uint8 or not src.is_contiguous() or src.numel() == 0:
+        raise StswinHipError("yuv_to_rgb: src must be a contiguous, non-empty uint8 tensor")
+    if fmt == "nv12":
+        if src.dim() != 3 or src.shape[1] % 3 or src.shape[2] % 2:
+            raise StswinHipError(f"yuv_to_rgb: nv12 src must be uint8 [n][3 Hs / 2][Ws] with Hs and Ws even, got {tuple(src.shape)}")
+        n, Hs, Ws = src.shape[0], src.shape[1] // 3 * 2, src.shape[2]
+    else:
+        if src.dim() != 4 or src.shape[3] != 2 or src.shape[2] % 2:
+            raise StswinHipError(f"yuv_to_rgb: uyvy src must be uint8 [n][Hs][Ws][2] with Ws even, got {tuple(src.shape)}")
+        n, Hs, Ws = src.shape[:3]
+    _yuv_matrix(matrix, src.device, "yuv_to_rgb")
+    if out is None:
+        out = torch.empty(n, Hs, Ws, 3, dtype=torch.uint8, device=src.device)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (n, Hs, Ws, 3) or not out.is_contiguous() or out.device != src.device:
+        raise StswinHipError(f"yuv_to_rgb: out must be contiguous uint8 [{n}][{Hs}][{Ws}][3] on {src.device}, got {out.dtype} "
+                             f"{tuple(out.shape)} on {out.device}")
+    elif _same_memory(out, src) or _same_memory(out, matrix):
+        raise StswinHipError("yuv_to_rgb: out shares memory with src or matrix")
+    _check(load().stswin_yuv_to_rgb(_p(src), _p(matrix), _p(out), n, Hs, Ws, _YUV_FORMATS[fmt], _YUV_CHROMA[chroma], _stream()),
+           "yuv_to_rgb")
+    return out
+
+
+def rgb_to_nv12(src: torch.Tensor, matrix: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint8 RGB [n][Hs][Ws][3] (Hs, Ws even) -> NV12 uint8 [n][3 Hs / 2][Ws]: luma per pixel, chroma from the 2 x 2 block's mean, with
+    matrix int32 [3][4] on the device (utils.yuv.to_yuv_matrix); equals utils.yuv.rgb_to_nv12 byte for byte.  `out` must not share
+    memory with src; returns out (include/stswin_hip.h, stswin_rgb_to_nv12)."""
+    if (not isinstance(src, torch.Tensor) or src.dtype != torch.uint8 or src.dim() != 4 or src.shape[3] != 3 or not src.is_contiguous()
+            or src.numel() == 0 or src.shape[1] % 2 or src.shape[2] % 2):
+        got = f"{src.dtype} {tuple(src.shape)}" if isinstance(src, torch.Tensor) else type(src).__name__
+        raise StswinHipError(f"rgb_to_nv12: src must be contiguous, non-empty uint8 [n][Hs][Ws][3] with Hs and Ws even, got {got}")
+    n, Hs, Ws, _ = src.shape
+    _yuv_matrix(matrix, src.device, "rgb_to_nv12")
+    if out is None:
+        out = torch.empty(n, Hs // 2 * 3, Ws, dtype=torch.uint8, device=src.device)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (n, Hs // 2 * 3, Ws) or not out.is_contiguous() or out.device != src.device:
+        raise StswinHipError(f"rgb_to_nv12: out must be contiguous uint8 [{n}][{Hs // 2 * 3}][{Ws}] on {src.device}, got {out.dtype} "
+                             f"{tuple(out.shape)} on {out.device}")
+    elif _same_memory(out, src) or _same_memory(out, matrix):
+        raise StswinHipError("rgb_to_nv12: out shares memory with src or matrix")
+    _check(load().stswin_rgb_to_nv12(_p(src), _p(matrix), _p(out), n, Hs, Ws, _stream()), "rgb_to_nv12")
+    return out
+
+
 def _int_table(t: Optional[torch.Tensor], rows: int, what: str):
     if t is None:
         raise StswinHipError(f"frame_ingest: the {what} table is missing")

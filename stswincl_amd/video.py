@@ -43,6 +43,8 @@ from .hip import StswinHipError
 
 T = 4                   # frames per clip (the model asserts T == 4)
 RULES = ("endovis18", "cadis")
+PIXEL_FORMATS = ("rgb", "nv12", "uyvy")
+_FRAME_FORMS = {"rgb": "uint8 RGB [n][Hs][Ws][3]", "nv12": "uint8 NV12 [n][3 Hs / 2][Ws]", "uyvy": "uint8 UYVY [n][Hs][Ws][2]"}
 
 
 def _check_rule(rule: str) -> None:
@@ -287,7 +289,7 @@ class VideoSegmenter:
     seg = VideoSegmenter(model, batch=1, out="logits" | "labels" | "overlay", out_size=None, graph=False)
 
     push(frames, gt=None) takes uint8 RGB frames [n][Hs][Ws][3] (or one [Hs][Ws][3]; torch tensor on the model's GPU or the CPU, or
-    a numpy array) and returns [(frame_index, result), ...] for the frames whose clip is now complete.  finish() runs what is
+    a numpy array; NV12 or UYVY frames with pixel_format, below) and returns [(frame_index, result), ...] for the frames whose clip is now complete.  finish() runs what is
     left at the end of the sequence; reset() starts the next one (frame indices restart at 0).  segment_sequence(frames, gt=None)
     is reset + push + finish, results in frame order.  Frames are resized to the model's input size (H, W) = 8 x
     swin.input_resolution.
@@ -326,6 +328,18 @@ class VideoSegmenter:
     The bytes are uploaded as they are and decoded to the int64 index map on the device (hip.gt_decode) when they are pushed; scoring
     then proceeds as with an int64 gt.  unmatched() is the pooled number of colour-coded pixels that no table row holds.
 
+    pixel_format="nv12" | "uyvy" (yuv_standard="bt709" | "bt601", full_range=False, chroma="replicate" | "linear"): push takes the
+    frames as a decoder or a capture card delivers them, uint8 [n][3 Hs / 2][Ws] (NV12: Hs luma rows, then Hs / 2 rows of (U, V) pairs)
+    or uint8 [n][Hs][Ws][2] (UYVY: U, Y0, V, Y1 per pixel pair), one frame without [n], on the CPU or the GPU, Hs (NV12) and Ws even;
+    frame_shape stays (Hs, Ws).  The raw bytes are uploaded as they are (1.5 or 2 bytes per pixel) and one launch (hip.yuv_to_rgb,
+    defined to the bit by utils.yuv.yuv_to_rgb with utils.yuv.to_rgb_matrix(yuv_standard, full_range)) makes the RGB frame that
+    everything downstream reads, so the results are those of pushing utils.yuv.yuv_to_rgb(frames) as RGB.  A raw frame pushed as a GPU
+    tensor is read by that launch only: it is free again after its ResNet pass, for out="overlay" too (the segmenter keeps the RGB
+    frame it made).  Under graph=True the static input buffer holds the raw frame and the captured step begins with the conversion.
+    out_format="nv12" (out="overlay" only; any pixel_format; an odd frame size raises at the first push): the result is the overlay as
+    NV12, uint8 [3 Hs / 2][Ws] = utils.yuv.rgb_to_nv12 of the RGB overlay with utils.yuv.to_yuv_matrix(yuv_standard, full_range), made
+    by one more launch (hip.rgb_to_nv12), the last captured one under graph=True.
+
     scores="deferred" (endovis18): a scored frame's counts go into a device log instead of to the host - no download and no
     synchronisation per frame - and push returns the labels (logits, overlay) alone, as cadis does; under graph=True the counting
     launch runs after the replayed step.  endo_scores() downloads the log once and returns utils.EndoMetric.EndoScores: the per-frame
@@ -338,9 +352,20 @@ class VideoSegmenter:
     def __init__(self, model, batch: int = 1, out: str = "logits", out_size: Optional[Sequence[int]] = None, graph: bool = False,
                  protocol: str = "endovis18", metric_classes: Optional[int] = None, align_corners: Optional[bool] = None,
                  palette=None, alpha: int = 128, transparent: Optional[Sequence[int]] = None, edge_alpha: Optional[int] = 255,
-                 gt_table=None, scores: str = "frame"):
+                 gt_table=None, scores: str = "frame", pixel_format: str = "rgb", yuv_standard: str = "bt709", full_range: bool = False,
+                 chroma: str = "replicate", out_format: str = "rgb"):
         if out not in ("logits", "labels", "overlay"):
             raise StswinHipError(f"out must be 'logits', 'labels' or 'overlay', got {out!r}")
+        if pixel_format not in PIXEL_FORMATS:
+            raise StswinHipError(f"pixel_format must be one of {PIXEL_FORMATS}, got {pixel_format!r}")
+        if out_format not in ("rgb", "nv12"):
+            raise StswinHipError(f"out_format must be 'rgb' or 'nv12', got {out_format!r}")
+        if out_format == "nv12" and out != "overlay":
+            raise StswinHipError("out_format='nv12' belongs to out='overlay'")
+        if chroma not in ("replicate", "linear"):
+            raise StswinHipError(f"chroma must be 'replicate' or 'linear', got {chroma!r}")
+        if yuv_standard not in ("bt709", "bt601"):
+            raise StswinHipError(f"yuv_standard must be 'bt709' or 'bt601', got {yuv_standard!r}")
         if out != "overlay" and (palette is not None or transparent is not None):
             raise StswinHipError("palette and transparent belong to out='overlay'")
         if graph and batch != 1:
@@ -401,6 +426,14 @@ class VideoSegmenter:
                 raise StswinHipError(f"out='overlay': {e}") from e
             self._table = torch.from_numpy(table).to(self.device)       # persistent: a captured graph reads it
         self.edge_alpha = edge_alpha
+        self.pixel_format, self.chroma, self.out_format = pixel_format, chroma, out_format
+        self._to_rgb = self._to_yuv = None                               # persistent: a captured graph reads them
+        if pixel_format != "rgb" or out_format == "nv12":
+            from .utils import yuv
+            if pixel_format != "rgb":
+                self._to_rgb = torch.from_numpy(yuv.to_rgb_matrix(yuv_standard, bool(full_range))).to(self.device)
+            if out_format == "nv12":
+                self._to_yuv = torch.from_numpy(yuv.to_yuv_matrix(yuv_standard, bool(full_range))).to(self.device)
         self.graph = graph
         self.planner = ClipPlanner(batch, rule=protocol)
         self.frame_shape = None
@@ -416,7 +449,7 @@ class VideoSegmenter:
 
     def reset(self) -> None:
         self.planner.reset()
-        self._frames = {}                 # frame index -> (uint8 tensor [k][Hs][Ws][3], GPU or CPU, row) until its ResNet pass
+        self._frames = {}                 # frame index -> (uint8 tensor [k][Hs][Ws][3] (or raw nv12 / uyvy), GPU or CPU, row) until its ResNet pass
         self._kept = {}                   # out="overlay": frame index -> GPU uint8 [1][Hs][Ws][3] from its ResNet pass until its clip's result
         self._gt = {}
         if self._seq_logged:              # scores="deferred": the sequence that ends here has rows in the log
@@ -534,13 +567,24 @@ class VideoSegmenter:
     def _as_frames(self, frames) -> torch.Tensor:
         if isinstance(frames, np.ndarray):
             frames = torch.from_numpy(frames)
+        form = _FRAME_FORMS[self.pixel_format]
         if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8:
-            raise StswinHipError("frames must be uint8 RGB [n][Hs][Ws][3] (torch tensor or numpy array)")
-        if frames.dim() == 3:
+            raise StswinHipError(f"frames must be {form} (torch tensor or numpy array)")
+        dims = 3 if self.pixel_format == "nv12" else 4
+        if frames.dim() == dims - 1:
             frames = frames[None]
-        if frames.dim() != 4 or frames.shape[3] != 3:
-            raise StswinHipError(f"frames must be uint8 RGB [n][Hs][Ws][3], got {tuple(frames.shape)}")
-        shape = tuple(frames.shape[1:3])
+        if frames.dim() != dims or (dims == 4 and frames.shape[3] != (2 if self.pixel_format == "uyvy" else 3)):
+            raise StswinHipError(f"frames must be {form}, got {tuple(frames.shape)}")
+        if self.pixel_format == "nv12":
+            if frames.shape[1] % 3 or frames.shape[2] % 2:
+                raise StswinHipError(f"frames must be {form} with Hs and Ws even, got {tuple(frames.shape)}")
+            shape = (frames.shape[1] // 3 * 2, frames.shape[2])
+        else:
+            shape = tuple(frames.shape[1:3])
+            if shape[1] % 2 and self.pixel_format == "uyvy":
+                raise StswinHipError(f"frames must be {form} with Ws even, got {tuple(frames.shape)}")
+        if self.out_format == "nv12" and (shape[0] % 2 or shape[1] % 2):
+            raise StswinHipError(f"out_format='nv12' needs an even frame size, got {shape}")
         if self.frame_shape is None:
             if self.out == "overlay":
                 if self.out_size is None:
@@ -566,15 +610,22 @@ class VideoSegmenter:
             return dst.copy_(part)
         return self._pinned.upload(part.numpy(), dst)
 
+    def _static_image(self, raw: torch.Tensor, u8: torch.Tensor) -> torch.Tensor:
+        """The graph step's first launches: the static input buffer (raw pixel formats: converted into the static RGB buffer u8, which
+        the overlay blends onto) -> the fp32 image."""
+        if self._to_rgb is not None:
+            hip.yuv_to_rgb(raw, self._to_rgb, self.pixel_format, self.chroma, out=u8)
+        return ingest(u8, self.size, protocol=self.protocol)
+
     def _upload_table(self, values: List[int], dst: Optional[torch.Tensor] = None) -> torch.Tensor:
         if dst is None:
             dst = torch.empty(len(values), dtype=torch.int32, device=self.device)
         return self._pinned.upload(np.asarray(values, dtype=np.int32), dst)
 
     def _ingest_new(self, new: List[int]) -> torch.Tensor:
-        """The new frames' fp32 images [n][3][H][W]: one ingest launch per run of rows of one pushed tensor.  out="overlay" keeps the
-        device tensor that the ingest read, one view per frame, for the frame's own clip: the copy made of CPU frames, the pushed
-        tensor itself for GPU frames."""
+        """The new frames' fp32 images [n][3][H][W]: one ingest launch per run of rows of one pushed tensor (raw pixel formats: one
+        hip.yuv_to_rgb launch before it).  out="overlay" keeps the device RGB tensor that the ingest read, one view per frame, for the
+        frame's own clip: the copy made of CPU frames, the pushed tensor itself for GPU RGB frames, the converted frames for raw ones."""
         out = torch.empty(len(new), 3, *self.size, dtype=torch.float32, device=self.device)
         j = 0
         while j < len(new):
@@ -584,6 +635,8 @@ class VideoSegmenter:
                 self._frames.pop(new[j + k])
                 k += 1
             dev = self._put_frames(src, r0, k)
+            if self._to_rgb is not None:                     # raw frames: the RGB frames are made here, the raw bytes are done with
+                dev = hip.yuv_to_rgb(dev, self._to_rgb, self.pixel_format, self.chroma)
             ingest(dev, self.size, out[j:j + k], self.protocol)
             if self._table is not None:
                 for i in range(k):
@@ -621,10 +674,13 @@ class VideoSegmenter:
         return logits, None
 
     def _overlay(self, labels: torch.Tensor, frames) -> torch.Tensor:
-        """labels (B, *out_size) blended onto the clips' own frames: one launch per clip (the frames live in separate tensors)."""
+        """labels (B, *out_size) blended onto the clips' own frames: one launch per clip (the frames live in separate tensors);
+        out_format="nv12": one more launch turns the overlays (B, Hs, Ws, 3) into NV12 (B, 3 Hs / 2, Ws)."""
         out = torch.empty(*labels.shape, 3, dtype=torch.uint8, device=self.device)
         for b, fr in enumerate(frames):
             hip.labels_overlay(labels[b:b + 1], self._table, fr, self.edge_alpha, out[b:b + 1])
+        if self._to_yuv is not None:
+            return hip.rgb_to_nv12(out, self._to_yuv)
         return out
 
     def _labels(self, logits: torch.Tensor, gt: Optional[torch.Tensor] = None, want: bool = True) -> Optional[torch.Tensor]:
@@ -669,14 +725,16 @@ class VideoSegmenter:
             # first steady-state step (or first of the other output form): one eager warm-up on the static buffers (on a side stream,
             # as graph.py's GraphedStep does), then the capture; this step's result is the warm-up's
             u8 = torch.empty(1, *self.frame_shape, 3, dtype=torch.uint8, device=self.device)
+            # raw pixel formats: the static input buffer holds the raw frame, the step begins with its conversion into u8
+            raw = u8 if self._to_rgb is None else torch.empty(1, *src.shape[1:], dtype=torch.uint8, device=self.device)
             frames = [u8] if self._table is not None else None     # the steady step's clip is the new frame's: blend onto the static buffer
             table = torch.empty(T + 1, dtype=torch.int32, device=self.device)
-            self._put_frames(src, r, 1, u8)
+            self._put_frames(src, r, 1, raw)
             self._upload_table(st.table(), table)
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
-                logits, labels = self._compute(ingest(u8, self.size, protocol=self.protocol), table, 1, 1, want_labels, frames)
+                logits, labels = self._compute(self._static_image(raw, u8), table, 1, 1, want_labels, frames)
                 logits = logits.clone()
             torch.cuda.current_stream().wait_stream(side)
             torch.cuda.synchronize()
@@ -684,13 +742,13 @@ class VideoSegmenter:
             graph = torch.cuda.CUDAGraph()
             autocast = torch.is_autocast_enabled()
             with torch.cuda.graph(graph):
-                out, out_labels = self._compute(ingest(u8, self.size, protocol=self.protocol), table, 1, 1, want_labels, frames)
-            self._g = (graph, u8, table, out, out_labels, want_labels, autocast)
+                out, out_labels = self._compute(self._static_image(raw, u8), table, 1, 1, want_labels, frames)
+            self._g = (graph, raw, table, out, out_labels, want_labels, autocast, u8)
             return logits, labels, False, frames
-        graph, u8, table, out, out_labels, _, autocast = g
+        graph, raw, table, out, out_labels, _, autocast, u8 = g
         if torch.is_autocast_enabled() != autocast:
             raise StswinHipError("autocast differs from the state the step was captured under: make a new VideoSegmenter")
-        self._put_frames(src, r, 1, u8)
+        self._put_frames(src, r, 1, raw)
         self._upload_table(st.table(), table)
         graph.replay()
         return out, out_labels, True, [u8] if self._table is not None else None
