@@ -514,7 +514,16 @@ def stem_wgrad(dy, A, dw, frames, H, W, accumulate=False):
 
 
 def maxpool3x3s2(src, dst, arg, frames, H, W, Ho, Wo, backward=False):
+    """forward: src [F*H*W][C] -> dst [F*Ho*Wo][C] and the winning taps arg (uint8 [F*Ho*Wo][C]); backward: src = d(out), dst = d(in)."""
     C = src.shape[1]
+    _pair("maxpool3x3s2", src, dst)
+    if (Ho, Wo) != ((H - 1) // 2 + 1, (W - 1) // 2 + 1):
+        raise StswinHipError(f"maxpool3x3s2: ({Ho}, {Wo}) is not the 3x3 stride-2 pad-1 pool of ({H}, {W})")
+    _rows("maxpool3x3s2", src, frames * (Ho * Wo if backward else H * W), "src")
+    _rows("maxpool3x3s2", dst, frames * (H * W if backward else Ho * Wo), "dst")
+    if arg.dtype != torch.uint8 or arg.device != src.device or tuple(arg.shape) != (frames * Ho * Wo, C) or not arg.is_contiguous():
+        raise StswinHipError(f"maxpool3x3s2: arg must be a contiguous uint8 [{frames * Ho * Wo}][{C}] on {src.device}, got "
+                             f"{arg.dtype} {tuple(arg.shape)} on {arg.device}")
     _check(load().stswin_maxpool3x3s2(_dt(src), _p(src), _ld(src), _p(dst), _ld(dst), _p(arg), frames, H,
                                       W, Ho, Wo, C, 1 if backward else 0, _stream()), "maxpool3x3s2")
     return dst
@@ -1130,8 +1139,33 @@ def bn_relu_pool(x, mean, rstd, gamma, beta, frames, H, W, groups=1, unit=0):
     return out, arg
 
 
+def _pair(fn: str, src: torch.Tensor, dst: torch.Tensor) -> None:
+    """Source and destination of a token kernel: one dtype (the kernel is instantiated for ONE element type and reads both through
+    it), one device, one width.  Raises before anything is launched."""
+    if src.dtype != dst.dtype:
+        raise StswinHipError(f"{fn}: source is {src.dtype} but destination is {dst.dtype}")
+    if src.device != dst.device:
+        raise StswinHipError(f"{fn}: source on {src.device} but destination on {dst.device}")
+    if src.dim() != 2 or dst.dim() != 2 or src.shape[1] != dst.shape[1]:
+        raise StswinHipError(f"{fn}: source {tuple(src.shape)} and destination {tuple(dst.shape)} must be 2-D and equally wide")
+
+
+def _rows(fn: str, t: torch.Tensor, rows: int, what: str) -> None:
+    if t.shape[0] != rows:
+        raise StswinHipError(f"{fn}: {what} has {t.shape[0]} rows, the stated geometry needs {rows}")
+
+
 def rows_broadcast(v, out, groups, scale=1.0, accumulate=False, M=None):
+    """out[r] (+)= v[r // (M / groups)] * scale for the first M rows of out: v fp32 [groups][C], contiguous."""
     M = out.shape[0] if M is None else M
+    if v.dtype != torch.float32 or not v.is_contiguous():
+        raise StswinHipError(f"rows_broadcast: v must be a contiguous fp32 matrix, got {v.dtype}, strides {tuple(v.stride())}")
+    if v.device != out.device:
+        raise StswinHipError(f"rows_broadcast: v on {v.device} but out on {out.device}")
+    if v.dim() != 2 or out.dim() != 2 or v.shape[1] != out.shape[1]:
+        raise StswinHipError(f"rows_broadcast: v {tuple(v.shape)} and out {tuple(out.shape)} must be 2-D and equally wide")
+    if groups <= 0 or v.shape[0] != groups or M > out.shape[0] or M % groups:
+        raise StswinHipError(f"rows_broadcast: v has {v.shape[0]} rows for {groups} groups; M = {M} of out's {out.shape[0]} rows")
     _check(load().stswin_rows_broadcast(_dt(out), _p(v), _p(out), _ld(out), M, v.shape[1], groups,
                                         scale, 1 if accumulate else 0, _stream()), "rows_broadcast")
     return out
@@ -1140,12 +1174,25 @@ def rows_broadcast(v, out, groups, scale=1.0, accumulate=False, M=None):
 def bilinear(src, dst, frames, h, w, H, W, backward=False):
     """forward: src [F*h*w][C] -> dst [F*H*W][C]; backward: src = d(out) [F*H*W][C] -> dst = d(in) [F*h*w][C]."""
     C = dst.shape[1]
+    _pair("bilinear", src, dst)
+    _rows("bilinear", src, frames * (H * W if backward else h * w), "src")
+    _rows("bilinear", dst, frames * (h * w if backward else H * W), "dst")
     _check(load().stswin_bilinear(_dt(src), _p(src), _ld(src), _p(dst), _ld(dst), frames, h, w, H, W, C,
                                   1 if backward else 0, _stream()), "bilinear")
     return dst
 
 
 def logits_upsample(tokens, nchw, frames, h, w, H, W, nc, backward=False):
+    """forward: tokens [F*h*w][>= nc] -> nchw [F][nc][H][W]; backward: nchw = d(logits) -> columns < nc of tokens = d(tokens)."""
+    if tokens.dtype != nchw.dtype:
+        raise StswinHipError(f"logits_upsample: tokens are {tokens.dtype} but the NCHW tensor is {nchw.dtype}")
+    if tokens.device != nchw.device:
+        raise StswinHipError(f"logits_upsample: tokens on {tokens.device} but the NCHW tensor on {nchw.device}")
+    if tokens.dim() != 2 or tokens.shape[1] < nc or nc <= 0:
+        raise StswinHipError(f"logits_upsample: tokens {tuple(tokens.shape)} cannot hold {nc} classes")
+    _rows("logits_upsample", tokens, frames * h * w, "tokens")
+    if nchw.numel() != frames * nc * H * W or not nchw.is_contiguous():
+        raise StswinHipError(f"logits_upsample: the NCHW tensor {tuple(nchw.shape)} is not a contiguous [{frames}][{nc}][{H}][{W}]")
     _check(load().stswin_logits_upsample(_dt(tokens), _p(tokens), _ld(tokens), _p(nchw), frames, h, w, H, W, nc,
                                          1 if backward else 0, _stream()), "logits_upsample")
 

@@ -1,5 +1,10 @@
 """Decode-head kernels (conv as gather GEMM, grouped BatchNorm, bilinear, pooling, logits upsample, OHEM-CE) and the
-ASPP module: HIP vs torch fp32 on the CPU / the reference golden.  fp32 path 1e-3 (typically 1e-5), bf16 path 3e-2."""
+ASPP module: HIP vs torch fp32 on the CPU / the reference golden.  fp32 path 1e-3 (typically 1e-5), bf16 path 3e-2.
+
+These are tests of the autograd wrappers under autocast, one relative L2 norm per tensor.  The element-wise contract of the
+kernels behind them lives elsewhere: bilinear, logits_upsample, rows_broadcast, the pooled sums and the stand-alone max pool in
+tests/test_hip_resample_contract.py (float64 reference tests/resample_ref.py: borders, backward windows, pad columns, column slices,
+first-maximum taps), BatchNorm in tests/test_hip_bn_contract.py, OHEM-CE in tests/test_hip_ohem_contract.py."""
 import pytest
 import torch
 import torch.nn as nn
