@@ -581,6 +581,20 @@ int stswin_labels_overlay(const unsigned char* labels, const unsigned char* fram
  * not 1 or 8; -1423 out overlaps in. */
 int stswin_gt_decode(const unsigned char* in, const unsigned char* table, void* out, int* unmatched, int n, int H, int W, int ch,
                      int ncolours, int out_bytes, void* stream);
+/* ---- per-frame instrument report (stswincl_amd/utils/instruments.py, VideoSegmenter(report=...)): labels uint8 [n][H][W], out int64
+ * [n][nc][10].  Row out[f][c][0..9], taken over the pixels (y, x) of frame f whose label equals c:
+ *     0: count      1, 2: sum x, sum y      3, 4, 5: sum x^2, sum xy, sum y^2
+ *     6, 7: max(W - x), max(H - y)          8, 9: max(x + 1), max(y + 1)
+ * The extent is four maxima so that an all-zero row means "class absent"; the half-open box of a present class is
+ * [W - out[6], out[8]) x [H - out[7], out[9]).  Pixels with label >= nc are counted nowhere.  out is accumulated, never cleared (sums
+ * add, extents take the maximum): the caller zeroes it, and may pool several calls in one buffer.  1 <= nc <= 64 and 1 <= H, W <=
+ * 16384, so every sum fits an int64 (sum x^2 <= 2^28 2^28).  Integer atomics only (exact, independent of order: bit-reproducible).
+ * One launch, no scratch buffer, no synchronisation (graph-capturable).  Any pointer alignment, any W: labels 16-byte aligned with
+ * W % 16 == 0 takes the body with 16 pixels of one row per thread from one 16-byte load, anything else the byte body.
+ * Errors: -1545 n, H or W <= 0, or H or W > 16384 (or more workgroups than a grid holds); -1546 labels or out NULL; -1547 nc outside
+ * 1 .. 64.  (-1544 is stswin_pair_loss's.) */
+int stswin_label_moments(const unsigned char* labels /*[n][H][W]*/, long long* out /*[n][nc][10]*/, int n, int H, int W, int nc,
+                         void* stream);
 /* ---- frames as a video source delivers them (stswincl_amd/utils/yuv.py, VideoSegmenter(pixel_format=..., out_format="nv12")):
  * stswin_yuv_to_rgb makes the HWC RGB frame uint8 [n][Hs][Ws][3] that stswin_frame_ingest and stswin_labels_overlay read,
  * stswin_rgb_to_nv12 turns such a frame into NV12.  Hs (NV12) and Ws are even.

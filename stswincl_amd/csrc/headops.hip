@@ -1435,6 +1435,203 @@ extern "C" int stswin_gt_decode(const unsigned char* in, const unsigned char* ta
   return 0;
 }
 
+// Per-frame, per-class moments of a label map (stswincl_amd/utils/instruments.py states the row; VideoSegmenter(report=...)): count,
+// sum x, sum y, sum x^2, sum xy, sum y^2 and the extent as four maxima, over the pixels of each label < nc.  One pass over 1 byte per
+// pixel.  A thread takes ONE chunk of up to 16 pixels of one row (the wide body: one 16-byte load, which needs labels 16-byte aligned
+// and W % 16 == 0 so that every row of every frame starts on the grid; otherwise 16 byte loads and the row's last chunk is short); a
+// workgroup of LM_THREADS = 512 threads takes 512 consecutive chunks (8 KB) of ONE frame, a wave 64 consecutive ones.
+//   * A full chunk of one label (label maps are long runs: nearly every chunk) is the six small numbers 1, cx, dy, cx^2, cx dy, dy^2
+//     with cx = x0 / 16 its chunk column and dy its row less the row of the wave's first chunk.  Per distinct label among the wave's
+//     such chunks these are summed across the wave in 32 bits (six DPP steps per number, no LDS traffic), the extent comes from the
+//     first and last lane (rows) and two more DPP maxima (columns), and lane 63 alone expands the sums to the ten terms in 64 bits -
+//     sum_{i<16} (16 cx + i) = 256 cx + 120, sum (16 cx + i)^2 = 4096 cx^2 + 3840 cx + 1240 - and adds them to the workgroup's LDS table.
+//   * A chunk with several runs, or a short one, adds run by run: a run [first, last] of row y is n, n (first + last) / 2,
+//     n first^2 + 2 first T1 + T2 with T1, T2 the sums of i and i^2 below n, and y n, y sum x, y^2 n.
+// At the end the workgroup adds its non-zero LDS entries to out[f] with 64-bit global atomics: integer adds and maxima only, so the
+// result is exact and does not depend on the order.  The workgroup size is measured, not derived ("Instrument report"): on a
+// cold map the launch costs 1.3 us per 4 KB that ONE workgroup reads, whatever the code does with them, and 16 ns per workgroup of the
+// frame, because all of them queue up on the background's ten entries of out; 8 KB per workgroup is where the two meet at 1024 x 1280.
+#define LM_THREADS 512
+
+struct LmTerms {
+  unsigned n, sx, sy;                  // < 2^32 for one run and for a wave's 64 chunks (64 * 16 * 16383)
+  unsigned long long sxx, sxy, syy;
+  unsigned e0, e1, e2, e3;             // W - first, H - y, last + 1, y + 1
+};
+
+__device__ __forceinline__ LmTerms lm_run(unsigned first, unsigned n, unsigned y, unsigned H, unsigned W) {
+  LmTerms t;
+  const unsigned last = first + n - 1;
+  const unsigned t1 = n * (n - 1) / 2, t2 = (n - 1) * n * (2 * n - 1) / 6;
+  t.n = n;
+  t.sx = n * (first + last) / 2;
+  t.sy = y * n;
+  t.sxx = (unsigned long long)(first * first) * n + (unsigned long long)(2 * first * t1 + t2);
+  t.sxy = (unsigned long long)y * t.sx;
+  t.syy = (unsigned long long)(y * y) * n;
+  t.e0 = W - first;
+  t.e1 = H - y;
+  t.e2 = last + 1;
+  t.e3 = y + 1;
+  return t;
+}
+
+__device__ __forceinline__ void lm_flush(unsigned long long* sums, unsigned* ext, unsigned l, const LmTerms& t) {
+  unsigned long long* s = sums + 6 * l;
+  atomicAdd(s + 0, (unsigned long long)t.n);
+  atomicAdd(s + 1, (unsigned long long)t.sx);
+  atomicAdd(s + 2, (unsigned long long)t.sy);
+  atomicAdd(s + 3, t.sxx);
+  atomicAdd(s + 4, t.sxy);
+  atomicAdd(s + 5, t.syy);
+  unsigned* e = ext + 4 * l;
+  atomicMax(e + 0, t.e0);
+  atomicMax(e + 1, t.e1);
+  atomicMax(e + 2, t.e2);
+  atomicMax(e + 3, t.e3);
+}
+
+__device__ __forceinline__ unsigned lm_byte(const uint4& v, int i) {          // (i is a constant or selects by compares: no indexing)
+  return ((i < 4 ? v.x : i < 8 ? v.y : i < 12 ? v.z : v.w) >> (8 * (i & 3))) & 255u;
+}
+
+// The wave's sum / maximum of an unsigned value, valid in lane 63; every lane of the wave must be active.  quad_perm [1,0,3,2] and
+// [2,3,0,1], row_shr 4 and 8 leave a row's total in its lane 15; row_bcast 15 into rows 1 and 3, row_bcast 31 into rows 2 and 3 carry
+// the totals on.  A lane without a source reads 0, the identity of both operations.
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ unsigned lm_dpp(unsigned v) {
+  return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xf, false);
+}
+
+template <bool MAX>
+__device__ __forceinline__ unsigned lm_wave(unsigned v) {
+#define LM_STEP(CTRL, ROWS)                          \
+  {                                                  \
+    const unsigned o = lm_dpp<CTRL, ROWS>(v);        \
+    v = MAX ? max(v, o) : v + o;                     \
+  }
+  LM_STEP(0xb1, 0xf)
+  LM_STEP(0x4e, 0xf)
+  LM_STEP(0x114, 0xf)
+  LM_STEP(0x118, 0xf)
+  LM_STEP(0x142, 0xa)
+  LM_STEP(0x143, 0xc)
+#undef LM_STEP
+  return v;
+}
+
+template <bool WIDE>
+__global__ __launch_bounds__(LM_THREADS) void label_moments_kernel(const unsigned char* __restrict__ labels, unsigned long long* out, int H,
+                                                                   int W, int nc, int cpr, int blocks_per_frame) {
+  __shared__ unsigned long long sums[64 * 6];
+  __shared__ unsigned ext[64 * 4];
+  for (int i = threadIdx.x; i < 6 * nc; i += LM_THREADS) sums[i] = 0ull;
+  for (int i = threadIdx.x; i < 4 * nc; i += LM_THREADS) ext[i] = 0u;
+  __syncthreads();
+  const int f = (int)(blockIdx.x / (unsigned)blocks_per_frame);
+  const int q = (int)(blockIdx.x % (unsigned)blocks_per_frame) * LM_THREADS + (int)threadIdx.x;      // < 2^24 + 2^10 chunks of the frame
+  const int row = q / cpr, col = q - row * cpr;
+  const bool valid = row < H;                                  // (the chunk exists; the wave's lanes with a chunk are a prefix)
+  const int len = valid ? min(16, W - 16 * col) : 0;
+  uint4 v = make_uint4(0u, 0u, 0u, 0u);
+  if (valid) {
+    const unsigned char* p = labels + ((long)f * H + row) * W + 16 * col;
+    if (WIDE) {
+      v = *reinterpret_cast<const uint4*>(p);
+    } else {
+      unsigned w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+      for (int i = 0; i < 16; ++i)
+        if (i < len) w[i >> 2] |= (unsigned)p[i] << (8 * (i & 3));
+      v = make_uint4(w[0], w[1], w[2], w[3]);
+    }
+  }
+  const unsigned l0 = v.x & 255u, splat = l0 * 0x01010101u;
+  const bool full = len == 16 && v.x == splat && v.y == splat && v.z == splat && v.w == splat;       // the usual chunk: one label
+  if (valid && !full) {
+    unsigned change = 0;               // bit i: pixel i starts a run (i >= 1)
+#pragma unroll
+    for (int i = 1; i < 16; ++i)
+      if (lm_byte(v, i) != lm_byte(v, i - 1)) change |= 1u << i;
+    change &= (1u << len) - 1u;
+    int a = 0;
+    while (a < len) {
+      const unsigned rest = change >> (a + 1);
+      const int e = rest ? a + 1 + __builtin_ctz(rest) : len;
+      const unsigned l = lm_byte(v, a);
+      if (l < (unsigned)nc) lm_flush(sums, ext, l, lm_run((unsigned)(16 * col + a), (unsigned)(e - a), (unsigned)row, (unsigned)H, (unsigned)W));
+      a = e;
+    }
+  }
+  // the full chunks, label by label (wave-uniform from here: every lane takes part in the sums)
+  const unsigned row_w = (unsigned)__builtin_amdgcn_readfirstlane(row);       // lane 0's row: the smallest of the wave
+  const unsigned cx = (unsigned)col, dy = (unsigned)row - row_w;              // dy <= 64 / cpr + 1
+  unsigned long long todo = __ballot(full && l0 < (unsigned)nc);
+  while (todo) {
+    const int first = __ffsll((long long)todo) - 1;
+    const unsigned L = (unsigned)__builtin_amdgcn_readlane((int)l0, first);
+    const bool mine = full && l0 == L;
+    const unsigned long long m = __ballot(mine);
+    todo &= ~m;
+    const int last = 63 - __clzll((long long)m);
+    const unsigned mcx = mine ? cx : 0u, mdy = mine ? dy : 0u;
+    // <= 64 lanes of cx < 1024, dy <= 65: every sum stays far below 2^32; the count and sum dy share a word (64 < 2^8)
+    const unsigned c_sdy = lm_wave<false>((mine ? 1u : 0u) | (mdy << 8));
+    const unsigned scx = lm_wave<false>(mcx), scx2 = lm_wave<false>(mcx * mcx), scxdy = lm_wave<false>(mcx * mdy);
+    const unsigned sdy2 = lm_wave<false>(mdy * mdy);
+    const unsigned cx_max = lm_wave<true>(mcx), cx_min = 1023u - lm_wave<true>(mine ? 1023u - cx : 0u);
+    const unsigned dy_min = (unsigned)__builtin_amdgcn_readlane((int)dy, first), dy_max = (unsigned)__builtin_amdgcn_readlane((int)dy, last);
+    if ((threadIdx.x & 63) == 63) {
+      const unsigned c = c_sdy & 255u, sdy = c_sdy >> 8;
+      const unsigned sy = c * row_w + sdy;                                                      // sum of the chunks' rows
+      const unsigned long long scxy = (unsigned long long)row_w * scx + scxdy;
+      const unsigned long long sy2 = (unsigned long long)c * (row_w * row_w) + (unsigned long long)(2u * row_w * sdy + sdy2);
+      LmTerms t;
+      t.n = 16u * c;
+      t.sx = 256u * scx + 120u * c;
+      t.sy = 16u * sy;
+      t.sxx = 4096ull * scx2 + (unsigned long long)(3840u * scx + 1240u * c);
+      t.sxy = 256ull * scxy + 120ull * sy;
+      t.syy = 16ull * sy2;
+      t.e0 = (unsigned)W - 16u * cx_min;
+      t.e1 = (unsigned)H - (row_w + dy_min);
+      t.e2 = 16u * cx_max + 16u;
+      t.e3 = row_w + dy_max + 1u;
+      lm_flush(sums, ext, L, t);
+    }
+  }
+  __syncthreads();
+  unsigned long long* o = out + (long)f * nc * 10;
+  for (int i = threadIdx.x; i < 10 * nc; i += LM_THREADS) {
+    const int c = i / 10, k = i - 10 * c;
+    if (k < 6) {
+      const unsigned long long s = sums[6 * c + k];
+      if (s) atomicAdd(o + i, s);
+    } else {
+      const unsigned e = ext[4 * c + k - 6];
+      if (e) atomicMax(o + i, (unsigned long long)e);
+    }
+  }
+}
+
+extern "C" int stswin_label_moments(const unsigned char* labels, long long* out, int n, int H, int W, int nc, void* stream) {
+  if (n <= 0 || H <= 0 || W <= 0 || H > 16384 || W > 16384) return -1545;
+  if (labels == nullptr || out == nullptr) return -1546;
+  if (nc < 1 || nc > 64) return -1547;
+  const bool wide = ((uintptr_t)labels & 15) == 0 && W % 16 == 0;
+  const int cpr = (W + 15) / 16;
+  const long chunks = (long)H * cpr;
+  const long bpf = (chunks + LM_THREADS - 1) / LM_THREADS;
+  if (bpf * n > 0x7fffffffL) return -1545;
+  dim3 grid((unsigned)(bpf * n));
+  hipStream_t st = (hipStream_t)stream;
+  unsigned long long* o = reinterpret_cast<unsigned long long*>(out);
+  if (wide) hipLaunchKernelGGL(label_moments_kernel<true>, grid, dim3(LM_THREADS), 0, st, labels, o, H, W, nc, cpr, (int)bpf);
+  else hipLaunchKernelGGL(label_moments_kernel<false>, grid, dim3(LM_THREADS), 0, st, labels, o, H, W, nc, cpr, (int)bpf);
+  STSWIN_CHECK_LAUNCH();
+  return 0;
+}
+
 // Frames as a video source delivers them (stswincl_amd/utils/yuv.py states the arithmetic): NV12 or UYVY -> the HWC RGB frame that
 // stswin_frame_ingest and stswin_labels_overlay read, and RGB -> NV12.  matrix int32 [3][4]: out_c = clamp((m[c][0] t0 + m[c][1] t1 +
 // m[c][2] t2 + m[c][3]) >> 14, 0, 255) in int32 (|sum| < 2^25).  A thread owns YUV_PPT = 8 (wide body) or 2 (byte body) consecutive

@@ -1479,6 +1479,34 @@ def gt_decode(src: torch.Tensor, table: torch.Tensor, out_dtype: torch.dtype = t
     return out
 
 
+def label_moments(labels: torch.Tensor, nc: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint8 labels [n][H][W] -> int64 [n][nc][10], per frame and class c < nc over the pixels (y, x) with that label: count, sum x,
+    sum y, sum x^2, sum xy, sum y^2, max(W - x), max(H - y), max(x + 1), max(y + 1) (utils.instruments.label_moments is the numpy
+    definition; an all-zero row is an absent class, labels >= nc are counted nowhere).  Without `out` the result starts from zeros; a
+    given `out` is accumulated into (sums add, extents take the maximum) and must not share memory with labels; returns out
+    (include/stswin_hip.h, stswin_label_moments)."""
+    if not isinstance(labels, torch.Tensor) or labels.dtype != torch.uint8 or labels.dim() != 3 or not labels.is_contiguous():
+        got = f"{labels.dtype} {tuple(labels.shape)}" if isinstance(labels, torch.Tensor) else type(labels).__name__
+        raise StswinHipError(f"label_moments: labels must be contiguous uint8 [n][H][W], got {got}")
+    n, H, W = labels.shape
+    if n <= 0 or H <= 0 or W <= 0:
+        raise StswinHipError(f"label_moments: empty labels {tuple(labels.shape)}")
+    if H > 16384 or W > 16384:
+        raise StswinHipError(f"label_moments: a {H} x {W} map, the kernel takes up to 16384 x 16384")
+    if not isinstance(nc, int) or not 1 <= nc <= 64:
+        raise StswinHipError(f"label_moments: {nc!r} classes, the kernel takes 1 .. 64")
+    if out is None:
+        out = torch.zeros(n, nc, 10, dtype=torch.int64, device=labels.device)
+    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.int64 or tuple(out.shape) != (n, nc, 10) or not out.is_contiguous()
+          or out.device != labels.device):
+        got = f"{out.dtype} {tuple(out.shape)} on {out.device}" if isinstance(out, torch.Tensor) else type(out).__name__
+        raise StswinHipError(f"label_moments: out must be contiguous int64 [{n}][{nc}][10] on {labels.device}, got {got}")
+    elif _same_memory(out, labels):
+        raise StswinHipError("label_moments: out shares memory with labels")
+    _check(load().stswin_label_moments(_p(labels), _p(out), n, H, W, nc, _stream()), "label_moments")
+    return out
+
+
 YUV_NV12, YUV_UYVY = 0, 1                      # stswin_yuv_to_rgb's `format` (plain integers in the header's comment, not #defines)
 YUV_REPLICATE, YUV_LINEAR = 0, 1               # ... and its `chroma`
 _YUV_FORMATS = {"nv12": YUV_NV12, "uyvy": YUV_UYVY}

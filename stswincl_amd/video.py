@@ -286,7 +286,7 @@ class _Pinned:
 class VideoSegmenter:
     """Segment video sequences with an eval-mode TswinPlus, one result per frame, each frame's ResNet features computed once.
 
-    seg = VideoSegmenter(model, batch=1, out="logits" | "labels" | "overlay", out_size=None, graph=False)
+    seg = VideoSegmenter(model, batch=1, out="logits" | "labels" | "overlay", out_size=None, graph=False, report=None)
 
     push(frames, gt=None) takes uint8 RGB frames [n][Hs][Ws][3] (or one [Hs][Ws][3]; torch tensor on the model's GPU or the CPU, or
     a numpy array; NV12 or UYVY frames with pixel_format, below) and returns [(frame_index, result), ...] for the frames whose clip is now complete.  finish() runs what is
@@ -346,6 +346,19 @@ class VideoSegmenter:
     lists that scores="frame" (the default) returns, and the reference's val_map aggregates, per sequence too: a sequence's ordinal
     is the number of earlier sequences that scored a frame since reset_metrics(), which clears the log.
 
+    report="frame" | "deferred" (out="labels" | "overlay", both protocols; min_area=1): wherever a step's label map is made - the scoring
+    launches with ground truth included - one more launch (hip.label_moments, before the overlay launch: it reads the labels) takes
+    each frame's per-class moments, int64 [nc][10] with nc the model's classes: count, sum x, sum y, sum x^2, sum xy, sum y^2 and the
+    extent (utils.instruments states the row).  report="frame": a result r becomes (r, moments), a tuple r + (moments,), the moments on
+    the device - no download and no synchronisation (utils.instruments.InstrumentReport.from_moments(moments.cpu(), out_size) reads
+    them).  Under graph=True the captured step holds the clearing of the moments buffer (a fill kernel) and the moments launch behind
+    the label launch, and the moments of the last replayed step of a push are a view of that buffer, as the labels are; with ground
+    truth the labels, and so the moments, are made after the replay.  report="deferred": results are unchanged and the rows go into a
+    device log (copied from the graph's buffer after a replay); instrument_report() downloads the log once and returns the
+    InstrumentReport - presence, area, box, centroid, principal axis per frame and class, classes below min_area pixels absent - over
+    every frame released since reset_metrics(), rows ordered by sequence and frame, a sequence's ordinal being the number of earlier
+    sequences that released a frame.  Class names are the caller's (instrument_report(names=...)).
+
     Runs under torch.no_grad().  Refuses (StswinHipError): a model in train mode, a model or frames not on the GPU, a frame size
     that differs from the earlier frames'."""
 
@@ -353,7 +366,7 @@ class VideoSegmenter:
                  protocol: str = "endovis18", metric_classes: Optional[int] = None, align_corners: Optional[bool] = None,
                  palette=None, alpha: int = 128, transparent: Optional[Sequence[int]] = None, edge_alpha: Optional[int] = 255,
                  gt_table=None, scores: str = "frame", pixel_format: str = "rgb", yuv_standard: str = "bt709", full_range: bool = False,
-                 chroma: str = "replicate", out_format: str = "rgb"):
+                 chroma: str = "replicate", out_format: str = "rgb", report: Optional[str] = None, min_area: int = 1):
         if out not in ("logits", "labels", "overlay"):
             raise StswinHipError(f"out must be 'logits', 'labels' or 'overlay', got {out!r}")
         if pixel_format not in PIXEL_FORMATS:
@@ -377,6 +390,12 @@ class VideoSegmenter:
             raise StswinHipError(f"scores must be 'frame' or 'deferred', got {scores!r}")
         if scores == "deferred" and protocol != "endovis18":
             raise StswinHipError("scores='deferred' belongs to protocol='endovis18' (protocol='cadis' pools its counts in confusion_matrix())")
+        if report not in (None, "frame", "deferred"):
+            raise StswinHipError(f"report must be None, 'frame' or 'deferred', got {report!r}")
+        if report is not None and out == "logits":
+            raise StswinHipError("report belongs to out='labels' and out='overlay' (the moments are taken over the label map)")
+        if isinstance(min_area, bool) or not isinstance(min_area, int) or min_area < 1:
+            raise StswinHipError(f"min_area must be an int >= 1, got {min_area!r}")
         self.model = model
         self._check_train()
         if any(not p.is_cuda for p in model.parameters()):
@@ -404,6 +423,14 @@ class VideoSegmenter:
         self._log_rows = []               # ... and per row (sequence ordinal, frame index) on the host
         self._seq = 0
         self._seq_logged = False
+        self.report, self.min_area = report, min_area
+        self._classes = model.classifier[-1].out_channels
+        if report is not None and not 1 <= self._classes <= 64:
+            raise StswinHipError(f"report: the model has {self._classes} classes, hip.label_moments takes 1 .. 64")
+        self._rlog = None                 # report="deferred": int64 [capacity][nc][10] on the device, one row per released frame ...
+        self._rlog_rows = []              # ... and per row (sequence ordinal, frame index) on the host
+        self._rseq = 0
+        self._rseq_logged = False
         self._gt_table = None
         self._unmatched = None
         if gt_table is not None:
@@ -455,15 +482,22 @@ class VideoSegmenter:
         if self._seq_logged:              # scores="deferred": the sequence that ends here has rows in the log
             self._seq += 1
             self._seq_logged = False
+        if self._rseq_logged:             # report="deferred": likewise, with its own ordinal
+            self._rseq += 1
+            self._rseq_logged = False
 
     def reset_metrics(self) -> None:
         """Clear what an evaluation pools and reset() keeps: the confusion matrix (protocol="cadis"), the score log and its sequence
-        ordinal (scores="deferred"), the count of unmatched ground-truth pixels (gt_table)."""
+        ordinal (scores="deferred"), the instrument log and its ordinal (report="deferred"), the count of unmatched ground-truth
+        pixels (gt_table)."""
         if self._cm is not None:
             self._cm.zero_()
         self._log_rows = []
         self._seq = 0
         self._seq_logged = False
+        self._rlog_rows = []
+        self._rseq = 0
+        self._rseq_logged = False
         if self._unmatched is not None:
             self._unmatched.zero_()
 
@@ -501,6 +535,46 @@ class VideoSegmenter:
         self._log[n:n + 1].copy_(counts)
         self._log_rows.append((self._seq, frame))
         self._seq_logged = True
+
+    def instrument_report(self, names: Optional[Sequence[str]] = None):
+        """report="deferred": one download of the instrument log -> utils.instruments.InstrumentReport (min_area as given to the
+        segmenter) over every frame released since reset_metrics(), rows ordered by sequence and frame (.sequences[r], .frames[r]).
+        names: the caller's class names, for as_rows()."""
+        if self.report != "deferred":
+            raise StswinHipError("instrument_report() belongs to report='deferred'")
+        from .utils.instruments import InstrumentReport
+        n = len(self._rlog_rows)
+        mom = self._rlog[:n].cpu().numpy() if n else np.zeros((0, self._classes, 10), dtype=np.int64)
+        order = sorted(range(n), key=lambda r: self._rlog_rows[r])     # the log is in release order
+        rows = [self._rlog_rows[r] for r in order]
+        try:
+            return InstrumentReport.from_moments(mom[order], self.out_size or (0, 0), self.min_area, names, [f for _, f in rows],
+                                                 [s for s, _ in rows])
+        except ValueError as e:
+            raise StswinHipError(f"instrument_report: {e}") from e
+
+    def _moments(self, labels: torch.Tensor) -> Optional[torch.Tensor]:
+        """report: the moments int64 [B][nc][10] of a step's labels [B][*out_size], one launch behind the clearing of its buffer (a
+        fill kernel, also when captured: no memset node); None without report."""
+        if self.report is None:
+            return None
+        return hip.label_moments(labels, self._classes)
+
+    def _reported(self, frame: int, result, moments: Optional[torch.Tensor]):
+        """A frame's result with its moments [1][nc][10]: report="frame" appends them (on the device), "deferred" logs them."""
+        if self.report == "frame":
+            return result + (moments[0],) if isinstance(result, tuple) else (result, moments[0])
+        if self.report == "deferred":
+            n = len(self._rlog_rows)
+            if self._rlog is None or n == self._rlog.shape[0]:      # (a device copy; the log doubles when full)
+                grown = torch.zeros(max(64, 2 * n), *moments.shape[1:], dtype=torch.int64, device=self.device)
+                if n:
+                    grown[:n].copy_(self._rlog)
+                self._rlog = grown
+            self._rlog[n:n + 1].copy_(moments)
+            self._rlog_rows.append((self._rseq, frame))
+            self._rseq_logged = True
+        return result
 
     def confusion_matrix(self) -> np.ndarray:
         """protocol="cadis": the pooled confusion matrix, float64 [metric_classes][metric_classes], rows gt, columns prediction."""
@@ -645,8 +719,9 @@ class VideoSegmenter:
         return out
 
     def _compute(self, img: Optional[torch.Tensor], table: torch.Tensor, B: int, n_new: int, labels: bool = False, frames=None):
-        """ResNet on the new frames' images, clip assembly, Swin / ASPP / head: -> logits (B, nc, H, W) (and with labels = True the
-        labels (B, *out_size), or for out="overlay" the overlay (B, *out_size, 3) on `frames`, one uint8 [1][Hs][Ws][3] per clip).
+        """ResNet on the new frames' images, clip assembly, Swin / ASPP / head: -> logits (B, nc, H, W), and with labels = True the
+        labels (B, *out_size), or for out="overlay" the overlay (B, *out_size, 3) on `frames`, one uint8 [1][Hs][Ws][3] per clip, and
+        with report the labels' moments (B, nc, 10), taken before the overlay launch.
         Every launch on the current stream, no host synchronisation (graph-capturable)."""
         m = self.model
         hip.arena_reset(self.device)
@@ -670,8 +745,9 @@ class VideoSegmenter:
         logits = m.forward_frame_tokens(clips, h, w, self.size[0], self.size[1])
         if labels:
             lab = self._labels(logits)
-            return logits, lab if self._table is None else self._overlay(lab, frames)
-        return logits, None
+            mom = self._moments(lab)
+            return logits, lab if self._table is None else self._overlay(lab, frames), mom
+        return logits, None, None
 
     def _overlay(self, labels: torch.Tensor, frames) -> torch.Tensor:
         """labels (B, *out_size) blended onto the clips' own frames: one launch per clip (the frames live in separate tensors);
@@ -710,13 +786,13 @@ class VideoSegmenter:
         B, n_new = len(st.clips), len(st.new)
         want_labels = self.out != "logits" and not any(g in self._gt for g in st.clips)
         if self.graph and self._steady(st):
-            logits, labels, replayed, frames = self._run_graph(st, want_labels)
+            logits, labels, moments, replayed, frames = self._run_graph(st, want_labels)
         else:
             img = self._ingest_new(st.new) if n_new else None
             frames = [self._kept.pop(g) for g in st.clips] if self._table is not None else None
-            logits, labels = self._compute(img, self._upload_table(st.table()), B, n_new, want_labels, frames)
+            logits, labels, moments = self._compute(img, self._upload_table(st.table()), B, n_new, want_labels, frames)
             replayed = False
-        return self._results(st.clips, logits, labels, frames), replayed
+        return self._results(st.clips, logits, labels, frames, moments), replayed
 
     def _run_graph(self, st: Step, want_labels: bool):
         src, r = self._frames.pop(st.new[0])
@@ -734,7 +810,7 @@ class VideoSegmenter:
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
-                logits, labels = self._compute(self._static_image(raw, u8), table, 1, 1, want_labels, frames)
+                logits, labels, moments = self._compute(self._static_image(raw, u8), table, 1, 1, want_labels, frames)
                 logits = logits.clone()
             torch.cuda.current_stream().wait_stream(side)
             torch.cuda.synchronize()
@@ -742,24 +818,30 @@ class VideoSegmenter:
             graph = torch.cuda.CUDAGraph()
             autocast = torch.is_autocast_enabled()
             with torch.cuda.graph(graph):
-                out, out_labels = self._compute(self._static_image(raw, u8), table, 1, 1, want_labels, frames)
-            self._g = (graph, raw, table, out, out_labels, want_labels, autocast, u8)
-            return logits, labels, False, frames
-        graph, raw, table, out, out_labels, _, autocast, u8 = g
+                out, out_labels, out_moments = self._compute(self._static_image(raw, u8), table, 1, 1, want_labels, frames)
+            self._g = (graph, raw, table, out, out_labels, want_labels, autocast, u8, out_moments)
+            return logits, labels, moments, False, frames
+        graph, raw, table, out, out_labels, _, autocast, u8, out_moments = g
         if torch.is_autocast_enabled() != autocast:
             raise StswinHipError("autocast differs from the state the step was captured under: make a new VideoSegmenter")
         self._put_frames(src, r, 1, raw)
         self._upload_table(st.table(), table)
         graph.replay()
-        return out, out_labels, True, [u8] if self._table is not None else None
+        return out, out_labels, out_moments, True, [u8] if self._table is not None else None
 
-    def _results(self, clips: List[int], logits: torch.Tensor, labels: Optional[torch.Tensor], frames=None) -> List[Tuple[int, object]]:
-        """`labels`: the step's labels (out="overlay": its overlays), or None when some clip has ground truth or out="logits"."""
+    def _results(self, clips: List[int], logits: torch.Tensor, labels: Optional[torch.Tensor], frames=None,
+                 moments: Optional[torch.Tensor] = None) -> List[Tuple[int, object]]:
+        """`labels`: the step's labels (out="overlay": its overlays) and with report their `moments`, or None when some clip has ground
+        truth or out="logits"."""
         if labels is not None:
-            return [(g, labels[b]) for b, g in enumerate(clips)]
+            if moments is None:
+                return [(g, labels[b]) for b, g in enumerate(clips)]
+            return [(g, self._reported(g, labels[b], moments[b:b + 1])) for b, g in enumerate(clips)]
         res = []
+        mom = {}                              # report: the moments of the labels that final() last saw, per clip
 
         def final(b, lab):                    # labels (1, *out_size) -> the result form of out="labels" | "overlay"
+            mom[b] = self._moments(lab)       # (before the overlay launch: it reads the labels)
             return lab[0] if self._table is None else self._overlay(lab, frames[b:b + 1])[0]
 
         for b, g in enumerate(clips):
@@ -780,6 +862,8 @@ class VideoSegmenter:
             from .utils.EndoMetric import predict_and_score
             lab, dices, ious = predict_and_score(logits[b:b + 1], self.out_size, gt)
             res.append((g, (lg if self.out == "logits" else final(b, lab), dices[0], ious[0])))
+        if self.report is not None:
+            res = [(g, self._reported(g, r, mom[b])) for b, (g, r) in enumerate(res)]
         return res
 
 
