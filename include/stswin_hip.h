@@ -595,6 +595,33 @@ int stswin_gt_decode(const unsigned char* in, const unsigned char* table, void* 
  * 1 .. 64.  (-1544 is stswin_pair_loss's.) */
 int stswin_label_moments(const unsigned char* labels /*[n][H][W]*/, long long* out /*[n][nc][10]*/, int n, int H, int W, int nc,
                          void* stream);
+/* ---- connected instances of a label map (stswincl_amd/utils/instruments.py label_components, VideoSegmenter(instances=K)): labels
+ * uint8 [n][H][W] -> components int32 [n][H][W], rows int64 [n][K][12], total int32 [n].  A component is a maximal set of pixels of
+ * one frame with the same label c < nc, bit c of `skip` clear, joined under connectivity 4 or 8; a frame's components of all classes
+ * are numbered 0, 1, 2, ... by their first pixel in raster order (the smallest y W + x they hold).
+ *   components  every pixel's ordinal, not bounded by K; -1 for a skipped label or a label >= nc
+ *   total[f]    the number of components of frame f, not bounded by K
+ *   rows[f][i]  for i < min(total[f], K):   0: class   1: first = y W + x of the first pixel   2 .. 11: the ten integers of
+ *               stswin_label_moments over the component's pixels (count, sum x, sum y, sum x^2, sum xy, sum y^2, max(W - x),
+ *               max(H - y), max(x + 1), max(y + 1)); all zero from total[f] on.  With total[f] > K the rows kept are the first K in
+ *               that order, whatever the order of execution; components and total are complete even then.
+ * All three outputs are written in full by the call (rows is cleared by a fill kernel on the stream, no memset node).  workspace:
+ * caller-owned, 4-byte aligned, >= stswin_label_components_scratch(n, H, W) bytes (an int32 parent map and the counts of the
+ * numbering pass); nothing in it needs clearing and nothing survives the call.  Seven launches (six when the map is one tile), no
+ * synchronisation, no allocation (graph-capturable); no kernel waits on another workgroup.  Integer atomics only (exact, independent
+ * of order: bit-reproducible).  Any pointer alignment of labels, any W; 1 <= H, W <= 16384.  The buffers must not overlap (the host
+ * wrapper checks).
+ * Errors, before anything is launched: -1830 n, H or W <= 0, or H or W > 16384 (or more workgroups than a grid holds; also what
+ * stswin_label_components_scratch returns for such a shape); -1831 labels, components, rows, total or workspace NULL; -1832 nc
+ * outside 1 .. 64; -1833 connectivity not 4 or 8; -1834 K outside 1 .. 1024; -1835 workspace_bytes too small or workspace not 4-byte
+ * aligned. */
+long stswin_label_components_scratch(int n, int H, int W);
+int stswin_label_components(const unsigned char* labels /*[n][H][W]*/, int* components /*[n][H][W]*/, long long* rows /*[n][K][12]*/,
+                            int* total /*[n]*/, int n, int H, int W, int nc, int connectivity, long skip, int K, void* workspace,
+                            long workspace_bytes, void* stream);
+/* the geometry of stswin_label_components (the tests place their shapes around it): which = 0, 1: height and width in pixels of the
+ * tile a workgroup labels in LDS (16, 64), 2: the pixels of a raster chunk of the numbering pass (2048); anything else: -1. */
+int stswin_label_components_geometry(int which);
 /* ---- frames as a video source delivers them (stswincl_amd/utils/yuv.py, VideoSegmenter(pixel_format=..., out_format="nv12")):
  * stswin_yuv_to_rgb makes the HWC RGB frame uint8 [n][Hs][Ws][3] that stswin_frame_ingest and stswin_labels_overlay read,
  * stswin_rgb_to_nv12 turns such a frame into NV12.  Hs (NV12) and Ws are even.

@@ -1632,6 +1632,418 @@ extern "C" int stswin_label_moments(const unsigned char* labels, long long* out,
   return 0;
 }
 
+// Connected components of a label map and their moments rows (stswincl_amd/utils/instruments.py, label_components, states the
+// result; VideoSegmenter(instances=K)): block-based union-find on an int32 parent map of frame-local pixel indices y W + x.  A link
+// only ever points to a smaller index of the same component (LDS or global atomicMin), so a component's root is its first pixel in
+// raster order and every loop below is a root chase or a compare-and-lower that ends because a value strictly decreased: no kernel
+// waits on another workgroup - no flag, ticket or look-back - and the launch boundaries are the only ordering between the passes.
+//   1 cc_tile_kernel    a workgroup labels one CC_TH x CC_TW tile in LDS.  A tile row is one wave: a ballot of "differs from the left
+//                       neighbour" gives every pixel the first pixel of its horizontal run; runs of neighbouring rows are joined
+//                       (cc_union in LDS) once per stretch of pixels under the same upper run; then a root chase, and parent = the
+//                       frame-local index of the pixel's in-tile root, -1 for a pixel of a skipped class or a class >= nc
+//   2 cc_border_kernel  a thread per pixel of a tile's first row (first column) joins it with the pixel it faces across the border,
+//                       or with a diagonal one (8-connectivity), once per stretch and pair of tiles: cc_union on the global map
+//   3 cc_count_kernel   every pixel's parent becomes its root; a workgroup counts the roots of its raster chunk of CC_CHUNK pixels
+//   4 cc_scan_kernel    one workgroup per frame: exclusive scan of the chunk counts (in place) and the frame's total
+//   5 cc_number_kernel  a root's ordinal = its chunk's offset + its rank in the chunk (raster order, so truncation keeps the first K);
+//                       the ordinal goes into `components` at the root, class and first pixel into its row
+//   6 cc_rows_kernel    a thread takes up to CC_PPT pixels of one row: components = the root's ordinal for every other pixel, and
+//                       the ten moments terms into rows[ordinal] for ordinals < K.  As label_moments_kernel does for labels: a full
+//                       chunk of one component is pre-added across the wave per distinct ordinal (DPP sums of small numbers, lane
+//                       63 expands them), a chunk with several runs adds run by run, both into the workgroup's LDS table of the
+//                       instances it meets, which ends as one 64-bit global atomic per non-zero entry.
+// Integer atomics only: exact and independent of the order.  rows is cleared by a fill kernel; every other word that is read was
+// written by an earlier pass (parent, counts, total and components in full).  No kernel uses scratch memory.
+#define CC_TH 16
+#define CC_TW 64
+#define CC_CHUNK 2048
+#define CC_PPT 8
+#define CC_THREADS 256
+
+__device__ __forceinline__ bool cc_valid(unsigned l, int nc, unsigned long long skip) { return l < (unsigned)nc && !((skip >> (l & 63u)) & 1ull); }
+
+__device__ __forceinline__ int cc_load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// Join the sets of a and b; P[i] <= i always.  Each turn either ends or continues with a strictly smaller a.
+template <typename Find>
+__device__ __forceinline__ void cc_union(int* P, int a, int b, Find find) {
+  for (;;) {
+    a = find(P, a);
+    b = find(P, b);
+    if (a == b) return;
+    if (a < b) {
+      const int t = a;
+      a = b;
+      b = t;
+    }
+    const int old = atomicMin(P + a, b);          // a was a root when read: link it below b, unless someone lowered it first
+    if (old == a) return;
+    a = old;
+  }
+}
+
+struct CcFindLds {
+  __device__ __forceinline__ int operator()(const int* P, int a) const {
+    int p;
+    while ((p = ((const volatile int*)P)[a]) != a) a = p;
+    return a;
+  }
+};
+struct CcFindGlobal {
+  __device__ __forceinline__ int operator()(const int* P, int a) const {
+    int p;
+    while ((p = cc_load(P + a)) != a) a = p;
+    return a;
+  }
+};
+
+__global__ __launch_bounds__(CC_THREADS) void cc_tile_kernel(const unsigned char* __restrict__ labels, int* __restrict__ parent, int H, int W,
+                                                             int nc, unsigned long long skip, int conn8, int tiles_x, int tiles_y) {
+  __shared__ unsigned char cls[CC_TH * CC_TW];
+  __shared__ int L[CC_TH * CC_TW];
+  const int tile = (int)(blockIdx.x % (unsigned)(tiles_x * tiles_y)), f = (int)(blockIdx.x / (unsigned)(tiles_x * tiles_y));
+  const int y0 = tile / tiles_x * CC_TH, x0 = tile % tiles_x * CC_TW;
+  const unsigned char* lab = labels + (long)f * H * W;
+  int* par = parent + (long)f * H * W;
+  const int tx = (int)threadIdx.x & (CC_TW - 1), ty0 = (int)threadIdx.x / CC_TW;      // rows ty0, ty0 + 4, ty0 + 8, ty0 + 12
+  bool start[4];                                                                        // (constant indices only: registers)
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int ty = ty0 + 4 * j, i = ty * CC_TW + tx, y = y0 + ty, x = x0 + tx;
+    unsigned l = 255u;                                                                  // 255: not part of any component
+    if (y < H && x < W) {
+      l = lab[(long)y * W + x];
+      if (!cc_valid(l, nc, skip)) l = 255u;
+    }
+    cls[i] = (unsigned char)l;
+    // a tile row is one wave: every pixel starts at the first pixel of its horizontal run (the highest start bit at or below tx)
+    const unsigned left = (unsigned)__shfl_up((int)l, 1);
+    start[j] = tx == 0 || left != l;
+    const unsigned long long below = __ballot(start[j]) & (~0ull >> (63 - tx));
+    L[i] = ty * CC_TW + 63 - __clzll((long long)below);
+  }
+  __syncthreads();
+  // join the runs of neighbouring rows, once per stretch of pixels that lie under the same upper run: where the stretch begins.  A
+  // diagonal neighbour only matters where the upper neighbour is of another class (else it belongs to the upper neighbour's run),
+  // the upper left one only at the start of a run (else the pixel to the left lies under that run)
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int ty = ty0 + 4 * j, i = ty * CC_TW + tx;
+    const unsigned l = cls[i];
+    if (l == 255u || ty == 0) continue;
+    if (cls[i - CC_TW] == l) {
+      if (start[j] || cls[i - CC_TW - 1] != l) cc_union(L, i, i - CC_TW, CcFindLds());
+    } else if (conn8) {
+      if (start[j] && tx > 0 && cls[i - CC_TW - 1] == l) cc_union(L, i, i - CC_TW - 1, CcFindLds());
+      if (tx < CC_TW - 1 && cls[i - CC_TW + 1] == l) cc_union(L, i, i - CC_TW + 1, CcFindLds());
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int ty = ty0 + 4 * j, i = ty * CC_TW + tx, y = y0 + ty, x = x0 + tx;
+    if (y < H && x < W) {
+      int r = -1;
+      if (cls[i] != 255u) {
+        const int t = CcFindLds()(L, i);
+        r = (y0 + t / CC_TW) * W + x0 + t % CC_TW;
+      }
+      par[(long)y * W + x] = r;
+    }
+  }
+}
+
+__global__ __launch_bounds__(CC_THREADS) void cc_border_kernel(const unsigned char* __restrict__ labels, int* parent, int H, int W, int nc,
+                                                               unsigned long long skip, int conn8, long rows_items, long per_frame, long items) {
+  const long g = (long)blockIdx.x * CC_THREADS + threadIdx.x;
+  if (g >= items) return;                  // (the grid's tail)
+  const int f = (int)(g / per_frame);
+  long q = g - (long)f * per_frame;
+  const unsigned char* lab = labels + (long)f * H * W;
+  int* par = parent + (long)f * H * W;
+  // the pixel (y, x), the step (dy, dx) across the border and the step (ay, ax) along it, t its position along the border of length n,
+  // edge the length of one tile's side along it
+  int y, x, dy, dx, ay, ax, t, n, edge;
+  if (q < rows_items) {
+    y = (int)(q / W + 1) * CC_TH;
+    x = (int)(q % W);
+    dy = -1, dx = 0, ay = 0, ax = 1, t = x, n = W, edge = CC_TW;
+  } else {
+    q -= rows_items;
+    x = (int)(q / H + 1) * CC_TW;
+    y = (int)(q % H);
+    dy = 0, dx = -1, ay = 1, ax = 0, t = y, n = H, edge = CC_TH;
+  }
+  const unsigned l = lab[(long)y * W + x];
+  if (!cc_valid(l, nc, skip)) return;
+  const int p = y * W + x, across = (y + dy) * W + x + dx, along = ay * W + ax;
+  // as in the tile: one union per stretch of border pixels that face the same run on the other side, where the stretch begins - and
+  // where the next pair of tiles begins, whose pixels nothing has joined with the last pair's yet; a diagonal neighbour only where
+  // the facing pixel is of another class, the backward one only at the start of this side's run (else the pixel before faces it)
+  const bool first = t == 0 || lab[p - along] != l;
+  if (lab[across] == l) {
+    if (first || t % edge == 0 || lab[across - along] != l) cc_union(par, p, across, CcFindGlobal());
+  } else if (conn8) {
+    if (first && t > 0 && lab[across - along] == l) cc_union(par, p, across - along, CcFindGlobal());
+    if (t < n - 1 && lab[across + along] == l) cc_union(par, p, across + along, CcFindGlobal());
+  }
+}
+
+// the workgroup's sum of v in every thread (CC_THREADS = 4 waves); `red` is 4 words of LDS
+__device__ __forceinline__ unsigned cc_block_sum(unsigned v, unsigned* red) {
+  const unsigned w = lm_wave<false>(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 63) red[threadIdx.x >> 6] = w;
+  __syncthreads();
+  return red[0] + red[1] + red[2] + red[3];
+}
+
+__global__ __launch_bounds__(CC_THREADS) void cc_count_kernel(int* parent, int* __restrict__ counts, int HW, int chunks) {
+  __shared__ unsigned red[4];
+  const int ch = (int)(blockIdx.x % (unsigned)chunks), f = (int)(blockIdx.x / (unsigned)chunks);
+  int* par = parent + (long)f * HW;
+  const int base = ch * CC_CHUNK + (int)threadIdx.x * CC_PPT;
+  unsigned c = 0;
+#pragma unroll
+  for (int i = 0; i < CC_PPT; ++i) {
+    const int p = base + i;
+    if (p < HW) {
+      int a = par[p];
+      if (a >= 0) {
+        if (a != p) {
+          a = CcFindGlobal()(par, a);
+          par[p] = a;                        // (a reader sees the old link or the root: both lead to the root)
+        } else {
+          c += 1u;
+        }
+      }
+    }
+  }
+  c = cc_block_sum(c, red);
+  if (threadIdx.x == 0) counts[(long)f * chunks + ch] = (int)c;
+}
+
+// inclusive scan of v over the workgroup's threads; `red` is 4 words of LDS
+__device__ __forceinline__ unsigned cc_block_scan(unsigned v, unsigned* red) {
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const unsigned t = __shfl_up(v, o);
+    if ((int)(threadIdx.x & 63) >= o) v += t;
+  }
+  __syncthreads();
+  if ((threadIdx.x & 63) == 63) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  const int w = threadIdx.x >> 6;
+  return v + (w > 0 ? red[0] : 0u) + (w > 1 ? red[1] : 0u) + (w > 2 ? red[2] : 0u);
+}
+
+__global__ __launch_bounds__(CC_THREADS) void cc_scan_kernel(int* counts, int* __restrict__ total, int chunks) {
+  __shared__ unsigned red[4];
+  int* c = counts + (long)blockIdx.x * chunks;
+  unsigned carry = 0;
+  for (int base = 0; base < chunks; base += CC_THREADS) {
+    const int i = base + (int)threadIdx.x;
+    const unsigned v = i < chunks ? (unsigned)c[i] : 0u;
+    const unsigned incl = cc_block_scan(v, red);
+    if (i < chunks) c[i] = (int)(carry + incl - v);
+    carry += red[0] + red[1] + red[2] + red[3];
+  }
+  if (threadIdx.x == 0) total[blockIdx.x] = (int)carry;
+}
+
+__global__ __launch_bounds__(CC_THREADS) void cc_number_kernel(const unsigned char* __restrict__ labels, const int* __restrict__ parent,
+                                                               const int* __restrict__ offsets, int* __restrict__ comp,
+                                                               unsigned long long* __restrict__ rows, int HW, int chunks, int K) {
+  __shared__ unsigned red[4];
+  const int ch = (int)(blockIdx.x % (unsigned)chunks), f = (int)(blockIdx.x / (unsigned)chunks);
+  const int* par = parent + (long)f * HW;
+  const int base = ch * CC_CHUNK + (int)threadIdx.x * CC_PPT;
+  unsigned mask = 0;                         // bit i: pixel base + i is a root
+#pragma unroll
+  for (int i = 0; i < CC_PPT; ++i)
+    if (base + i < HW && par[base + i] == base + i) mask |= 1u << i;
+  const unsigned mine = (unsigned)__builtin_popcount(mask);
+  unsigned o = (unsigned)offsets[(long)f * chunks + ch] + cc_block_scan(mine, red) - mine;
+#pragma unroll
+  for (int i = 0; i < CC_PPT; ++i)
+    if (mask & (1u << i)) {
+      const int p = base + i;
+      comp[(long)f * HW + p] = (int)o;
+      if (o < (unsigned)K) {
+        unsigned long long* r = rows + ((long)f * K + o) * 12;
+        r[0] = labels[(long)f * HW + p];
+        r[1] = (unsigned long long)p;
+      }
+      ++o;
+    }
+}
+
+__device__ __forceinline__ void cc_flush(unsigned long long* r, const LmTerms& t) {      // r: the instance's row
+  atomicAdd(r + 2, (unsigned long long)t.n);
+  atomicAdd(r + 3, (unsigned long long)t.sx);
+  atomicAdd(r + 4, (unsigned long long)t.sy);
+  atomicAdd(r + 5, t.sxx);
+  atomicAdd(r + 6, t.sxy);
+  atomicAdd(r + 7, t.syy);
+  atomicMax(r + 8, (unsigned long long)t.e0);
+  atomicMax(r + 9, (unsigned long long)t.e1);
+  atomicMax(r + 10, (unsigned long long)t.e2);
+  atomicMax(r + 11, (unsigned long long)t.e3);
+}
+
+// The workgroup's table of the instances it meets: slot ord % CC_SLOTS belongs to the first ordinal that claims it (compare-and-swap
+// on its tag), later ordinals of the same slot go to the global row directly.  Nothing waits: a claim succeeds or the other path is taken.
+#define CC_SLOTS 32
+
+struct CcTable {
+  int tag[CC_SLOTS];
+  unsigned long long sums[CC_SLOTS * 6];
+  unsigned ext[CC_SLOTS * 4];
+};
+
+__device__ __forceinline__ void cc_add(CcTable& tb, unsigned long long* frows, int ord, const LmTerms& t) {
+  const int slot = ord & (CC_SLOTS - 1);
+  int owner = ((volatile int*)tb.tag)[slot];
+  if (owner == -1) {
+    owner = atomicCAS(&tb.tag[slot], -1, ord);
+    if (owner == -1) owner = ord;
+  }
+  if (owner == ord) lm_flush(tb.sums, tb.ext, (unsigned)slot, t);
+  else cc_flush(frows + (long)ord * 12, t);
+}
+
+__global__ __launch_bounds__(CC_THREADS) void cc_rows_kernel(const int* __restrict__ parent, int* comp, unsigned long long* rows, int H, int W,
+                                                             int K, int cpr, int blocks_per_frame) {
+  __shared__ CcTable tb;
+  for (int i = threadIdx.x; i < CC_SLOTS; i += CC_THREADS) tb.tag[i] = -1;
+  for (int i = threadIdx.x; i < CC_SLOTS * 6; i += CC_THREADS) tb.sums[i] = 0ull;
+  for (int i = threadIdx.x; i < CC_SLOTS * 4; i += CC_THREADS) tb.ext[i] = 0u;
+  __syncthreads();
+  const int f = (int)(blockIdx.x / (unsigned)blocks_per_frame);
+  const int q = (int)(blockIdx.x % (unsigned)blocks_per_frame) * CC_THREADS + (int)threadIdx.x;
+  const int row = q / cpr, col = q - row * cpr;
+  const bool valid = row < H;                                  // (the wave's lanes with a chunk are a prefix)
+  const int len = valid ? min(CC_PPT, W - CC_PPT * col) : 0;
+  const long fo = (long)f * H * W;
+  const int p0 = row * W + CC_PPT * col;
+  const int* par = parent + fo;
+  int* cmp = comp + fo;
+  unsigned long long* frows = rows + (long)f * K * 12;
+  // runs of one root, left to right; the chunk is `full` when it is one run of CC_PPT pixels of a component
+  int run_root = -2, run_start = 0, run_ord = -1, ord = -1;      // ord: a full chunk's ordinal
+  bool full = false;
+#pragma unroll
+  for (int i = 0; i <= CC_PPT; ++i) {
+    const int r = i < len ? par[p0 + i] : -2;
+    if (r != run_root) {
+      if (run_root >= 0) {                                     // the run [run_start, i) ends here
+        if (run_start == 0 && i == CC_PPT) full = true, ord = run_ord;
+        else if (run_ord < K)
+          cc_add(tb, frows, run_ord, lm_run((unsigned)(CC_PPT * col + run_start), (unsigned)(i - run_start), (unsigned)row, (unsigned)H, (unsigned)W));
+      }
+      run_root = r;
+      run_start = i;
+      run_ord = r >= 0 ? cmp[r] : -1;                          // (written at the roots by cc_number_kernel; this kernel writes the others)
+    }
+    if (i < len && r != p0 + i) cmp[p0 + i] = run_ord;
+  }
+  // the full chunks, ordinal by ordinal (wave-uniform from here: every lane takes part in the sums)
+  const unsigned row_w = (unsigned)__builtin_amdgcn_readfirstlane(row);       // lane 0's row: the smallest of the wave
+  const unsigned cx = (unsigned)col, dy = (unsigned)row - row_w;              // cx < 2048, dy <= 64 / cpr + 1
+  unsigned long long todo = __ballot(full && ord < K);
+  while (todo) {
+    const int first = __ffsll((long long)todo) - 1;
+    const int O = __builtin_amdgcn_readlane(ord, first);
+    const bool mine = full && ord == O;
+    const unsigned long long m = __ballot(mine);
+    todo &= ~m;
+    const int last = 63 - __clzll((long long)m);
+    const unsigned mcx = mine ? cx : 0u, mdy = mine ? dy : 0u;
+    // <= 64 lanes of cx < 2048, dy <= 65: every sum stays below 2^32; the count and sum dy share a word (64 < 2^8)
+    const unsigned c_sdy = lm_wave<false>((mine ? 1u : 0u) | (mdy << 8));
+    const unsigned scx = lm_wave<false>(mcx), scx2 = lm_wave<false>(mcx * mcx), scxdy = lm_wave<false>(mcx * mdy);
+    const unsigned sdy2 = lm_wave<false>(mdy * mdy);
+    const unsigned cx_max = lm_wave<true>(mcx), cx_min = 2047u - lm_wave<true>(mine ? 2047u - cx : 0u);
+    const unsigned dy_min = (unsigned)__builtin_amdgcn_readlane((int)dy, first), dy_max = (unsigned)__builtin_amdgcn_readlane((int)dy, last);
+    if ((threadIdx.x & 63) == 63) {
+      const unsigned c = c_sdy & 255u, sdy = c_sdy >> 8;
+      const unsigned sy = c * row_w + sdy;                                                      // sum of the chunks' rows
+      const unsigned long long scxy = (unsigned long long)row_w * scx + scxdy;
+      const unsigned long long sy2 = (unsigned long long)c * (row_w * row_w) + (unsigned long long)(2u * row_w * sdy + sdy2);
+      LmTerms t;                       // sum_{i<8} (8 cx + i) = 64 cx + 28, sum (8 cx + i)^2 = 512 cx^2 + 448 cx + 140
+      t.n = 8u * c;
+      t.sx = 64u * scx + 28u * c;
+      t.sy = 8u * sy;
+      t.sxx = 512ull * scx2 + (unsigned long long)(448u * scx + 140u * c);
+      t.sxy = 64ull * scxy + 28ull * sy;
+      t.syy = 8ull * sy2;
+      t.e0 = (unsigned)W - 8u * cx_min;
+      t.e1 = (unsigned)H - (row_w + dy_min);
+      t.e2 = 8u * cx_max + 8u;
+      t.e3 = row_w + dy_max + 1u;
+      cc_add(tb, frows, O, t);
+    }
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < CC_SLOTS * 10; i += CC_THREADS) {        // the table's non-zero entries into the rows of their owners
+    const int slot = i / 10, k = i - 10 * slot, owner = tb.tag[slot];
+    if (owner < 0) continue;
+    unsigned long long* o = frows + (long)owner * 12 + 2 + k;
+    if (k < 6) {
+      const unsigned long long v = tb.sums[6 * slot + k];
+      if (v) atomicAdd(o, v);
+    } else {
+      const unsigned e = tb.ext[4 * slot + k - 6];
+      if (e) atomicMax(o, (unsigned long long)e);
+    }
+  }
+}
+
+extern "C" int stswin_label_components_geometry(int which) { return which == 0 ? CC_TH : which == 1 ? CC_TW : which == 2 ? CC_CHUNK : -1; }
+
+extern "C" long stswin_label_components_scratch(int n, int H, int W) {
+  if (n <= 0 || H <= 0 || W <= 0 || H > 16384 || W > 16384) return -1830;
+  const long HW = (long)H * W, chunks = (HW + CC_CHUNK - 1) / CC_CHUNK;
+  return 4 * (long)n * (HW + chunks);                    // the parent map, then the chunk counts
+}
+
+extern "C" int stswin_label_components(const unsigned char* labels, int* components, long long* rows, int* total, int n, int H, int W, int nc,
+                                       int connectivity, long skip, int K, void* workspace, long workspace_bytes, void* stream) {
+  if (n <= 0 || H <= 0 || W <= 0 || H > 16384 || W > 16384) return -1830;
+  if (labels == nullptr || components == nullptr || rows == nullptr || total == nullptr || workspace == nullptr) return -1831;
+  if (nc < 1 || nc > 64) return -1832;
+  if (connectivity != 4 && connectivity != 8) return -1833;
+  if (K < 1 || K > 1024) return -1834;
+  if (workspace_bytes < stswin_label_components_scratch(n, H, W) || ((uintptr_t)workspace & 3)) return -1835;
+  const int HW = H * W, chunks = (HW + CC_CHUNK - 1) / CC_CHUNK;
+  const int tiles_x = (W + CC_TW - 1) / CC_TW, tiles_y = (H + CC_TH - 1) / CC_TH;
+  const int cpr = (W + CC_PPT - 1) / CC_PPT;
+  const long bpf = ((long)H * cpr + CC_THREADS - 1) / CC_THREADS;
+  const long rows_items = (long)(tiles_y - 1) * W, per_frame = rows_items + (long)(tiles_x - 1) * H;
+  const long border_blocks = (per_frame * n + CC_THREADS - 1) / CC_THREADS;
+  if ((long)tiles_x * tiles_y * n > 0x7fffffffL || (long)chunks * n > 0x7fffffffL || bpf * n > 0x7fffffffL || border_blocks > 0x7fffffffL)
+    return -1830;
+  hipStream_t st = (hipStream_t)stream;
+  int* parent = reinterpret_cast<int*>(workspace);
+  int* counts = parent + (long)n * HW;
+  unsigned long long* r = reinterpret_cast<unsigned long long*>(rows);
+  const unsigned long long sk = (unsigned long long)skip;
+  const int conn8 = connectivity == 8;
+  stswin_zero_bytes(rows, sizeof(long long) * 12 * (size_t)K * (size_t)n, st);         // (a kernel, not hipMemsetAsync: see common.h)
+  hipLaunchKernelGGL(cc_tile_kernel, dim3((unsigned)(tiles_x * tiles_y * n)), dim3(CC_THREADS), 0, st, labels, parent, H, W, nc, sk, conn8, tiles_x,
+                     tiles_y);
+  if (per_frame > 0)
+    hipLaunchKernelGGL(cc_border_kernel, dim3((unsigned)border_blocks), dim3(CC_THREADS), 0, st, labels, parent, H, W, nc, sk, conn8, rows_items,
+                       per_frame, per_frame * n);
+  hipLaunchKernelGGL(cc_count_kernel, dim3((unsigned)(chunks * n)), dim3(CC_THREADS), 0, st, parent, counts, HW, chunks);
+  hipLaunchKernelGGL(cc_scan_kernel, dim3((unsigned)n), dim3(CC_THREADS), 0, st, counts, total, chunks);
+  hipLaunchKernelGGL(cc_number_kernel, dim3((unsigned)(chunks * n)), dim3(CC_THREADS), 0, st, labels, (const int*)parent, (const int*)counts,
+                     components, r, HW, chunks, K);
+  hipLaunchKernelGGL(cc_rows_kernel, dim3((unsigned)(bpf * n)), dim3(CC_THREADS), 0, st, (const int*)parent, components, r, H, W, K, cpr, (int)bpf);
+  STSWIN_CHECK_LAUNCH();
+  return 0;
+}
+
 // Frames as a video source delivers them (stswincl_amd/utils/yuv.py states the arithmetic): NV12 or UYVY -> the HWC RGB frame that
 // stswin_frame_ingest and stswin_labels_overlay read, and RGB -> NV12.  matrix int32 [3][4]: out_c = clamp((m[c][0] t0 + m[c][1] t1 +
 // m[c][2] t2 + m[c][3]) >> 14, 0, 255) in int32 (|sum| < 2^25).  A thread owns YUV_PPT = 8 (wide body) or 2 (byte body) consecutive

@@ -1507,7 +1507,91 @@ def label_moments(labels: torch.Tensor, nc: int, out: Optional[torch.Tensor] = N
     return out
 
 
-YUV_NV12, YUV_UYVY = 0, 1                      # stswin_yuv_to_rgb's `format` (plain integers in the header's comment, not #defines)
+CC_TILE = (16, 64)          # stswin_label_components: (height, width) of the tile a workgroup labels in LDS ...
+CC_CHUNK = 2048             # ... and the pixels of a raster chunk of its numbering pass (stswin_label_components_geometry gives the same)
+
+
+def label_components_scratch(n: int, H: int, W: int) -> int:
+    """Bytes of workspace hip.label_components needs for labels [n][H][W]."""
+    b = int(load().stswin_label_components_scratch(n, H, W))
+    if b < 0:
+        raise StswinHipError(f"label_components: {n} maps of {H} x {W}, the kernel takes up to 16384 x 16384")
+    return b
+
+
+def label_components(labels: torch.Tensor, nc: int, connectivity: int = 8, skip=(), max_instances: int = 256, out=None,
+                     workspace: Optional[torch.Tensor] = None):
+    """uint8 labels [n][H][W] -> (components int32 [n][H][W], rows int64 [n][K][12], total int32 [n]), K = max_instances: the connected
+    components (4- or 8-connectivity, within a frame) of the labels c < nc not in `skip`, numbered per frame by their first pixel in
+    raster order; components holds each pixel's ordinal (-1: no component), total the frame's count, neither bounded by K; rows[f][i]
+    for i < min(total[f], K) is [class, first pixel y W + x, then the ten integers of label_moments over the instance], zero from
+    total[f] on (utils.instruments.label_components is the numpy definition, matched bit for bit, truncation included).  out: a triple
+    of such buffers, written in full; workspace: uint8, >= label_components_scratch(n, H, W) bytes.  With both given the call
+    allocates nothing and synchronises nothing (graph-capturable).  Returns the triple (include/stswin_hip.h,
+    stswin_label_components)."""
+    if not isinstance(labels, torch.Tensor) or labels.dtype != torch.uint8 or labels.dim() != 3 or not labels.is_contiguous():
+        got = f"{labels.dtype} {tuple(labels.shape)}" if isinstance(labels, torch.Tensor) else type(labels).__name__
+        raise StswinHipError(f"label_components: labels must be contiguous uint8 [n][H][W], got {got}")
+    if not labels.is_cuda:
+        raise StswinHipError("label_components: labels must be on the GPU (no CPU path exists; utils.instruments.label_components is "
+                             "the numpy definition)")
+    n, H, W = labels.shape
+    if n <= 0 or H <= 0 or W <= 0:
+        raise StswinHipError(f"label_components: empty labels {tuple(labels.shape)}")
+    if H > 16384 or W > 16384:
+        raise StswinHipError(f"label_components: a {H} x {W} map, the kernel takes up to 16384 x 16384")
+    if isinstance(nc, bool) or not isinstance(nc, int) or not 1 <= nc <= 64:
+        raise StswinHipError(f"label_components: {nc!r} classes, the kernel takes 1 .. 64")
+    if isinstance(connectivity, bool) or not isinstance(connectivity, int) or connectivity not in (4, 8):
+        raise StswinHipError(f"label_components: connectivity must be 4 or 8, got {connectivity!r}")
+    try:
+        skip = tuple(skip)
+    except TypeError:
+        skip = (skip,)
+    if any(isinstance(c, bool) or not isinstance(c, int) or not 0 <= c <= 63 for c in skip):
+        raise StswinHipError(f"label_components: skip holds classes 0 .. 63, got {skip!r}")
+    K = max_instances
+    if isinstance(K, bool) or not isinstance(K, int) or not 1 <= K <= 1024:
+        raise StswinHipError(f"label_components: max_instances must be 1 .. 1024, got {K!r}")
+    dev = labels.device
+    want = (("components", torch.int32, (n, H, W)), ("rows", torch.int64, (n, K, 12)), ("total", torch.int32, (n,)))
+    if out is None:
+        out = tuple(torch.empty(shape, dtype=dt, device=dev) for _, dt, shape in want)
+    else:
+        if not isinstance(out, (tuple, list)) or len(out) != 3:
+            raise StswinHipError("label_components: out must be the triple (components, rows, total)")
+        for t, (what, dt, shape) in zip(out, want):
+            if not isinstance(t, torch.Tensor) or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
+                got = f"{t.dtype} {tuple(t.shape)} on {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__
+                form = "".join(f"[{d}]" for d in shape)
+                raise StswinHipError(f"label_components: {what} must be contiguous {dt} {form} on {dev}, got {got}")
+    need = label_components_scratch(n, H, W)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.dim() != 1 or not workspace.is_contiguous()
+          or workspace.device != dev):
+        got = f"{workspace.dtype} {tuple(workspace.shape)} on {workspace.device}" if isinstance(workspace, torch.Tensor) else type(workspace).__name__
+        raise StswinHipError(f"label_components: workspace must be contiguous uint8 [bytes] on {dev}, got {got}")
+    elif workspace.numel() < need:
+        raise StswinHipError(f"label_components: a workspace of {workspace.numel()} bytes, {n} maps of {H} x {W} need {need}")
+    elif workspace.data_ptr() % 4:
+        raise StswinHipError("label_components: workspace must be 4-byte aligned")
+    bufs = (("labels", labels), ("components", out[0]), ("rows", out[1]), ("total", out[2]), ("workspace", workspace))
+    for i, (wa, a) in enumerate(bufs):
+        for wb, b in bufs[i + 1:]:
+            if _same_memory(a, b):
+                raise StswinHipError(f"label_components: {wb} shares memory with {wa}")
+    mask = 0
+    for c in skip:
+        mask |= 1 << c
+    if mask >= 1 << 63:                      # (the mask travels in a C long: bit 63 is its sign bit)
+        mask -= 1 << 64
+    _check(load().stswin_label_components(_p(labels), _p(out[0]), _p(out[1]), _p(out[2]), n, H, W, nc, connectivity, mask, K,
+                                          _p(workspace), workspace.numel(), _stream()), "label_components")
+    return tuple(out)
+
+
+YUV_NV12, YUV_UYVY = 0, 1                     # stswin_yuv_to_rgb's `format` (plain integers in the header's comment, not #defines)
 YUV_REPLICATE, YUV_LINEAR = 0, 1               # ... and its `chroma`
 _YUV_FORMATS = {"nv12": YUV_NV12, "uyvy": YUV_UYVY}
 _YUV_CHROMA = {"replicate": YUV_REPLICATE, "linear": YUV_LINEAR}

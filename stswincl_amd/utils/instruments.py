@@ -10,6 +10,10 @@ stswin_label_moments):
 The extent is four maxima, so an all-zero row is an absent class and rows pool by adding 0 .. 5 and taking the maximum of 6 .. 9; the
 half-open box of a present class is [W - row[6], row[8]) x [H - row[7], row[9]).  Labels >= nc are counted nowhere.
 
+label_components splits the classes into connected instances (hip.label_components, VideoSegmenter(instances=K)): one row of twelve
+integers per frame and instance - its class, its first pixel y * W + x in raster order, then the ten above over its pixels - and
+InstanceReport reads those rows as InstrumentReport reads the class rows, by the same arithmetic.
+
 This module ships no dataset's class names: pass `names` if the rows of a log should carry them."""
 from __future__ import annotations
 
@@ -43,6 +47,97 @@ def label_moments(labels, nc: int) -> np.ndarray:
             out[f, c] = [x.size, x.sum(), y.sum(), (x * x).sum(), (x * y).sum(), (y * y).sum(),
                          (W - x).max(), (H - y).max(), (x + 1).max(), (y + 1).max()]
     return out
+
+
+INSTANCE_ROW = 12       # integers per frame and instance: class, first pixel, then the ten above
+
+
+def label_components(labels, nc: int, connectivity: int = 8, skip: Sequence[int] = (), max_instances: int = 256):
+    """Integer labels [n][H][W] (or one [H][W]) -> (components int32 [n][H][W], rows int64 [n][K][12], total int32 [n]) with K =
+    max_instances: what hip.label_components gives bit for bit.
+
+    A component is a maximal set of pixels of one frame with the same label c < nc, c not in `skip`, joined under 4- or
+    8-connectivity.  A frame's components of all classes are numbered 0, 1, 2, ... by their first pixel in raster order (the smallest
+    y * W + x they hold).  components holds every pixel's ordinal (not bounded by K), -1 for skipped labels and labels >= nc; total[f]
+    is the frame's number of components (not bounded by K either); rows[f][i] for i < min(total[f], K) is [class, first = y * W + x]
+    followed by the ten integers of the moments row over the component's pixels, and all zero from total[f] on.  With total > K the rows
+    kept are the first K in that order.
+
+    Two passes with a union-find whose roots are the smallest index of their set, so a root is its component's first pixel."""
+    lab = np.asarray(labels)
+    if lab.ndim == 2:
+        lab = lab[None]
+    if lab.ndim != 3 or lab.dtype.kind not in "iu" or min(lab.shape) < 1:
+        raise ValueError(f"label_components: labels are integers [n][H][W], got {lab.dtype} {lab.shape}")
+    if isinstance(nc, bool) or int(nc) != nc or not 1 <= nc <= 64:
+        raise ValueError(f"label_components: 1 .. 64 classes, got {nc!r}")
+    if connectivity not in (4, 8):
+        raise ValueError(f"label_components: connectivity is 4 or 8, got {connectivity!r}")
+    skip = tuple(skip)
+    if any(isinstance(c, bool) or int(c) != c or not 0 <= c <= 63 for c in skip):
+        raise ValueError(f"label_components: skip holds classes 0 .. 63, got {skip!r}")
+    K = max_instances
+    if isinstance(K, bool) or int(K) != K or not 1 <= K <= 1024:
+        raise ValueError(f"label_components: max_instances is 1 .. 1024, got {K!r}")
+    n, H, W = lab.shape
+    back = [(0, -1), (-1, 0)] + ([(-1, -1), (-1, 1)] if connectivity == 8 else [])     # the neighbours that come earlier in raster order
+    comp = np.full((n, H, W), -1, dtype=np.int32)
+    rows = np.zeros((n, K, INSTANCE_ROW), dtype=np.int64)
+    total = np.zeros(n, dtype=np.int32)
+    for f in range(n):
+        # plain Python lists and integers from here on (exact, and quicker to index than arrays); -1: a pixel of no component
+        cls = [c if 0 <= c < nc and c not in skip else -1 for c in lab[f].reshape(-1).tolist()]
+        parent = list(range(H * W))
+
+        def find(a):
+            while parent[a] != a:
+                parent[a] = parent[parent[a]]
+                a = parent[a]
+            return a
+
+        for p in range(H * W):                # pass 1: join every pixel with its earlier neighbours of the same label
+            if cls[p] < 0:
+                continue
+            y, x = divmod(p, W)
+            for dy, dx in back:
+                v, u = y + dy, x + dx
+                if v >= 0 and 0 <= u < W and cls[v * W + u] == cls[p]:
+                    a, b = find(p), find(v * W + u)
+                    if a != b:
+                        parent[max(a, b)] = min(a, b)
+        ordinal, kept, flat = {}, [], [-1] * (H * W)
+        for p in range(H * W):                # pass 2: roots come up in raster order of the first pixel
+            if cls[p] < 0:
+                continue
+            y, x = divmod(p, W)
+            r = find(p)
+            if r == p:
+                ordinal[r] = len(ordinal)
+                if len(kept) < K:
+                    kept.append([cls[p], p, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0])
+            i = flat[p] = ordinal[r]
+            if i < K:
+                row = kept[i]
+                for k, v in enumerate((1, x, y, x * x, x * y, y * y)):
+                    row[2 + k] += v
+                for k, v in enumerate((W - x, H - y, x + 1, y + 1)):
+                    row[8 + k] = max(row[8 + k], v)
+        comp[f] = np.asarray(flat, dtype=np.int32).reshape(H, W)
+        if kept:
+            rows[f, :len(kept)] = kept
+        total[f] = len(ordinal)
+    return comp, rows, total
+
+
+def _shape_of(row, H: int, W: int):
+    """One present ten-integer row -> (box, centroid, angle, axes), the arithmetic both reports share."""
+    n, sx, sy, sxx, sxy, syy, ex0, ey0, ex1, ey1 = (int(v) for v in row)                    # Python integers: exact
+    n20, n11, n02 = n * sxx - sx * sx, n * sxy - sx * sy, n * syy - sy * sy                 # n^2 (mu20, mu11, mu02)
+    big = (n20 + n02) + math.sqrt((n20 - n02) ** 2 + 4 * n11 * n11)                         # 2 n^2 lambda_major
+    major = big / (2 * n * n)
+    minor = 2 * (n20 * n02 - n11 * n11) / (n * n * big) if big > 0 else 0.0
+    return ((W - ex0, H - ey0, ex1, ey1), (sx / n, sy / n), 0.5 * math.atan2(2 * n11, n20 - n02),
+            (math.sqrt(major), math.sqrt(max(minor, 0.0))))
 
 
 class InstrumentReport:
@@ -104,15 +199,7 @@ class InstrumentReport:
         rep.angle = np.full((rows, nc), np.nan)
         rep.axes = np.full((rows, nc, 2), np.nan)
         for r, c in zip(*np.nonzero(rep.present)):
-            n, sx, sy, sxx, sxy, syy, ex0, ey0, ex1, ey1 = (int(v) for v in rep.moments[r, c])      # Python integers: exact
-            rep.box[r, c] = (W - ex0, H - ey0, ex1, ey1)
-            rep.centroid[r, c] = (sx / n, sy / n)
-            n20, n11, n02 = n * sxx - sx * sx, n * sxy - sx * sy, n * syy - sy * sy                 # n^2 (mu20, mu11, mu02)
-            rep.angle[r, c] = 0.5 * math.atan2(2 * n11, n20 - n02)
-            big = (n20 + n02) + math.sqrt((n20 - n02) ** 2 + 4 * n11 * n11)                         # 2 n^2 lambda_major
-            major = big / (2 * n * n)
-            minor = 2 * (n20 * n02 - n11 * n11) / (n * n * big) if big > 0 else 0.0
-            rep.axes[r, c] = (math.sqrt(major), math.sqrt(max(minor, 0.0)))
+            rep.box[r, c], rep.centroid[r, c], rep.angle[r, c], rep.axes[r, c] = _shape_of(rep.moments[r, c], H, W)
         return rep
 
     def __len__(self) -> int:
@@ -141,5 +228,100 @@ class InstrumentReport:
                 row["centroid"] = tuple(float(v) for v in self.centroid[r, c]) if here else None
                 row["angle"] = float(self.angle[r, c]) if here else None
                 row["axes"] = tuple(float(v) for v in self.axes[r, c]) if here else None
+                out.append(row)
+        return out
+
+
+class InstanceReport:
+    """InstrumentReport per connected instance: from the rows and totals of label_components (hip.label_components,
+    VideoSegmenter(instances=K)), per row-frame r and kept instance i < K:
+
+      present   bool    [rows][K]      i < total and count >= min_area
+      cls       int64   [rows][K]      the instance's class (-1 where not present)
+      first     int64   [rows][K]      y * W + x of its first pixel in raster order (-1 where not present)
+      area, box, centroid, angle, axes   as InstrumentReport's, by the same arithmetic, [rows][K] in front
+      total     int64   [rows]         the frame's number of components, not bounded by K
+      truncated bool    [rows]         total > K: the frame holds more instances than rows were kept for
+
+    frames / sequences / names as InstrumentReport's; names are per class."""
+
+    def __init__(self):
+        self.size = None
+        self.min_area = 1
+        self.names = None
+        self.frames: List[int] = []
+        self.sequences: List[int] = []
+        self.rows = self.total = self.truncated = self.present = self.cls = self.first = None
+        self.area = self.box = self.centroid = self.angle = self.axes = None
+
+    @classmethod
+    def from_rows(cls, rows, total, size: Sequence[int], min_area: int = 1, names: Optional[Sequence[str]] = None,
+                  frames: Optional[Sequence[int]] = None, sequences: Optional[Sequence[int]] = None) -> "InstanceReport":
+        """rows: integers [frames][K][12] (or one frame's [K][12]), total: integers [frames] (or a scalar), numpy or CPU torch tensors;
+        size = (H, W) of the label maps."""
+        rw = np.asarray(rows)
+        tot = np.asarray(total)
+        if rw.ndim == 2:
+            rw = rw[None]
+        tot = tot.reshape(-1)
+        if rw.ndim != 3 or rw.shape[2] != INSTANCE_ROW or rw.dtype.kind not in "iu":
+            raise ValueError(f"InstanceReport: rows are integers [frames][K][{INSTANCE_ROW}], got {rw.dtype} {rw.shape}")
+        n, K = rw.shape[:2]
+        if tot.dtype.kind not in "iu" or tot.shape != (n,):
+            raise ValueError(f"InstanceReport: total holds one integer per frame ({n}), got {tot.dtype} {tot.shape}")
+        if isinstance(min_area, bool) or int(min_area) != min_area or min_area < 1:
+            raise ValueError(f"InstanceReport: min_area is an integer >= 1, got {min_area!r}")
+        H, W = (int(v) for v in size)
+        for what, v in (("frames", frames), ("sequences", sequences)):
+            if v is not None and len(v) != n:
+                raise ValueError(f"InstanceReport: {len(v)} {what} for {n} rows")
+        rep = cls()
+        rep.size, rep.min_area = (H, W), int(min_area)
+        rep.names = list(names) if names is not None else None
+        rep.frames = [int(f) for f in frames] if frames is not None else list(range(n))
+        rep.sequences = [int(s) for s in sequences] if sequences is not None else [0] * n
+        rep.rows = rw.astype(np.int64)
+        rep.total = tot.astype(np.int64)
+        rep.truncated = rep.total > K
+        rep.present = (np.arange(K)[None, :] < rep.total[:, None]) & (rep.rows[:, :, 2] >= rep.min_area)
+        rep.cls = np.where(rep.present, rep.rows[:, :, 0], -1)
+        rep.first = np.where(rep.present, rep.rows[:, :, 1], -1)
+        rep.area = np.where(rep.present, rep.rows[:, :, 2], 0)
+        rep.box = np.full((n, K, 4), np.nan)
+        rep.centroid = np.full((n, K, 2), np.nan)
+        rep.angle = np.full((n, K), np.nan)
+        rep.axes = np.full((n, K, 2), np.nan)
+        for r, i in zip(*np.nonzero(rep.present)):
+            rep.box[r, i], rep.centroid[r, i], rep.angle[r, i], rep.axes[r, i] = _shape_of(rep.rows[r, i, 2:], H, W)
+        if rep.names is not None and rep.present.any() and int(rep.cls.max()) >= len(rep.names):
+            raise ValueError(f"InstanceReport: {len(rep.names)} names, the rows hold class {int(rep.cls.max())}")
+        return rep
+
+    def __len__(self) -> int:
+        return len(self.frames)
+
+    def counts(self, nc: Optional[int] = None) -> np.ndarray:
+        """int64 [frames][nc]: the number of present instances per class (nc: the names' length, else the largest class + 1)."""
+        if nc is None:
+            nc = len(self.names) if self.names is not None else (int(self.cls.max()) + 1 if self.present.any() else 0)
+        out = np.zeros((len(self), nc), dtype=np.int64)
+        for r, i in zip(*np.nonzero(self.present)):
+            out[r, self.cls[r, i]] += 1
+        return out
+
+    def as_rows(self) -> List[dict]:
+        """One dict per present instance, in frame order then instance order, for a log: sequence, frame, instance, class (and name,
+        when names were given), area, box, centroid, angle, axes as plain Python values."""
+        out = []
+        for r in range(len(self)):
+            for i in np.nonzero(self.present[r])[0]:
+                row = {"sequence": self.sequences[r], "frame": self.frames[r], "instance": int(i), "class": int(self.cls[r, i])}
+                if self.names is not None:
+                    row["name"] = self.names[row["class"]]
+                row["area"] = int(self.area[r, i])
+                row["box"] = tuple(int(v) for v in self.box[r, i])
+                row["centroid"] = tuple(float(v) for v in self.centroid[r, i])
+                row["angle"] = float(self.angle[r, i])
+                row["axes"] = tuple(float(v) for v in self.axes[r, i])
                 out.append(row)
         return out

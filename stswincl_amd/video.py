@@ -286,7 +286,7 @@ class _Pinned:
 class VideoSegmenter:
     """Segment video sequences with an eval-mode TswinPlus, one result per frame, each frame's ResNet features computed once.
 
-    seg = VideoSegmenter(model, batch=1, out="logits" | "labels" | "overlay", out_size=None, graph=False, report=None)
+    seg = VideoSegmenter(model, batch=1, out="logits" | "labels" | "overlay", out_size=None, graph=False, report=None, instances=None)
 
     push(frames, gt=None) takes uint8 RGB frames [n][Hs][Ws][3] (or one [Hs][Ws][3]; torch tensor on the model's GPU or the CPU, or
     a numpy array; NV12 or UYVY frames with pixel_format, below) and returns [(frame_index, result), ...] for the frames whose clip is now complete.  finish() runs what is
@@ -359,6 +359,21 @@ class VideoSegmenter:
     every frame released since reset_metrics(), rows ordered by sequence and frame, a sequence's ordinal being the number of earlier
     sequences that released a frame.  Class names are the caller's (instrument_report(names=...)).
 
+    instances=K (1 .. 1024; needs report; connectivity=8 | 4, instance_skip=None): the report split into connected instances, for
+    frames that hold two shafts or two claspers.  Wherever the moments launch runs - the scoring paths with ground truth included -
+    the launches of hip.label_components follow it on the same label map: the components of every class not in instance_skip
+    (default: what `transparent` defaults to, (0,) for endovis18 and (classes - 1,) for cadis), numbered per frame by their first pixel
+    in raster order, the first K with a row int64 [12] = class, first pixel y W + x and the ten integers of the moments row
+    (utils.instruments.label_components defines them; K truncates deterministically and `total` still counts every component).
+    report="frame": a result r becomes r + (moments, rows, total), rows int64 [K][12] and total an int32 scalar tensor, both on the
+    device - no download and no synchronisation.  Under graph=True the captured step holds the launches behind the moments launch;
+    the component map and the workspace are the segmenter's own, allocated by the eager warm-up frames, and rows and total of the
+    last replayed step of a push are views of the graph's buffers, as the moments are; with ground truth they are made after the
+    replay, as the labels are.  report="deferred": rows and totals go into a device log that grows as the moments log does;
+    instance_report(names=None) downloads it once and returns utils.instruments.InstanceReport over every frame released since
+    reset_metrics(), with instrument_report()'s order, sequence ordinals and reset() / reset_metrics() behaviour.  instances=None:
+    every result, launch and captured graph is what it is without the keyword.
+
     Runs under torch.no_grad().  Refuses (StswinHipError): a model in train mode, a model or frames not on the GPU, a frame size
     that differs from the earlier frames'."""
 
@@ -366,7 +381,8 @@ class VideoSegmenter:
                  protocol: str = "endovis18", metric_classes: Optional[int] = None, align_corners: Optional[bool] = None,
                  palette=None, alpha: int = 128, transparent: Optional[Sequence[int]] = None, edge_alpha: Optional[int] = 255,
                  gt_table=None, scores: str = "frame", pixel_format: str = "rgb", yuv_standard: str = "bt709", full_range: bool = False,
-                 chroma: str = "replicate", out_format: str = "rgb", report: Optional[str] = None, min_area: int = 1):
+                 chroma: str = "replicate", out_format: str = "rgb", report: Optional[str] = None, min_area: int = 1,
+                 instances: Optional[int] = None, connectivity: int = 8, instance_skip: Optional[Sequence[int]] = None):
         if out not in ("logits", "labels", "overlay"):
             raise StswinHipError(f"out must be 'logits', 'labels' or 'overlay', got {out!r}")
         if pixel_format not in PIXEL_FORMATS:
@@ -427,6 +443,26 @@ class VideoSegmenter:
         self._classes = model.classifier[-1].out_channels
         if report is not None and not 1 <= self._classes <= 64:
             raise StswinHipError(f"report: the model has {self._classes} classes, hip.label_moments takes 1 .. 64")
+        self.instances, self.connectivity, self.instance_skip = instances, connectivity, None
+        if instances is None:
+            if connectivity != 8 or instance_skip is not None:
+                raise StswinHipError("connectivity and instance_skip belong to instances=K")
+        else:
+            if report is None:
+                raise StswinHipError("instances=K splits the instrument report: it needs report='frame' or 'deferred'")
+            if isinstance(instances, bool) or not isinstance(instances, int) or not 1 <= instances <= 1024:
+                raise StswinHipError(f"instances must be None or an int 1 .. 1024, got {instances!r}")
+            if isinstance(connectivity, bool) or connectivity not in (4, 8):
+                raise StswinHipError(f"connectivity must be 4 or 8, got {connectivity!r}")
+            if instance_skip is None:     # the background, or the remapped ignore label: what `transparent` defaults to
+                instance_skip = (self._classes - 1,) if protocol == "cadis" else (0,)
+            instance_skip = tuple(instance_skip)
+            if any(isinstance(c, bool) or not isinstance(c, int) or not 0 <= c <= 63 for c in instance_skip):
+                raise StswinHipError(f"instance_skip holds classes 0 .. 63, got {instance_skip!r}")
+            self.instance_skip = instance_skip
+        self._cc_map = self._cc_ws = None     # instances: the component map and the workspace, kept across steps (a captured graph uses them)
+        self._cc_retired = []                 # ... and the smaller ones they replaced
+        self._ilog = self._ilog_total = None  # report="deferred", instances: int64 [capacity][K][12] and int32 [capacity], rows as _rlog's
         self._rlog = None                 # report="deferred": int64 [capacity][nc][10] on the device, one row per released frame ...
         self._rlog_rows = []              # ... and per row (sequence ordinal, frame index) on the host
         self._rseq = 0
@@ -558,14 +594,66 @@ class VideoSegmenter:
         fill kernel, also when captured: no memset node); None without report."""
         if self.report is None:
             return None
-        return hip.label_moments(labels, self._classes)
+        mom = hip.label_moments(labels, self._classes)
+        if self.instances is None:
+            return mom
+        return (mom,) + self._components(labels)
+
+    def _components(self, labels: torch.Tensor):
+        """instances: (rows int64 [B][K][12], total int32 [B]) of a step's labels [B][*out_size], the launches of hip.label_components
+        behind the moments launch.  The component map and the workspace are the segmenter's own and only ever grow, so the warm-up
+        frames allocate what the captured step then uses; rows and total are fresh per step (under capture: the graph's buffers)."""
+        B, H, W = labels.shape
+        need = hip.label_components_scratch(B, H, W)
+        if self._cc_ws is None or self._cc_ws.numel() < need or self._cc_map.numel() < B * H * W:
+            self._cc_retired += [t for t in (self._cc_ws, self._cc_map) if t is not None]     # (a captured step may still use them)
+            self._cc_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            self._cc_map = torch.empty(B * H * W, dtype=torch.int32, device=self.device)
+        rows = torch.empty(B, self.instances, 12, dtype=torch.int64, device=self.device)
+        total = torch.empty(B, dtype=torch.int32, device=self.device)
+        hip.label_components(labels, self._classes, self.connectivity, self.instance_skip, self.instances,
+                             out=(self._cc_map[:B * H * W].view(B, H, W), rows, total), workspace=self._cc_ws)
+        return rows, total
+
+    def instance_report(self, names: Optional[Sequence[str]] = None):
+        """report="deferred" with instances=K: one download of the instance log -> utils.instruments.InstanceReport (min_area as given
+        to the segmenter) over every frame released since reset_metrics(), rows ordered by sequence and frame as instrument_report()'s.
+        names: the caller's class names, for as_rows()."""
+        if self.report != "deferred" or self.instances is None:
+            raise StswinHipError("instance_report() belongs to report='deferred' with instances=K")
+        from .utils.instruments import InstanceReport
+        n = len(self._rlog_rows)
+        rows = self._ilog[:n].cpu().numpy() if n else np.zeros((0, self.instances, 12), dtype=np.int64)
+        total = self._ilog_total[:n].cpu().numpy() if n else np.zeros(0, dtype=np.int32)
+        order = sorted(range(n), key=lambda r: self._rlog_rows[r])     # the log is in release order
+        where = [self._rlog_rows[r] for r in order]
+        try:
+            return InstanceReport.from_rows(rows[order], total[order], self.out_size or (0, 0), self.min_area, names,
+                                            [f for _, f in where], [s for s, _ in where])
+        except ValueError as e:
+            raise StswinHipError(f"instance_report: {e}") from e
 
     def _reported(self, frame: int, result, moments: Optional[torch.Tensor]):
         """A frame's result with its moments [1][nc][10]: report="frame" appends them (on the device), "deferred" logs them."""
+        inst = None
+        if isinstance(moments, tuple):        # instances: (moments, rows [1][K][12], total [1])
+            moments, inst = moments[0], moments[1:]
         if self.report == "frame":
-            return result + (moments[0],) if isinstance(result, tuple) else (result, moments[0])
+            extra = (moments[0],) if inst is None else (moments[0], inst[0][0], inst[1][0])
+            return result + extra if isinstance(result, tuple) else (result,) + extra
         if self.report == "deferred":
             n = len(self._rlog_rows)
+            if inst is not None:
+                if self._ilog is None or n == self._ilog.shape[0]:      # (grows with the moments log: the same rows)
+                    cap = max(64, 2 * n)
+                    grown = torch.zeros(cap, *inst[0].shape[1:], dtype=torch.int64, device=self.device)
+                    grown_total = torch.zeros(cap, dtype=torch.int32, device=self.device)
+                    if n:
+                        grown[:n].copy_(self._ilog[:n])
+                        grown_total[:n].copy_(self._ilog_total[:n])
+                    self._ilog, self._ilog_total = grown, grown_total
+                self._ilog[n:n + 1].copy_(inst[0])
+                self._ilog_total[n:n + 1].copy_(inst[1])
             if self._rlog is None or n == self._rlog.shape[0]:      # (a device copy; the log doubles when full)
                 grown = torch.zeros(max(64, 2 * n), *moments.shape[1:], dtype=torch.int64, device=self.device)
                 if n:
@@ -836,7 +924,7 @@ class VideoSegmenter:
         if labels is not None:
             if moments is None:
                 return [(g, labels[b]) for b, g in enumerate(clips)]
-            return [(g, self._reported(g, labels[b], moments[b:b + 1])) for b, g in enumerate(clips)]
+            return [(g, self._reported(g, labels[b], _rows_of(moments, b))) for b, g in enumerate(clips)]
         res = []
         mom = {}                              # report: the moments of the labels that final() last saw, per clip
 
@@ -865,6 +953,13 @@ class VideoSegmenter:
         if self.report is not None:
             res = [(g, self._reported(g, r, mom[b])) for b, (g, r) in enumerate(res)]
         return res
+
+
+def _rows_of(moments, b: int):
+    """Clip b's part [1][...] of a step's moments, or of its (moments, rows, total) with instances."""
+    if isinstance(moments, tuple):
+        return tuple(m[b:b + 1] for m in moments)
+    return moments[b:b + 1]
 
 
 def _clone(r):
