@@ -33,7 +33,10 @@ extern "C" {
 #define STSWIN_GF_CS_PARTIAL 32768 /* `colsum` is a caller-owned fp32 table [2*ceil(M/256)][N] instead of the fp32 [N] accumulator: row b
                                     * receives (plain stores, no atomics) the column sums of output rows 128b..128b+127;
                                     * stswin_cs_reduce then adds the rows into the bias gradient.  M/128 same-address atomics cost
-                                    * 38 us on a 65536 x 512 output; the table + reduce cost ~5 us (N % 4 == 0). */
+                                    * 38 us on a 65536 x 512 output; the table + reduce cost ~5 us (N % 4 == 0).
+                                    * Kernels whose workgroups own 256 output rows without a 128-row split (the 256x64 tiles, the 256x256 ring with
+                                    * the fp32 LDS epilogue) store the sum of rows 256t..256t+255 in row 2t and zero in row 2t+1: every consumer
+                                    * (stswin_cs_reduce, stswin_cs_group_reduce) works on whole 256-row tiles (tests/test_hip_gemm_nt_contract.py). */
 #define STSWIN_GF_CS_SQ 65536   /* with STSWIN_GF_CS_PARTIAL: `colsum` holds TWO planes [2][2*ceil(M/256)][N]; the second receives the column
                                   * sums of SQUARES of the same values: the BatchNorm statistics of a convolution output come out of
                                   * the convolution (stswin_cs_group_reduce + stswin_bn_finalize with x = NULL) */

@@ -141,7 +141,11 @@ DEVI f32x2 phi_poly2(f32x2 x) {
   f32x2 q = {C[7], C[7]};
 #pragma unroll
   for (int i = 6; i >= 0; --i) q = __builtin_elementwise_fma(q, s, (f32x2){C[i], C[i]});
-  return __builtin_elementwise_fma(z, q, (f32x2){0.5f, 0.5f});
+  // The float32 coefficients give Q(1) = 0.5000007 in this FMA chain, not 0.5: unclamped, Phi was 1.0000007 / -7.2e-7 beyond the clamp of z
+  // and gelu(x) > 0 for x < -3.96.  Clamping the result makes the tails exact whatever the coefficients round to; it changes a value only
+  // where the polynomial left [0, 1] (tests/test_gemm_ref.py evaluates this function in float32 from this file's coefficients).
+  const f32x2 r = __builtin_elementwise_fma(z, q, (f32x2){0.5f, 0.5f});
+  return __builtin_elementwise_min(__builtin_elementwise_max(r, (f32x2){0.f, 0.f}), (f32x2){1.f, 1.f});
 }
 DEVI f32x2 gelu_fast2(f32x2 x) { return x * phi_poly2(x); }
 DEVI f32x2 dgelu_fast2(f32x2 x) {

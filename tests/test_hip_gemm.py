@@ -35,18 +35,29 @@ def test_gemm_nt_plain_and_bias(dtype, m, n, k):
     hip.gemm_nt(a.cuda(), w.cuda(), out8, M=m, bias=bias.cuda(), flags=hip.GF_WAVES4)      # 4-wave variant, same result
     assert torch.equal(out8, out)
     if dtype == torch.bfloat16:
+        # GF_MID / GF_HALF / GF_NOPIPE select kernels of STSWIN_TUNING builds; the product library ignores the flags and these runs take
+        # the default dispatch (what it is per shape: tests/test_hip_gemm_nt_contract.py) - each run says which of the two it was
+        tuning = bool(hip.load().stswin_tuning_build())
+        last = hip.load().stswin_last_variant
         outb = torch.full((m, n), float("nan"), dtype=dtype, device="cuda")
         hip.gemm_nt(a.cuda(), w.cuda(), outb, M=m, bias=bias.cuda(), flags=hip.GF_BIG)     # 256x256 4-stage-ring kernel
+        ring = last(0)
+        assert ring in (hip.VAR_NT_RING256_REGEPI, hip.VAR_NT_RING256_LDSEPI)
         _close(outb, F.linear(a.float(), w.float(), bias), dtype, "big kernel")
+        hip.gemm_nt(a.cuda(), w.cuda(), outb, M=m, bias=bias.cuda())
+        default = last(0)
         outb.fill_(float("nan"))
         hip.gemm_nt(a.cuda(), w.cuda(), outb, M=m, bias=bias.cuda(), flags=hip.GF_MID)     # 256x128 3-stage-ring kernel
-        _close(outb, F.linear(a.float(), w.float(), bias), dtype, "mid kernel")
+        assert last(0) == (hip.VAR_NT_MID if tuning else default)
+        _close(outb, F.linear(a.float(), w.float(), bias), dtype, "mid kernel" if tuning else "GF_MID ignored: default dispatch")
         outb.fill_(float("nan"))
         hip.gemm_nt(a.cuda(), w.cuda(), outb, M=m, bias=bias.cuda(), flags=hip.GF_HALF)    # 256x128 ping-pong ring kernel
-        _close(outb, F.linear(a.float(), w.float(), bias), dtype, "half ping-pong kernel")
+        assert last(0) == (hip.VAR_NT_RING256x128_PP if tuning else default)
+        _close(outb, F.linear(a.float(), w.float(), bias), dtype, "half ping-pong kernel" if tuning else "GF_HALF ignored: default dispatch")
         outb.fill_(float("nan"))
         hip.gemm_nt(a.cuda(), w.cuda(), outb, M=m, bias=bias.cuda(), flags=hip.GF_BIG | hip.GF_NOPIPE)
-        _close(outb, F.linear(a.float(), w.float(), bias), dtype, "big kernel, no ping-pong")
+        assert last(0) == (hip.VAR_NT_RING256_NOPIPE if tuning else ring)
+        _close(outb, F.linear(a.float(), w.float(), bias), dtype, "big kernel, no ping-pong" if tuning else "GF_NOPIPE ignored: the forced ring kernel")
     out32 = torch.zeros(m, n, device="cuda")
     hip.gemm_nt(a.cuda(), w.cuda(), out32, M=m, flags=hip.GF_OUT_F32)
     hip.gemm_nt(a.cuda(), w.cuda(), out32, M=m, flags=hip.GF_OUT_F32 | hip.GF_ACCUM)
