@@ -625,6 +625,34 @@ int stswin_label_components(const unsigned char* labels /*[n][H][W]*/, int* comp
 /* the geometry of stswin_label_components (the tests place their shapes around it): which = 0, 1: height and width in pixels of the
  * tile a workgroup labels in LDS (16, 64), 2: the pixels of a raster chunk of the numbering pass (2048); anything else: -1. */
 int stswin_label_components_geometry(int which);
+/* ---- instances followed from frame to frame (stswincl_amd/utils/instruments.py InstanceTracker, VideoSegmenter(tracks=True)): the
+ * components, rows [K][12] and total [1] of ONE frame of stswin_label_components, frame after frame in frame order -> ids int32 [K],
+ * started int32 [1].  Instance j takes part if j < min(total, K) and rows[j][2] >= min_area.  ov[i][j] = the pixels that carry ordinal
+ * i in the previous call's map and j in this one (-1 and ordinals >= K count nowhere), u = area[i] + area[j] - ov.  A previous
+ * participant i and a current one j are a candidate iff ov > 0, their classes are equal (same_class = 1; 0 drops the condition) and
+ * 1000 ov >= min_iou u (min_iou in thousandths, 0 .. 1000; int64).  (i, j) is preferred to (i', j') iff ov u' > ov' u (int64
+ * products), then smaller i, then smaller j.  Repeatedly the most preferred candidate whose i and j are both unmatched is matched and
+ * ids[j] = the id of i; the participants left over take next, next + 1, ... in ascending j; every other entry of ids is -1; started =
+ * next after the call.  Bit for bit InstanceTracker.update, whatever the order of execution (integer atomics only).
+ * state: caller-owned, 16-byte aligned, >= stswin_track_state_bytes(H, W, K) bytes, int32 words:
+ *   [0] next id   [1] listed pairs   [2], [3] unused   cls[K], area[K], id[K] of the previous call's instances (cls -1: takes no part)
+ *   ov[K][K]   list[K K]: the pairs i << 10 | j with ov != 0   then, 16-byte aligned, the previous map [H W], padded with -1 to a
+ *   multiple of four pixels.
+ * stswin_track_reset (one fill kernel, no memset node) starts a sequence: next = 0, no previous instances, a previous map of -1, ov
+ * and the list cleared; a state must be reset once before its first use.  stswin_track_instances is two launches: the overlap pass
+ * reads both maps once (16-byte loads; 4-byte loads of a `components` that is only 4-byte aligned), writes the current map over the
+ * previous one in the same pass and counts the pairs on chip, one global atomic per distinct pair and workgroup; one workgroup then
+ * matches, writes ids, started and the new state and clears what the overlap pass counted.  No allocation, no synchronisation,
+ * `total` is read on the device only (graph-capturable); no kernel waits on another workgroup.  The buffers must not overlap (the host
+ * wrapper checks).
+ * Errors, before anything is launched: -1840 H or W <= 0 or > 16384; -1841 K outside 1 .. 1024 (stswin_track_state_bytes returns
+ * these two as well); -1842 a NULL pointer; -1843 state_bytes too small or state not 16-byte aligned; -1844 components, total, ids or
+ * started not 4-byte aligned, or rows not 8-byte aligned; -1845 min_iou outside 0 .. 1000, same_class not 0 or 1, or min_area < 1. */
+long stswin_track_state_bytes(int H, int W, int K);
+int stswin_track_reset(void* state, long state_bytes, int H, int W, int K, void* stream);
+int stswin_track_instances(const int* components /*[H][W]*/, const long long* rows /*[K][12]*/, const int* total /*[1]*/, void* state,
+                           long state_bytes, int H, int W, int K, int min_iou, int same_class, int min_area, int* ids /*[K]*/,
+                           int* started /*[1]*/, void* stream);
 /* ---- frames as a video source delivers them (stswincl_amd/utils/yuv.py, VideoSegmenter(pixel_format=..., out_format="nv12")):
  * stswin_yuv_to_rgb makes the HWC RGB frame uint8 [n][Hs][Ws][3] that stswin_frame_ingest and stswin_labels_overlay read,
  * stswin_rgb_to_nv12 turns such a frame into NV12.  Hs (NV12) and Ws are even.

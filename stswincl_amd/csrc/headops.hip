@@ -2044,6 +2044,275 @@ extern "C" int stswin_label_components(const unsigned char* labels, int* compone
   return 0;
 }
 
+// Instances followed from frame to frame (stswincl_amd/utils/instruments.py, InstanceTracker, states the result;
+// VideoSegmenter(tracks=True)).  The state buffer, in int32 words (include/stswin_hip.h states it too):
+//   [0] next id  [1] number of listed pairs  [2], [3] unused      cls[K], area[K], id[K] of the previous frame's instances (cls -1: takes
+//   no part)      ov[K][K] overlap counts      list[K K] the pairs (i << 10 | j) whose count is non-zero      the previous component map,
+//   16-byte aligned and padded with -1 to a multiple of four pixels
+// Between two calls ov is all zero and the list is empty: a call's matching launch clears exactly the entries its overlap launch made.
+//   1 trk_overlap_kernel  a thread reads four consecutive pixels of both maps (16-byte loads; 4-byte loads of a `components` that is
+//                         not 16-byte aligned, and of a map's last pixels), writes the current ones over the previous ones and counts
+//                         the pairs (i, j), both < K: equal pairs of its pixels in registers, the threads whose four pixels are one
+//                         pair across the wave per distinct pair, everything into the workgroup's LDS table (slot j % TRK_SLOTS
+//                         belongs to the first pair that claims it, others go to the global counter directly), which ends as one
+//                         global atomic per slot in use.  The add that finds a zero lists the pair.  A wave without a pair - all
+//                         background on either side - only copies.
+//   2 trk_match_kernel    one workgroup: drops the listed pairs that are no candidates, then rounds of "every pair that is the most
+//                         preferred remaining candidate of both its row and its column is matched" (compare-and-swap on the row's and
+//                         the column's best in LDS; a turn ends or goes on against a strictly better pair) until a round matches
+//                         nothing - the fixed point is the greedy matching - then ids, births by a scan over the ordinals, the new
+//                         state, and the clearing of ov and the list.
+// Integer atomics only: exact, whatever the order.  No kernel uses scratch memory or waits on another workgroup.
+#define TRK_THREADS 256
+#define TRK_VPT 2
+#define TRK_SLOTS 64
+#define TRK_MAXK 1024
+
+struct TrkLayout {
+  long cls, area, ids, ov, list, map, words;
+};
+static inline TrkLayout trk_layout(int H, int W, int K) {
+  TrkLayout l;
+  const long KK = (long)K * K;
+  l.cls = 4, l.area = 4 + (long)K, l.ids = 4 + 2L * K, l.ov = 4 + 3L * K;
+  l.list = l.ov + KK;
+  l.map = (l.list + KK + 3) & ~3L;
+  l.words = l.map + (((long)H * W + 3) & ~3L);
+  return l;
+}
+
+__global__ __launch_bounds__(TRK_THREADS) void trk_reset_kernel(int* __restrict__ s, long cls, long area, long ids, long ov, long map, long words) {
+  for (long i = (long)blockIdx.x * TRK_THREADS + threadIdx.x; i < words; i += (long)gridDim.x * TRK_THREADS)
+    s[i] = (i >= cls && i < area) || (i >= ids && i < ov) || i >= map ? -1 : 0;
+}
+
+__device__ __forceinline__ void trk_global(int* ov, int* list, int* npairs, int K, int key, unsigned c) {
+  const int old = atomicAdd(ov + (long)(key >> 10) * K + (key & 1023), (int)c);
+  if (old == 0) {                                         // (at most K K distinct pairs: the list of a reset state cannot overflow)
+    const int at = atomicAdd(npairs, 1);
+    if ((unsigned)at < (unsigned)(K * K)) list[at] = key;
+  }
+}
+
+__device__ __forceinline__ void trk_add(int* tag, unsigned* cnt, int* ov, int* list, int* npairs, int K, int key, unsigned c) {
+  const int slot = key & (TRK_SLOTS - 1);
+  int owner = ((volatile int*)tag)[slot];
+  if (owner == -1) {
+    owner = atomicCAS(&tag[slot], -1, key);
+    if (owner == -1) owner = key;
+  }
+  if (owner == key) atomicAdd(&cnt[slot], c);
+  else trk_global(ov, list, npairs, K, key, c);
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(TRK_THREADS) void trk_overlap_kernel(const int* __restrict__ cur, int* __restrict__ prev, int* ov, int* list,
+                                                                  int* npairs, long HW, int K) {
+  __shared__ int tag[TRK_SLOTS];
+  __shared__ unsigned cnt[TRK_SLOTS];
+  if (threadIdx.x < TRK_SLOTS) tag[threadIdx.x] = -1, cnt[threadIdx.x] = 0u;
+  __syncthreads();
+  const long nvec = (HW + 3) >> 2;
+  const int lane = (int)threadIdx.x & 63;
+#pragma unroll
+  for (int it = 0; it < TRK_VPT; ++it) {
+    const long v = ((long)blockIdx.x * TRK_VPT + it) * TRK_THREADS + threadIdx.x;
+    int4 c = make_int4(-1, -1, -1, -1), p = c;
+    if (v < nvec) {
+      const long p0 = 4 * v;
+      p = *reinterpret_cast<const int4*>(prev + p0);           // (the state's map is padded: in range)
+      if (VEC && p0 + 4 <= HW) {
+        c = *reinterpret_cast<const int4*>(cur + p0);
+      } else {
+        if (p0 < HW) c.x = cur[p0];
+        if (p0 + 1 < HW) c.y = cur[p0 + 1];
+        if (p0 + 2 < HW) c.z = cur[p0 + 2];
+        if (p0 + 3 < HW) c.w = cur[p0 + 3];
+      }
+      *reinterpret_cast<int4*>(prev + p0) = c;                 // (each pixel's old value was read by this thread; the padding stays -1)
+    }
+    const unsigned uk = (unsigned)K;
+    const int k0 = (unsigned)p.x < uk && (unsigned)c.x < uk ? (p.x << 10) | c.x : -1;
+    const int k1 = (unsigned)p.y < uk && (unsigned)c.y < uk ? (p.y << 10) | c.y : -1;
+    const int k2 = (unsigned)p.z < uk && (unsigned)c.z < uk ? (p.z << 10) | c.z : -1;
+    const int k3 = (unsigned)p.w < uk && (unsigned)c.w < uk ? (p.w << 10) | c.w : -1;
+    if (__ballot((k0 & k1 & k2 & k3) >= 0) == 0ull) continue;            // (wave-uniform) no pair in the wave's 256 pixels
+    const bool full = k0 >= 0 && k0 == k1 && k1 == k2 && k2 == k3;
+    if (!full) {                                                          // runs of equal pairs, left to right
+      int rk = k0;
+      unsigned rc = 1u;
+      if (k1 == rk) ++rc;
+      else {
+        if (rk >= 0) trk_add(tag, cnt, ov, list, npairs, K, rk, rc);
+        rk = k1, rc = 1u;
+      }
+      if (k2 == rk) ++rc;
+      else {
+        if (rk >= 0) trk_add(tag, cnt, ov, list, npairs, K, rk, rc);
+        rk = k2, rc = 1u;
+      }
+      if (k3 == rk) ++rc;
+      else {
+        if (rk >= 0) trk_add(tag, cnt, ov, list, npairs, K, rk, rc);
+        rk = k3, rc = 1u;
+      }
+      if (rk >= 0) trk_add(tag, cnt, ov, list, npairs, K, rk, rc);
+    }
+    unsigned long long todo = __ballot(full);                             // the threads of one pair, pair by pair (wave-uniform)
+    while (todo) {
+      const int first = __ffsll((long long)todo) - 1;
+      const int k = __builtin_amdgcn_readlane(k0, first);
+      const unsigned long long m = __ballot(full && k0 == k);
+      todo &= ~m;
+      if (lane == first) trk_add(tag, cnt, ov, list, npairs, K, k, 4u * (unsigned)__popcll(m));
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < TRK_SLOTS && tag[threadIdx.x] >= 0 && cnt[threadIdx.x]) trk_global(ov, list, npairs, K, tag[threadIdx.x], cnt[threadIdx.x]);
+}
+
+// a (overlap oa, union ua, key ka) is preferred to b: oa / ua > ob / ub as an exact int64 product (< 2^57), then the smaller (i, j)
+__device__ __forceinline__ bool trk_better(long oa, long ua, int ka, long ob, long ub, int kb) {
+  const long l = oa * ub, r = ob * ua;
+  return l > r || (l == r && ka < kb);
+}
+
+// the pair `key` becomes *best unless a better one holds it.  Each turn ends or continues against a strictly better holder.
+__device__ __forceinline__ void trk_contend(int* best, int key, long o, long u, const int* ov, const int* parea, const int* carea, int K) {
+  int cur = *(volatile int*)best;
+  for (;;) {
+    if (cur >= 0) {
+      const int ci = cur >> 10, cj = cur & 1023;
+      const long co = ov[(long)ci * K + cj];
+      if (!trk_better(o, u, key, co, (long)parea[ci] + carea[cj] - co, cur)) return;
+    }
+    const int old = atomicCAS(best, cur, key);
+    if (old == cur) return;
+    cur = old;
+  }
+}
+
+__global__ __launch_bounds__(TRK_THREADS) void trk_match_kernel(const long long* __restrict__ rows, const int* __restrict__ total, int* hdr,
+                                                                int* pcls, int* parea, int* pids, int* ov, int* list, int K, int min_iou,
+                                                                int same_class, int min_area, int* __restrict__ ids, int* __restrict__ started) {
+  __shared__ int ccls[TRK_MAXK], carea[TRK_MAXK], rbest[TRK_MAXK], cbest[TRK_MAXK], rmatch[TRK_MAXK], cmatch[TRK_MAXK];
+  __shared__ unsigned red[4];
+  __shared__ int changed;
+  const int tid = (int)threadIdx.x;
+  const int n = min(max(total[0], 0), K), np = min(max(hdr[1], 0), K * K), next = hdr[0];
+  for (int j = tid; j < K; j += TRK_THREADS) {
+    const long long a = j < n ? rows[(long)j * 12 + 2] : 0ll;
+    const bool part = j < n && a >= (long long)min_area;
+    ccls[j] = part ? (int)rows[(long)j * 12] : -1;
+    carea[j] = part ? (int)a : 0;
+    rmatch[j] = cmatch[j] = -1;
+  }
+  __syncthreads();
+  for (int p = tid; p < np; p += TRK_THREADS) {               // the listed pairs that are no candidates leave the list
+    const int key = list[p], i = key >> 10, j = key & 1023;
+    if (key < 0 || i >= K || j >= K) {                         // (only a state that was never reset holds such a key)
+      list[p] = -1;
+      continue;
+    }
+    const long o = ov[(long)i * K + j];
+    const int pc = pcls[i], cc = ccls[j];
+    bool ok = pc >= 0 && cc >= 0 && (!same_class || pc == cc);
+    if (ok) ok = 1000l * o >= (long)min_iou * ((long)parea[i] + carea[j] - o);
+    if (!ok) ov[(long)i * K + j] = 0, list[p] = -1;
+  }
+  for (;;) {
+    for (int j = tid; j < K; j += TRK_THREADS) rbest[j] = cbest[j] = -1;
+    if (tid == 0) changed = 0;
+    __syncthreads();
+    for (int p = tid; p < np; p += TRK_THREADS) {
+      const int key = list[p];
+      if (key < 0) continue;
+      const int i = key >> 10, j = key & 1023;
+      if (rmatch[i] >= 0 || cmatch[j] >= 0) {                 // matched, or beaten for good: done with
+        ov[(long)i * K + j] = 0, list[p] = -1;
+        continue;
+      }
+      const long o = ov[(long)i * K + j], u = (long)parea[i] + carea[j] - o;
+      trk_contend(rbest + i, key, o, u, ov, parea, carea, K);
+      trk_contend(cbest + j, key, o, u, ov, parea, carea, K);
+    }
+    __syncthreads();
+    for (int p = tid; p < np; p += TRK_THREADS) {
+      const int key = list[p];
+      if (key < 0) continue;
+      const int i = key >> 10, j = key & 1023;
+      if (rbest[i] == key && cbest[j] == key) rmatch[i] = j, cmatch[j] = i, changed = 1;
+    }
+    __syncthreads();
+    const int c = changed;
+    __syncthreads();
+    if (!c) break;
+  }
+  for (int p = tid; p < np; p += TRK_THREADS) {               // (none is left at the fixed point; the state's invariant does not rest on it)
+    const int key = list[p];
+    if (key >= 0) ov[(long)(key >> 10) * K + (key & 1023)] = 0, list[p] = -1;
+  }
+  unsigned carry = 0;                                          // births: the unmatched participants, numbered in ascending j
+  for (int base = 0; base < K; base += TRK_THREADS) {
+    const int j = base + tid;
+    const int m = j < K ? cmatch[j] : -1;
+    const unsigned b = j < K && ccls[j] >= 0 && m < 0 ? 1u : 0u;
+    const unsigned incl = cc_block_scan(b, red);
+    if (j < K) rbest[j] = m >= 0 ? pids[m] : b ? next + (int)(carry + incl - 1u) : -1;
+    carry += red[0] + red[1] + red[2] + red[3];
+  }
+  __syncthreads();                                             // (every previous id has been read)
+  for (int j = tid; j < K; j += TRK_THREADS) {
+    const int id = rbest[j];
+    ids[j] = id;
+    pids[j] = id, pcls[j] = ccls[j], parea[j] = carea[j];
+  }
+  if (tid == 0) hdr[0] = next + (int)carry, hdr[1] = 0, started[0] = next + (int)carry;
+}
+
+extern "C" long stswin_track_state_bytes(int H, int W, int K) {
+  if (H <= 0 || W <= 0 || H > 16384 || W > 16384) return -1840;
+  if (K < 1 || K > TRK_MAXK) return -1841;
+  return 4 * trk_layout(H, W, K).words;
+}
+
+extern "C" int stswin_track_reset(void* state, long state_bytes, int H, int W, int K, void* stream) {
+  if (H <= 0 || W <= 0 || H > 16384 || W > 16384) return -1840;
+  if (K < 1 || K > TRK_MAXK) return -1841;
+  if (state == nullptr) return -1842;
+  const TrkLayout l = trk_layout(H, W, K);
+  if (state_bytes < 4 * l.words || ((uintptr_t)state & 15)) return -1843;
+  long blocks = (l.words + TRK_THREADS - 1) / TRK_THREADS;
+  if (blocks > 2048) blocks = 2048;
+  hipLaunchKernelGGL(trk_reset_kernel, dim3((unsigned)blocks), dim3(TRK_THREADS), 0, (hipStream_t)stream, reinterpret_cast<int*>(state), l.cls,
+                     l.area, l.ids, l.ov, l.map, l.words);
+  STSWIN_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int stswin_track_instances(const int* components, const long long* rows, const int* total, void* state, long state_bytes, int H,
+                                      int W, int K, int min_iou, int same_class, int min_area, int* ids, int* started, void* stream) {
+  if (H <= 0 || W <= 0 || H > 16384 || W > 16384) return -1840;
+  if (K < 1 || K > TRK_MAXK) return -1841;
+  if (components == nullptr || rows == nullptr || total == nullptr || state == nullptr || ids == nullptr || started == nullptr) return -1842;
+  const TrkLayout l = trk_layout(H, W, K);
+  if (state_bytes < 4 * l.words || ((uintptr_t)state & 15)) return -1843;
+  if (((uintptr_t)components & 3) || ((uintptr_t)rows & 7) || ((uintptr_t)total & 3) || ((uintptr_t)ids & 3) || ((uintptr_t)started & 3)) return -1844;
+  if (min_iou < 0 || min_iou > 1000 || (same_class != 0 && same_class != 1) || min_area < 1) return -1845;
+  hipStream_t st = (hipStream_t)stream;
+  int* s = reinterpret_cast<int*>(state);
+  const long HW = (long)H * W, nvec = (HW + 3) >> 2;
+  const unsigned blocks = (unsigned)((nvec + TRK_THREADS * TRK_VPT - 1) / (TRK_THREADS * TRK_VPT));       // <= 2^17
+  if ((uintptr_t)components & 15)
+    hipLaunchKernelGGL(trk_overlap_kernel<false>, dim3(blocks), dim3(TRK_THREADS), 0, st, components, s + l.map, s + l.ov, s + l.list, s + 1, HW, K);
+  else
+    hipLaunchKernelGGL(trk_overlap_kernel<true>, dim3(blocks), dim3(TRK_THREADS), 0, st, components, s + l.map, s + l.ov, s + l.list, s + 1, HW, K);
+  hipLaunchKernelGGL(trk_match_kernel, dim3(1), dim3(TRK_THREADS), 0, st, rows, total, s, s + l.cls, s + l.area, s + l.ids, s + l.ov, s + l.list,
+                     K, min_iou, same_class, min_area, ids, started);
+  STSWIN_CHECK_LAUNCH();
+  return 0;
+}
+
 // Frames as a video source delivers them (stswincl_amd/utils/yuv.py states the arithmetic): NV12 or UYVY -> the HWC RGB frame that
 // stswin_frame_ingest and stswin_labels_overlay read, and RGB -> NV12.  matrix int32 [3][4]: out_c = clamp((m[c][0] t0 + m[c][1] t1 +
 // m[c][2] t2 + m[c][3]) >> 14, 0, 255) in int32 (|sum| < 2^25).  A thread owns YUV_PPT = 8 (wide body) or 2 (byte body) consecutive

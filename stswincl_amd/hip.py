@@ -1591,7 +1591,83 @@ def label_components(labels: torch.Tensor, nc: int, connectivity: int = 8, skip=
     return tuple(out)
 
 
-YUV_NV12, YUV_UYVY = 0, 1                     # stswin_yuv_to_rgb's `format` (plain integers in the header's comment, not #defines)
+def _track_shape(what: str, H, W, K) -> None:
+    for name, v in (("H", H), ("W", W)):
+        if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= 16384:
+            raise StswinHipError(f"{what}: {name} must be an int 1 .. 16384, got {v!r}")
+    if isinstance(K, bool) or not isinstance(K, int) or not 1 <= K <= 1024:
+        raise StswinHipError(f"{what}: K must be an int 1 .. 1024, got {K!r}")
+
+
+class TrackState:
+    """What hip.track_instances keeps between the frames of a sequence, for maps [H][W] and K instances: one device buffer of
+    stswin_track_state_bytes(H, W, K) bytes (the previous map, classes, areas and ids, the next id and the overlap counts; layout:
+    include/stswin_hip.h).  Made reset: the first frame it sees is all births from id 0.  reset() starts the next sequence (a fill
+    kernel on the current stream, graph-capturable)."""
+
+    def __init__(self, H: int, W: int, K: int, device):
+        _track_shape("TrackState", H, W, K)
+        device = _device(device)
+        if device.type != "cuda":
+            raise StswinHipError("TrackState: the state lives on the GPU (utils.instruments.InstanceTracker is the numpy definition)")
+        self.H, self.W, self.K, self.device = H, W, K, device
+        self.bytes = int(load().stswin_track_state_bytes(H, W, K))
+        if self.bytes < 0:
+            raise StswinHipError(f"TrackState: stswin_track_state_bytes({H}, {W}, {K}) failed with code {self.bytes}")
+        self.buffer = torch.empty(self.bytes, dtype=torch.uint8, device=device)      # (the caching allocator aligns to 512 bytes)
+        self.reset()
+
+    def reset(self) -> None:
+        with torch.cuda.device(self.device):
+            _check(load().stswin_track_reset(_p(self.buffer), self.bytes, self.H, self.W, self.K, _stream()), "track_reset")
+
+
+def track_instances(components: torch.Tensor, rows: torch.Tensor, total: torch.Tensor, state: TrackState, min_iou: int = 100,
+                    same_class: bool = True, min_area: int = 1, out=None):
+    """One frame of hip.label_components - components int32 [H][W], rows int64 [K][12], total int32 [1] (or a scalar tensor) - and the
+    TrackState of its sequence -> (ids int32 [K], started int32 [1]): ids[j] is the track of instance j, carried over from the
+    instance of the previous call that it overlaps best (intersection over union >= min_iou thousandths, the same class unless
+    same_class=False, greedy in order of preference), a new id next, next + 1, ... for the participants left over, -1 for
+    instances below min_area and rows past min(total, K); started = the ids handed out since the state's reset().  Frames go in
+    frame order.  utils.instruments.InstanceTracker is the numpy definition, matched bit for bit.  out: the pair (ids, started),
+    written in full; with it the call allocates nothing, and it never synchronises (graph-capturable).  Two launches
+    (include/stswin_hip.h, stswin_track_instances)."""
+    if not isinstance(state, TrackState):
+        raise StswinHipError(f"track_instances: state must be a hip.TrackState, got {type(state).__name__}")
+    H, W, K, dev = state.H, state.W, state.K, state.device
+    want = [("components", components, torch.int32, (H, W)), ("rows", rows, torch.int64, (K, 12)), ("total", total, torch.int32, None)]
+    if out is not None:
+        if not isinstance(out, (tuple, list)) or len(out) != 2:
+            raise StswinHipError("track_instances: out must be the pair (ids, started)")
+        want += [("ids", out[0], torch.int32, (K,)), ("started", out[1], torch.int32, (1,))]
+    for what, t, dt, shape in want:
+        ok = isinstance(t, torch.Tensor) and t.dtype == dt and t.is_contiguous() and t.device == dev
+        if ok:
+            ok = tuple(t.shape) == shape if shape is not None else t.numel() == 1 and t.dim() <= 1
+        if not ok:
+            got = f"{t.dtype} {tuple(t.shape)} on {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__
+            form = "".join(f"[{d}]" for d in shape) if shape is not None else "[1]"
+            raise StswinHipError(f"track_instances: {what} must be contiguous {dt} {form} on {dev} (a state of {H} x {W} maps and "
+                                 f"{K} instances), got {got}")
+    if isinstance(min_iou, bool) or not isinstance(min_iou, int) or not 0 <= min_iou <= 1000:
+        raise StswinHipError(f"track_instances: min_iou must be an int 0 .. 1000 (thousandths), got {min_iou!r}")
+    if not isinstance(same_class, bool):
+        raise StswinHipError(f"track_instances: same_class must be a bool, got {same_class!r}")
+    if isinstance(min_area, bool) or not isinstance(min_area, int) or min_area < 1:
+        raise StswinHipError(f"track_instances: min_area must be an int >= 1, got {min_area!r}")
+    if out is None:
+        out = (torch.empty(K, dtype=torch.int32, device=dev), torch.empty(1, dtype=torch.int32, device=dev))
+    bufs = (("components", components), ("rows", rows), ("total", total), ("state", state.buffer), ("ids", out[0]), ("started", out[1]))
+    for i, (wa, a) in enumerate(bufs):
+        for wb, b in bufs[i + 1:]:
+            if _same_memory(a, b):
+                raise StswinHipError(f"track_instances: {wb} shares memory with {wa}")
+    _check(load().stswin_track_instances(_p(components), _p(rows), _p(total), _p(state.buffer), state.bytes, H, W, K, min_iou,
+                                         int(same_class), min_area, _p(out[0]), _p(out[1]), _stream()), "track_instances")
+    return tuple(out)
+
+
+YUV_NV12, YUV_UYVY = 0, 1                    # stswin_yuv_to_rgb's `format` (plain integers in the header's comment, not #defines)
 YUV_REPLICATE, YUV_LINEAR = 0, 1               # ... and its `chroma`
 _YUV_FORMATS = {"nv12": YUV_NV12, "uyvy": YUV_UYVY}
 _YUV_CHROMA = {"replicate": YUV_REPLICATE, "linear": YUV_LINEAR}

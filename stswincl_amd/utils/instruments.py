@@ -14,6 +14,9 @@ label_components splits the classes into connected instances (hip.label_componen
 integers per frame and instance - its class, its first pixel y * W + x in raster order, then the ten above over its pixels - and
 InstanceReport reads those rows as InstrumentReport reads the class rows, by the same arithmetic.
 
+InstanceTracker gives the instances of consecutive frames a common id (hip.track_instances, VideoSegmenter(tracks=True)) by greedy
+matching on intersection over union in integers, and TrackReport reads the ids beside an InstanceReport: one entry per track.
+
 This module ships no dataset's class names: pass `names` if the rows of a log should carry them."""
 from __future__ import annotations
 
@@ -324,4 +327,150 @@ class InstanceReport:
                 row["angle"] = float(self.angle[r, i])
                 row["axes"] = tuple(float(v) for v in self.axes[r, i])
                 out.append(row)
+        return out
+
+
+class InstanceTracker:
+    """Identity of the instances of label_components from frame to frame: the numpy statement of what hip.track_instances computes,
+    in integers throughout, matched bit for bit (VideoSegmenter(tracks=True)).
+
+    update(components int32 [H][W], rows int64 [K][12], total) -> (ids int32 [K], started): an instance takes part if its ordinal is
+    < min(total, K) and its area rows[i][2] >= min_area.  With P the previous frame's participants (class cp, area ap, id tp) and C
+    this frame's (cc, ac): ov[i][j] = the pixels that carry ordinal i in the previous map and j in this one (-1 and ordinals >= K count
+    nowhere), u = ap[i] + ac[j] - ov.  (i, j) is a candidate iff ov > 0, cp[i] == cc[j] (dropped with same_class=False) and
+    1000 ov >= min_iou u (min_iou: thousandths, 0 .. 1000).  (i, j) is preferred to (i', j') iff ov u' > ov' u, then smaller i, then
+    smaller j: a strict total order.  Repeatedly the most preferred candidate whose i and j are both unmatched is matched and ids[j] =
+    tp[i]; the participants left over take next, next + 1, ... in ascending j; every other entry of ids is -1.  started is `next` after
+    the frame: the number of tracks begun since reset().  An instance that was absent for a frame comes back under a new id."""
+
+    def __init__(self, K: int, min_iou: int = 100, same_class: bool = True, min_area: int = 1):
+        if isinstance(K, bool) or int(K) != K or not 1 <= K <= 1024:
+            raise ValueError(f"InstanceTracker: K is 1 .. 1024, got {K!r}")
+        if isinstance(min_iou, bool) or int(min_iou) != min_iou or not 0 <= min_iou <= 1000:
+            raise ValueError(f"InstanceTracker: min_iou is an integer 0 .. 1000 (thousandths), got {min_iou!r}")
+        if isinstance(min_area, bool) or int(min_area) != min_area or min_area < 1:
+            raise ValueError(f"InstanceTracker: min_area is an integer >= 1, got {min_area!r}")
+        self.K, self.min_iou, self.same_class, self.min_area = int(K), int(min_iou), bool(same_class), int(min_area)
+        self.reset()
+
+    def reset(self) -> None:
+        self.next = 0
+        self._map = None                  # the previous frame's component map ...
+        self._part = {}                   # ... and its participants: ordinal -> (class, area, id)
+
+    def update(self, components, rows, total):
+        comp = np.asarray(components)
+        rw = np.asarray(rows)
+        K = self.K
+        if comp.ndim != 2 or comp.dtype.kind not in "iu" or min(comp.shape) < 1:
+            raise ValueError(f"InstanceTracker: components are integers [H][W], got {comp.dtype} {comp.shape}")
+        if rw.shape != (K, INSTANCE_ROW) or rw.dtype.kind not in "iu":
+            raise ValueError(f"InstanceTracker: rows are integers [{K}][{INSTANCE_ROW}], got {rw.dtype} {rw.shape}")
+        if self._map is not None and self._map.shape != comp.shape:
+            raise ValueError(f"InstanceTracker: a {comp.shape} map after {self._map.shape} ones (reset() starts a new sequence)")
+        total = int(np.asarray(total).reshape(-1)[0])
+        comp = comp.astype(np.int64)
+        n = min(max(total, 0), K)
+        cur = {j: (int(rw[j, 0]), int(rw[j, 2])) for j in range(n) if int(rw[j, 2]) >= self.min_area}
+        cand = []
+        if self._map is not None and self._part and cur:
+            both = (self._map >= 0) & (self._map < K) & (comp >= 0) & (comp < K)
+            pairs, counts = np.unique(self._map[both] * K + comp[both], return_counts=True)
+            for key, ov in zip(pairs.tolist(), counts.tolist()):
+                i, j = divmod(key, K)
+                if i not in self._part or j not in cur:
+                    continue
+                cp, ap, _ = self._part[i]
+                cc, ac = cur[j]
+                u = ap + ac - ov
+                if (cp == cc or not self.same_class) and 1000 * ov >= self.min_iou * u:
+                    cand.append((ov, u, i, j))
+        ids = np.full(K, -1, dtype=np.int32)
+        used_i, used_j = set(), set()
+        while True:                           # the most preferred candidate whose i and j are both still free (Python integers: exact)
+            best = None
+            for c in cand:
+                if c[2] in used_i or c[3] in used_j:
+                    continue
+                if best is None or c[0] * best[1] > best[0] * c[1] or (c[0] * best[1] == best[0] * c[1] and c[2:] < best[2:]):
+                    best = c
+            if best is None:
+                break
+            used_i.add(best[2])
+            used_j.add(best[3])
+            ids[best[3]] = self._part[best[2]][2]
+        for j in sorted(cur):
+            if j not in used_j:
+                ids[j] = self.next
+                self.next += 1
+        self._map = comp
+        self._part = {j: (cur[j][0], cur[j][1], int(ids[j])) for j in cur}
+        return ids, self.next
+
+
+class TrackReport:
+    """The instance report with identities: from an InstanceReport and the ids of InstanceTracker (hip.track_instances,
+    VideoSegmenter(tracks=True).track_report()), row for row:
+
+      ids      int32 [frames][K]    as given: the track of instance i of row-frame r, -1 where it takes no part
+      started  int64 [frames]       the tracks begun in the row's sequence up to and including its frame
+      tracks   list of dict         one per (sequence, id), in that order: sequence, track, class (at first sight), first and last
+                                    (frame indices), seen (frames), frames int64 [seen], centroids float64 [seen][2] and areas
+                                    int64 [seen], by the InstanceReport's own arithmetic
+
+    Ids start at 0 with every sequence."""
+
+    def __init__(self):
+        self.report = self.ids = self.started = None
+        self.tracks: List[dict] = []
+
+    @classmethod
+    def from_ids(cls, instance_report: InstanceReport, ids, started) -> "TrackReport":
+        rep = instance_report
+        if not isinstance(rep, InstanceReport) or rep.present is None:
+            raise ValueError("TrackReport: the first argument is an InstanceReport (InstanceReport.from_rows)")
+        n, K = rep.present.shape
+        idv = np.asarray(ids)
+        st = np.asarray(started).reshape(-1)
+        if idv.ndim == 1 and n == 1:
+            idv = idv[None]
+        if idv.shape != (n, K) or idv.dtype.kind not in "iu":
+            raise ValueError(f"TrackReport: ids are integers [{n}][{K}], got {idv.dtype} {idv.shape}")
+        if st.shape != (n,) or st.dtype.kind not in "iu":
+            raise ValueError(f"TrackReport: started holds one integer per frame ({n}), got {st.dtype} {st.shape}")
+        if ((idv >= 0) != rep.present).any():
+            raise ValueError("TrackReport: ids and the report disagree on which instances are present (another min_area?)")
+        out = cls()
+        out.report, out.ids, out.started = rep, idv.astype(np.int32), st.astype(np.int64)
+        seen = {}
+        for r in range(n):
+            for i in np.nonzero(rep.present[r])[0]:
+                key = (rep.sequences[r], int(idv[r, i]))
+                t = seen.get(key)
+                if t is None:
+                    t = seen[key] = {"sequence": key[0], "track": key[1], "class": int(rep.cls[r, i]), "first": rep.frames[r],
+                                     "frames": [], "centroids": [], "areas": []}
+                t["frames"].append(rep.frames[r])
+                t["centroids"].append(rep.centroid[r, i])
+                t["areas"].append(int(rep.area[r, i]))
+        for key in sorted(seen):
+            t = seen[key]
+            t["last"], t["seen"] = t["frames"][-1], len(t["frames"])
+            t["frames"] = np.asarray(t["frames"], dtype=np.int64)
+            t["centroids"] = np.asarray(t["centroids"], dtype=np.float64).reshape(-1, 2)
+            t["areas"] = np.asarray(t["areas"], dtype=np.int64)
+            out.tracks.append(t)
+        return out
+
+    def __len__(self) -> int:
+        return len(self.report)
+
+    def as_rows(self) -> List[dict]:
+        """The InstanceReport's rows, each with its "track"."""
+        out = self.report.as_rows()
+        k = 0
+        for r in range(len(self.report)):
+            for i in np.nonzero(self.report.present[r])[0]:
+                out[k]["track"] = int(self.ids[r, i])
+                k += 1
         return out

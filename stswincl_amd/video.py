@@ -374,6 +374,24 @@ class VideoSegmenter:
     reset_metrics(), with instrument_report()'s order, sequence ordinals and reset() / reset_metrics() behaviour.  instances=None:
     every result, launch and captured graph is what it is without the keyword.
 
+    tracks=True (needs instances=K; track_iou=100 in thousandths, track_same_class=True; min_area is the segmenter's): the instances
+    followed from frame to frame, so that a shaft keeps one id while its ordinal changes.  Behind the component launches of a frame run
+    the two of hip.track_instances (utils.instruments.InstanceTracker defines the result): an instance takes the id of the instance of
+    the previous frame it overlaps best, a new id otherwise; ids restart at 0 with every sequence (reset() resets the state with a fill
+    kernel), and an instance that was absent for a frame comes back under a new id.  The tracker takes frames in frame order, which is
+    not the order of release (endovis18 releases 0, 1, 4, 2, 5, 3, 6, ..., cadis 0, 1, 2, 5, 3, 6, 4, 7, ..., a batch in the planner's
+    order): a released frame whose predecessor has not been tracked is parked - its component map copied into a pool that grows as
+    needed, its rows and total kept - and tracked in the push that releases the predecessor.  report="frame": a result gains ids,
+    int32 [K] on the device, as its last element (-1: no instance or below min_area).  For a parked frame - frames 4 and 5 of an
+    endovis18 sequence, 5 and 6 of a cadis one, more with batch > 1 - the tensor is handed out at release holding -2 and is written
+    on the stream when the frame is tracked, at the latest by finish(): no synchronisation, read it after that push.  Under graph=True
+    the captured steady step holds the tracker's launches behind the component launches and ids is a view of the graph's buffer until
+    the next push, as rows and total are; the state is allocated by the warm-up frames; with ground truth the tracker follows the
+    eager component launches after the replay.  report="deferred": ids and the running number of tracks go into a device log beside
+    the instance log (a parked frame's row when it is tracked); track_report(names=None) downloads once and returns
+    utils.instruments.TrackReport over every frame released since reset_metrics(), in instance_report()'s order.  tracks=False:
+    every result, launch and captured graph is what it is without the keyword.
+
     Runs under torch.no_grad().  Refuses (StswinHipError): a model in train mode, a model or frames not on the GPU, a frame size
     that differs from the earlier frames'."""
 
@@ -382,7 +400,8 @@ class VideoSegmenter:
                  palette=None, alpha: int = 128, transparent: Optional[Sequence[int]] = None, edge_alpha: Optional[int] = 255,
                  gt_table=None, scores: str = "frame", pixel_format: str = "rgb", yuv_standard: str = "bt709", full_range: bool = False,
                  chroma: str = "replicate", out_format: str = "rgb", report: Optional[str] = None, min_area: int = 1,
-                 instances: Optional[int] = None, connectivity: int = 8, instance_skip: Optional[Sequence[int]] = None):
+                 instances: Optional[int] = None, connectivity: int = 8, instance_skip: Optional[Sequence[int]] = None,
+                 tracks: bool = False, track_iou: int = 100, track_same_class: bool = True):
         if out not in ("logits", "labels", "overlay"):
             raise StswinHipError(f"out must be 'logits', 'labels' or 'overlay', got {out!r}")
         if pixel_format not in PIXEL_FORMATS:
@@ -460,6 +479,23 @@ class VideoSegmenter:
             if any(isinstance(c, bool) or not isinstance(c, int) or not 0 <= c <= 63 for c in instance_skip):
                 raise StswinHipError(f"instance_skip holds classes 0 .. 63, got {instance_skip!r}")
             self.instance_skip = instance_skip
+        if not isinstance(tracks, bool):
+            raise StswinHipError(f"tracks must be a bool, got {tracks!r}")
+        if not tracks and (track_iou != 100 or track_same_class is not True):
+            raise StswinHipError("track_iou and track_same_class belong to tracks=True")
+        if tracks:
+            if instances is None:
+                raise StswinHipError("tracks=True follows the instances from frame to frame: it needs instances=K")
+            if isinstance(track_iou, bool) or not isinstance(track_iou, int) or not 0 <= track_iou <= 1000:
+                raise StswinHipError(f"track_iou must be an int 0 .. 1000 (thousandths), got {track_iou!r}")
+            if not isinstance(track_same_class, bool):
+                raise StswinHipError(f"track_same_class must be a bool, got {track_same_class!r}")
+        self.tracks, self.track_iou, self.track_same_class = tracks, track_iou, track_same_class
+        self._trk_state = None                # tracks: the hip.TrackState of the running sequence (made by the first tracked frame) ...
+        self._trk_next = 0                    # ... the next frame it takes, and the released frames that wait for it:
+        self._trk_parked = {}                 # frame -> [component map (a copy), rows [K][12], total [1], ids, started, log row or None]
+        self._trk_pool = []                   # ... whose map copies are taken from and given back to this pool
+        self._tlog = self._tlog_started = None    # report="deferred", tracks: int32 [capacity][K] and int32 [capacity], rows as _rlog's
         self._cc_map = self._cc_ws = None     # instances: the component map and the workspace, kept across steps (a captured graph uses them)
         self._cc_retired = []                 # ... and the smaller ones they replaced
         self._ilog = self._ilog_total = None  # report="deferred", instances: int64 [capacity][K][12] and int32 [capacity], rows as _rlog's
@@ -521,6 +557,11 @@ class VideoSegmenter:
         if self._rseq_logged:             # report="deferred": likewise, with its own ordinal
             self._rseq += 1
             self._rseq_logged = False
+        if self._trk_state is not None:   # tracks: ids restart at 0 (a fill kernel on the stream), what is parked is dropped
+            self._trk_state.reset()
+        self._trk_pool += [p[0] for p in self._trk_parked.values()]
+        self._trk_parked = {}
+        self._trk_next = 0
 
     def reset_metrics(self) -> None:
         """Clear what an evaluation pools and reset() keeps: the confusion matrix (protocol="cadis"), the score log and its sequence
@@ -589,7 +630,7 @@ class VideoSegmenter:
         except ValueError as e:
             raise StswinHipError(f"instrument_report: {e}") from e
 
-    def _moments(self, labels: torch.Tensor) -> Optional[torch.Tensor]:
+    def _moments(self, labels: torch.Tensor, tracked: bool = False) -> Optional[torch.Tensor]:
         """report: the moments int64 [B][nc][10] of a step's labels [B][*out_size], one launch behind the clearing of its buffer (a
         fill kernel, also when captured: no memset node); None without report."""
         if self.report is None:
@@ -597,7 +638,61 @@ class VideoSegmenter:
         mom = hip.label_moments(labels, self._classes)
         if self.instances is None:
             return mom
-        return (mom,) + self._components(labels)
+        inst = self._components(labels)
+        if tracked:                           # the graph's steady step: one frame, in frame order, the tracker's launches behind these
+            cc = self._cc_map[:labels[0].numel()].view(labels.shape[1:])
+            inst += tuple(t[None] for t in hip.track_instances(cc, inst[0][0], inst[1], self._trk_state, self.track_iou,
+                                                               self.track_same_class, self.min_area))
+        return (mom,) + inst
+
+    def _track(self, frame: int, cc: torch.Tensor, rows: torch.Tensor, total: torch.Tensor):
+        """tracks: (ids int32 [1][K], started int32 [1][1]) of a released frame whose component map `cc` [H][W], rows [K][12] and total
+        [1] have just been made.  The tracker takes frames in frame order: a frame whose predecessor has not been tracked yet is
+        parked - its map copied out of the segmenter's component map, ids handed out holding -2 - and tracked, with the frames that wait
+        on it, in the call that tracks the predecessor.  Launches on the stream only."""
+        K = self.instances
+        if self._trk_state is None or (self._trk_state.H, self._trk_state.W) != tuple(cc.shape):
+            self._trk_state = hip.TrackState(cc.shape[0], cc.shape[1], K, self.device)
+        ids = torch.empty(K, dtype=torch.int32, device=self.device)
+        started = torch.empty(1, dtype=torch.int32, device=self.device)
+        if frame != self._trk_next:
+            keep = self._trk_pool.pop() if self._trk_pool and self._trk_pool[-1].shape == cc.shape else torch.empty_like(cc)
+            keep.copy_(cc)
+            ids.fill_(-2)
+            started.fill_(-2)
+            self._trk_parked[frame] = [keep, rows, total, ids, started, None]
+            return ids[None], started[None]
+        self._track_now(cc, rows, total, ids, started)
+        while self._trk_next in self._trk_parked:
+            keep, prows, ptotal, pids, pstarted, log_row = self._trk_parked.pop(self._trk_next)
+            self._track_now(keep, prows, ptotal, pids, pstarted)
+            self._trk_pool.append(keep)
+            if log_row is not None:
+                self._tlog[log_row].copy_(pids)
+                self._tlog_started[log_row:log_row + 1].copy_(pstarted)
+        return ids[None], started[None]
+
+    def _track_now(self, cc, rows, total, ids, started) -> None:
+        hip.track_instances(cc, rows, total, self._trk_state, self.track_iou, self.track_same_class, self.min_area, out=(ids, started))
+        self._trk_next += 1
+
+    def track_report(self, names: Optional[Sequence[str]] = None):
+        """report="deferred" with tracks=True: one download of the track log -> utils.instruments.TrackReport over instance_report(names):
+        every frame released since reset_metrics(), in its order and with its sequence ordinals; ids restart at 0 with every sequence."""
+        if self.report != "deferred" or not self.tracks:
+            raise StswinHipError("track_report() belongs to report='deferred' with tracks=True")
+        if self._trk_parked:
+            raise StswinHipError("track_report(): released frames still wait for their predecessors (finish() the sequence first)")
+        from .utils.instruments import TrackReport
+        rep = self.instance_report(names)
+        n = len(self._rlog_rows)
+        ids = self._tlog[:n].cpu().numpy() if n else np.zeros((0, self.instances), dtype=np.int32)
+        started = self._tlog_started[:n].cpu().numpy() if n else np.zeros(0, dtype=np.int32)
+        order = sorted(range(n), key=lambda r: self._rlog_rows[r])     # the log is in release order
+        try:
+            return TrackReport.from_ids(rep, ids[order], started[order])
+        except ValueError as e:
+            raise StswinHipError(f"track_report: {e}") from e
 
     def _components(self, labels: torch.Tensor):
         """instances: (rows int64 [B][K][12], total int32 [B]) of a step's labels [B][*out_size], the launches of hip.label_components
@@ -636,10 +731,10 @@ class VideoSegmenter:
     def _reported(self, frame: int, result, moments: Optional[torch.Tensor]):
         """A frame's result with its moments [1][nc][10]: report="frame" appends them (on the device), "deferred" logs them."""
         inst = None
-        if isinstance(moments, tuple):        # instances: (moments, rows [1][K][12], total [1])
+        if isinstance(moments, tuple):        # instances: (moments, rows [1][K][12], total [1]), with tracks: ... ids [1][K], started [1][1])
             moments, inst = moments[0], moments[1:]
         if self.report == "frame":
-            extra = (moments[0],) if inst is None else (moments[0], inst[0][0], inst[1][0])
+            extra = (moments[0],) if inst is None else (moments[0], inst[0][0], inst[1][0]) + ((inst[2][0],) if self.tracks else ())
             return result + extra if isinstance(result, tuple) else (result,) + extra
         if self.report == "deferred":
             n = len(self._rlog_rows)
@@ -654,6 +749,20 @@ class VideoSegmenter:
                     self._ilog, self._ilog_total = grown, grown_total
                 self._ilog[n:n + 1].copy_(inst[0])
                 self._ilog_total[n:n + 1].copy_(inst[1])
+                if self.tracks:
+                    if self._tlog is None or n == self._tlog.shape[0]:
+                        cap = max(64, 2 * n)
+                        grown = torch.zeros(cap, self.instances, dtype=torch.int32, device=self.device)
+                        grown_started = torch.zeros(cap, dtype=torch.int32, device=self.device)
+                        if n:
+                            grown[:n].copy_(self._tlog[:n])
+                            grown_started[:n].copy_(self._tlog_started[:n])
+                        self._tlog, self._tlog_started = grown, grown_started
+                    if frame in self._trk_parked:         # its row is written when it is tracked
+                        self._trk_parked[frame][5] = n
+                    else:
+                        self._tlog[n:n + 1].copy_(inst[2])
+                        self._tlog_started[n:n + 1].copy_(inst[3][0])
             if self._rlog is None or n == self._rlog.shape[0]:      # (a device copy; the log doubles when full)
                 grown = torch.zeros(max(64, 2 * n), *moments.shape[1:], dtype=torch.int64, device=self.device)
                 if n:
@@ -695,7 +804,10 @@ class VideoSegmenter:
 
     def finish(self) -> List[Tuple[int, object]]:
         self._check_train()
-        return self._run_all(self.planner.finish())
+        res = self._run_all(self.planner.finish())
+        if self._trk_parked:
+            raise StswinHipError(f"internal error: frames {sorted(self._trk_parked)} were released and never tracked")
+        return res
 
     def segment_sequence(self, frames, gt=None) -> list:
         self.reset()
@@ -806,7 +918,8 @@ class VideoSegmenter:
             j += k
         return out
 
-    def _compute(self, img: Optional[torch.Tensor], table: torch.Tensor, B: int, n_new: int, labels: bool = False, frames=None):
+    def _compute(self, img: Optional[torch.Tensor], table: torch.Tensor, B: int, n_new: int, labels: bool = False, frames=None,
+                 tracked: bool = False):
         """ResNet on the new frames' images, clip assembly, Swin / ASPP / head: -> logits (B, nc, H, W), and with labels = True the
         labels (B, *out_size), or for out="overlay" the overlay (B, *out_size, 3) on `frames`, one uint8 [1][Hs][Ws][3] per clip, and
         with report the labels' moments (B, nc, 10), taken before the overlay launch.
@@ -833,7 +946,7 @@ class VideoSegmenter:
         logits = m.forward_frame_tokens(clips, h, w, self.size[0], self.size[1])
         if labels:
             lab = self._labels(logits)
-            mom = self._moments(lab)
+            mom = self._moments(lab, tracked)
             return logits, lab if self._table is None else self._overlay(lab, frames), mom
         return logits, None, None
 
@@ -885,6 +998,11 @@ class VideoSegmenter:
     def _run_graph(self, st: Step, want_labels: bool):
         src, r = self._frames.pop(st.new[0])
         g = self._g
+        tracked = self.tracks and want_labels     # the tracker's launches are part of the step: the steady state is in frame order
+        if tracked:
+            if self._trk_state is None or self._trk_parked or self._trk_next != st.new[0]:
+                raise StswinHipError(f"internal error: the steady step of frame {st.new[0]} found the tracker at frame {self._trk_next}")
+            self._trk_next += 1
         if g is None or g[5] != want_labels:
             # first steady-state step (or first of the other output form): one eager warm-up on the static buffers (on a side stream,
             # as graph.py's GraphedStep does), then the capture; this step's result is the warm-up's
@@ -898,7 +1016,7 @@ class VideoSegmenter:
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
-                logits, labels, moments = self._compute(self._static_image(raw, u8), table, 1, 1, want_labels, frames)
+                logits, labels, moments = self._compute(self._static_image(raw, u8), table, 1, 1, want_labels, frames, tracked)
                 logits = logits.clone()
             torch.cuda.current_stream().wait_stream(side)
             torch.cuda.synchronize()
@@ -906,7 +1024,7 @@ class VideoSegmenter:
             graph = torch.cuda.CUDAGraph()
             autocast = torch.is_autocast_enabled()
             with torch.cuda.graph(graph):
-                out, out_labels, out_moments = self._compute(self._static_image(raw, u8), table, 1, 1, want_labels, frames)
+                out, out_labels, out_moments = self._compute(self._static_image(raw, u8), table, 1, 1, want_labels, frames, tracked)
             self._g = (graph, raw, table, out, out_labels, want_labels, autocast, u8, out_moments)
             return logits, labels, moments, False, frames
         graph, raw, table, out, out_labels, _, autocast, u8, out_moments = g
@@ -924,12 +1042,20 @@ class VideoSegmenter:
         if labels is not None:
             if moments is None:
                 return [(g, labels[b]) for b, g in enumerate(clips)]
+            if self.tracks and len(moments) == 3:         # (five: the graph's steady step, tracked inside it)
+                hw = self.out_size[0] * self.out_size[1]
+                parts = [_rows_of(moments, b) for b in range(len(clips))]
+                moments = [m + self._track(g, self._cc_map[b * hw:(b + 1) * hw].view(self.out_size), m[1][0], m[2])
+                           for b, (g, m) in enumerate(zip(clips, parts))]
+                return [(g, self._reported(g, labels[b], moments[b])) for b, g in enumerate(clips)]
             return [(g, self._reported(g, labels[b], _rows_of(moments, b))) for b, g in enumerate(clips)]
         res = []
         mom = {}                              # report: the moments of the labels that final() last saw, per clip
 
         def final(b, lab):                    # labels (1, *out_size) -> the result form of out="labels" | "overlay"
             mom[b] = self._moments(lab)       # (before the overlay launch: it reads the labels)
+            if self.tracks:                   # (the component map is this clip's until the next clip's labels are made)
+                mom[b] += self._track(clips[b], self._cc_map[:lab[0].numel()].view(lab.shape[1:]), mom[b][1][0], mom[b][2])
             return lab[0] if self._table is None else self._overlay(lab, frames[b:b + 1])[0]
 
         for b, g in enumerate(clips):
