@@ -21,7 +21,7 @@ What is exact and what is ours:
     clips, stored as (255 * clip(u / 255. + n, 0, 1)).astype('uint8')): for a byte that is clamp(u + floor(255 n), 0, 255), an integer
     offset with the law of noise_thresholds(), exact.  The stream is ours: Philox4x32-10 keyed by ClipParams.noise and counted by the
     byte index (the reference's is unseeded and never repeats).  Off unless p_noise is given; the reference's CaDIS value is 0.5.
-  * the conversion: float32(u / 255.) (CaDIS: video.cadis_value_table() per plane) and the label table (CaDIS: 255 -> class_num - 1).
+  * the conversion: float32(u / 255.) (CaDIS: frames.cadis_value_table() per plane) and the label table (CaDIS: 255 -> class_num - 1).
 """
 from __future__ import annotations
 
@@ -33,13 +33,13 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import hip, video
+from . import hip
+from .frames import PRECISION_BITS, Pinned, T, bilinear_coeffs, check_rule, value_lut
 from .hip import StswinHipError
 
-T = video.T
 AB_BITS = 10            # fraction bits of the rotation's position tables
 INTER_BITS = 5          # fraction bits of a source position
-_ONE = 1 << video._PRECISION_BITS
+_ONE = 1 << PRECISION_BITS
 
 
 @dataclass
@@ -100,7 +100,7 @@ def axis_tables(in_size: int, out_size: int, start: int, count: int, ksize: int)
         bounds[valid, 0], bounds[valid, 1], coef[valid, 0] = src, 1, _ONE
         near[valid] = src
     else:
-        b, k = video.bilinear_coeffs(in_size, out_size)
+        b, k = bilinear_coeffs(in_size, out_size)
         if k.shape[1] > ksize:
             raise StswinHipError(f"scale {in_size} -> {out_size} needs {k.shape[1]} taps, the tables hold {ksize}")
         bounds[valid] = b[src]
@@ -227,7 +227,7 @@ class ClipAugmenter:
                  source: Optional[Sequence[int]] = None, p_hflip: Optional[float] = None, p_vflip: Optional[float] = None,
                  p_bc: Optional[float] = None, brightness_limit: float = 0.2, contrast_limit: float = 0.2, p_rotate: float = 0.5,
                  rotate_limit: float = 90.0, p_noise: float = 0.0, noise_var: float = 0.001):
-        video._check_rule(protocol)
+        check_rule(protocol)
         self.protocol = protocol
         self.crop = (int(crop[0]), int(crop[1]))
         self.source = (int(source[0]), int(source[1])) if source is not None else self.crop
@@ -253,7 +253,7 @@ class ClipAugmenter:
         self._ws = {}
         self._luts = {}
         self._thr = {}
-        self._pinned = video._Pinned()
+        self._pinned = Pinned()
 
     # ----------------------------------------------------------------------------------------- parameters
     def params(self, long_size: int, x1: int, y1: int, hflip: bool = False, vflip: bool = False, alpha: Optional[float] = None,
@@ -384,7 +384,7 @@ class ClipAugmenter:
             lab = np.arange(256, dtype=np.int64)
             if self.protocol == "cadis":
                 lab[255] = self.class_num - 1                      # CATA_new_512.py:237
-            t = self._luts[key] = (video._lut(dev, self.protocol), torch.from_numpy(lab).to(dev))
+            t = self._luts[key] = (value_lut(dev, self.protocol), torch.from_numpy(lab).to(dev))
         return t
 
     def _thresholds(self, dev):
@@ -430,7 +430,7 @@ class ClipAugmenter:
 
     def _upload(self, B: int, dev, params):
         """Build both stages' tables and copy them to the device table in one asynchronous copy from pinned memory.  Calls may follow
-        each other without a synchronise: video._Pinned rotates staging buffers and, before it rewrites one, waits for the event
+        each other without a synchronise: Pinned rotates staging buffers and, before it rewrites one, waits for the event
         recorded behind the copy that last read it; the device table itself is rewritten in stream order, behind the launches of the
         earlier call that read it."""
         t1, _ = self.tables(params)

@@ -30,14 +30,14 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from .. import hip, video
+from .. import hip
+from ..frames import PRECISION_BITS, Pinned, T, bilinear_coeffs
 from ..augment import bilinear_ksize, nearest_index
 from ..hip import StswinHipError
 
-T = video.T
 VIEWS = 6
 MAX_KSIZE = 16          # taps per output index the library's tables hold (include/stswin_hip.h, stswin_contrast_views)
-_ONE = 1 << video._PRECISION_BITS
+_ONE = 1 << PRECISION_BITS
 _HEAD = 8
 
 # dataset.py:56-68: view k is transform[k] over four frames, stacked by append_img_1 oldest first.  Frames: 0 image, 1 .. 4 prev1 ..
@@ -63,7 +63,7 @@ def value_table(mean: Sequence[float] = (0.485, 0.456, 0.406), std: Sequence[flo
     """fp32 [3][256]: the value of byte u in plane c after ToTensor and Normalize, in fp32 steps evaluated with torch's CPU ops:
     ((float32(u) / float32(255)) - float32(mean[c])) / float32(std[c]).  ToTensor is `.to(float32).div(255)`, Normalize is
     `.sub_(mean).div_(std)` with fp32 mean / std tensors; torchvision is not a dependency, so this derivation is the definition.
-    NOT video.cadis_value_table(), which follows a float64 pipeline."""
+    NOT frames.cadis_value_table(), which follows a float64 pipeline."""
     u = torch.arange(256, dtype=torch.uint8).to(torch.float32).div(255)
     m = torch.as_tensor(list(mean), dtype=torch.float32)
     s = torch.as_tensor(list(std), dtype=torch.float32)
@@ -80,7 +80,7 @@ def _axis(length: int, out_size: int):
         idx = np.arange(out_size, dtype=np.int32)
         b, k, near = np.stack([idx, np.ones_like(idx)], 1), np.full((out_size, 1), _ONE, np.int32), idx
     else:
-        b, k = video.bilinear_coeffs(length, out_size)
+        b, k = bilinear_coeffs(length, out_size)
         near = nearest_index(length, out_size).astype(np.int32)
     for a in (b, k, near):
         a.setflags(write=False)
@@ -142,7 +142,7 @@ class ContrastViews:
         self.table = value_table(mean, std)
         self._ws = {}
         self._luts = {}
-        self._pinned = video._Pinned()
+        self._pinned = Pinned()
 
     # ----------------------------------------------------------------------------------------- parameters
     def _coord(self, i: int, j: int, h: int, w: int, hflip: bool, vflip: bool) -> np.ndarray:
@@ -310,7 +310,7 @@ class ContrastViews:
         tab = self.tables(params, frames.shape[1], labels.shape[1])
         images, masks = self._outputs(out, B, dev)
         ws = self._workspace(B, dev)
-        # one asynchronous copy from pinned memory; calls may follow each other without a synchronise (video._Pinned waits for the
+        # one asynchronous copy from pinned memory; calls may follow each other without a synchronise (Pinned waits for the
         # copy that last read a staging buffer before it rewrites it; the device table is rewritten in stream order)
         self._pinned.upload(tab, ws["table"])
         V = self.views * B

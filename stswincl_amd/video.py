@@ -32,24 +32,20 @@ over every frame of every sequence (stswin_upsample_argmax_cm; reset_metrics() c
 """
 from __future__ import annotations
 
-from collections import deque
+from collections import deque, namedtuple
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from . import hip
+from .frames import (CADIS_MEAN, CADIS_SIZE, CADIS_STD, RULES, T, VALUE_TABLE, bilinear_coeffs, cadis_value_table,  # noqa: F401
+                     PRECISION_BITS as _PRECISION_BITS, Pinned as _Pinned, check_rule as _check_rule, tables as _tables, value_lut as _lut)
 from .hip import StswinHipError
+from .video_report import DeviceLog, ReportChain, Yield
 
-T = 4                   # frames per clip (the model asserts T == 4)
-RULES = ("endovis18", "cadis")
 PIXEL_FORMATS = ("rgb", "nv12", "uyvy")
 _FRAME_FORMS = {"rgb": "uint8 RGB [n][Hs][Ws][3]", "nv12": "uint8 NV12 [n][3 Hs / 2][Ws]", "uyvy": "uint8 UYVY [n][Hs][Ws][2]"}
-
-
-def _check_rule(rule: str) -> None:
-    if rule not in RULES:
-        raise StswinHipError(f"clip rule must be one of {RULES}, got {rule!r}")
 
 
 def clip_frames(f: int, t: int = T, rule: str = "endovis18") -> Tuple[int, ...]:
@@ -179,70 +175,6 @@ class ClipPlanner:
 
 
 # ----------------------------------------------------------------------------------------------- frame ingest
-# float32(u / 255.) of the reference (astype(float) / 255., then .float()): equal to the fp32 division u / 255.f for all 256 values,
-# not to u * (1 / 255.f) (126 differ)
-VALUE_TABLE = (np.arange(256, dtype=np.float64) / 255.).astype(np.float32)
-_PRECISION_BITS = 22
-
-# CaDIS (CATA_new_512.py:21-22, 228-229): float32 MEAN / STD arrays, `imgs / 255.` in float64, `(imgs - mean) / std` promoted to
-# float64, `.float()` at cata_test.py:125
-CADIS_MEAN = np.array([0.40789654, 0.44719302, 0.47026115], dtype=np.float32)
-CADIS_STD = np.array([0.28863828, 0.27408164, 0.27809835], dtype=np.float32)
-CADIS_SIZE = (540, 960)   # the CaDIS frames' size, which cata_test.py:129 resizes the logits back to
-
-
-def cadis_value_table() -> np.ndarray:
-    """fp32 [3][256]: the CaDIS value of byte u in RGB plane c, computed in float64 as the reference does, then cast."""
-    u = np.arange(256, dtype=np.float64) / 255.
-    return ((u[None, :] - CADIS_MEAN.astype(np.float64)[:, None]) / CADIS_STD.astype(np.float64)[:, None]).astype(np.float32)
-
-
-def bilinear_coeffs(in_size: int, out_size: int) -> Tuple[np.ndarray, np.ndarray]:
-    """Pillow's BILINEAR coefficients for one axis (libImaging/Resample.c precompute_coeffs + normalize_coeffs_8bpc), in float64:
-    -> (bounds int32 [out][2] = (first tap, taps), weights int32 [out][ksize] with 22 fraction bits)."""
-    scale = float(in_size) / out_size
-    fs = max(scale, 1.0)
-    support = fs                                            # the triangle filter's support is 1
-    ksize = int(np.ceil(support)) * 2 + 1
-    center = (np.arange(out_size, dtype=np.float64) + 0.5) * scale
-    xmin = np.maximum(np.trunc(center - support + 0.5), 0).astype(np.int64)
-    xmax = np.minimum(np.trunc(center + support + 0.5), in_size).astype(np.int64)
-    n = xmax - xmin
-    x = np.arange(ksize)
-    t = np.abs((x[None, :] + xmin[:, None] - center[:, None] + 0.5) * (1.0 / fs))
-    w = np.where((t < 1.0) & (x[None, :] < n[:, None]), 1.0 - t, 0.0)
-    ww = np.zeros(out_size)
-    for k in range(ksize):                                   # the sequential float64 sum of the C loop
-        ww += w[:, k]
-    w = np.where(ww[:, None] != 0.0, w / np.where(ww == 0.0, 1.0, ww)[:, None], w)
-    kk = np.trunc(np.where(w < 0, -0.5, 0.5) + w * (1 << _PRECISION_BITS)).astype(np.int32)
-    return np.stack([xmin, n], 1).astype(np.int32), np.ascontiguousarray(kk)
-
-
-_TABLES = {}            # (in, out, device) -> (bounds, weights) on the device
-_LUTS = {}
-
-
-def _tables(in_size: int, out_size: int, device):
-    key = (in_size, out_size, str(device))
-    tab = _TABLES.get(key)
-    if tab is None:
-        b, k = bilinear_coeffs(in_size, out_size)
-        assert int((b[:, 0] + b[:, 1]).max()) <= in_size and int(b[:, 0].min()) >= 0
-        tab = (torch.from_numpy(b).to(device), torch.from_numpy(k).to(device))
-        _TABLES[key] = tab
-    return tab
-
-
-def _lut(device, protocol: str = "endovis18"):
-    """The value table of a protocol on a device: a persistent tensor (a captured graph reads it)."""
-    key = (protocol, str(device))
-    t = _LUTS.get(key)
-    if t is None:
-        t = _LUTS[key] = torch.from_numpy(cadis_value_table() if protocol == "cadis" else VALUE_TABLE).to(device)
-    return t
-
-
 def ingest(frames: torch.Tensor, size: Tuple[int, int], out: Optional[torch.Tensor] = None, protocol: str = "endovis18") -> torch.Tensor:
     """uint8 RGB frames [n][Hs][Ws][3] on the GPU -> fp32 images [n][3][H][W] (the stem's input): PIL.Image.resize((W, H),
     Image.BILINEAR) bit for bit, then float32(u / 255.) (protocol="cadis": the per-plane cadis_value_table()).  One or two launches
@@ -259,30 +191,6 @@ def ingest(frames: torch.Tensor, size: Tuple[int, int], out: Optional[torch.Tens
 
 
 # ----------------------------------------------------------------------------------------------- the segmenter
-class _Pinned:
-    """Pinned host staging buffers for host -> device copies that do not block the host: a buffer is reused only after the copy
-    that last read it has run (its event)."""
-
-    def __init__(self, count: int = 4):
-        self.bufs = [None] * count
-        self.events = [None] * count
-        self.i = 0
-
-    def upload(self, arr: np.ndarray, dst: torch.Tensor) -> torch.Tensor:
-        i = self.i = (self.i + 1) % len(self.bufs)
-        if self.events[i] is not None:
-            self.events[i].synchronize()
-        flat = np.ascontiguousarray(arr).reshape(-1)
-        buf = self.bufs[i]
-        if buf is None or buf.numel() < flat.nbytes:
-            buf = self.bufs[i] = torch.empty(flat.nbytes, dtype=torch.uint8).pin_memory()
-        buf[:flat.nbytes].numpy().view(flat.dtype)[:] = flat
-        dst.view(torch.uint8).view(-1).copy_(buf[:flat.nbytes], non_blocking=True)
-        ev = self.events[i] = torch.cuda.Event()
-        ev.record()
-        return dst
-
-
 class VideoSegmenter:
     """Segment video sequences with an eval-mode TswinPlus, one result per frame, each frame's ResNet features computed once.
 
@@ -425,12 +333,6 @@ class VideoSegmenter:
             raise StswinHipError(f"scores must be 'frame' or 'deferred', got {scores!r}")
         if scores == "deferred" and protocol != "endovis18":
             raise StswinHipError("scores='deferred' belongs to protocol='endovis18' (protocol='cadis' pools its counts in confusion_matrix())")
-        if report not in (None, "frame", "deferred"):
-            raise StswinHipError(f"report must be None, 'frame' or 'deferred', got {report!r}")
-        if report is not None and out == "logits":
-            raise StswinHipError("report belongs to out='labels' and out='overlay' (the moments are taken over the label map)")
-        if isinstance(min_area, bool) or not isinstance(min_area, int) or min_area < 1:
-            raise StswinHipError(f"min_area must be an int >= 1, got {min_area!r}")
         self.model = model
         self._check_train()
         if any(not p.is_cuda for p in model.parameters()):
@@ -454,55 +356,12 @@ class VideoSegmenter:
                 raise StswinHipError(f"metric_classes must be 1 .. 64, got {self.metric_classes}")
         self._cm = None
         self.scores = scores
-        self._log = None                  # scores="deferred": int32 [capacity][3][nc] on the device, one row per scored frame ...
-        self._log_rows = []               # ... and per row (sequence ordinal, frame index) on the host
-        self._seq = 0
-        self._seq_logged = False
-        self.report, self.min_area = report, min_area
-        self._classes = model.classifier[-1].out_channels
-        if report is not None and not 1 <= self._classes <= 64:
-            raise StswinHipError(f"report: the model has {self._classes} classes, hip.label_moments takes 1 .. 64")
-        self.instances, self.connectivity, self.instance_skip = instances, connectivity, None
-        if instances is None:
-            if connectivity != 8 or instance_skip is not None:
-                raise StswinHipError("connectivity and instance_skip belong to instances=K")
-        else:
-            if report is None:
-                raise StswinHipError("instances=K splits the instrument report: it needs report='frame' or 'deferred'")
-            if isinstance(instances, bool) or not isinstance(instances, int) or not 1 <= instances <= 1024:
-                raise StswinHipError(f"instances must be None or an int 1 .. 1024, got {instances!r}")
-            if isinstance(connectivity, bool) or connectivity not in (4, 8):
-                raise StswinHipError(f"connectivity must be 4 or 8, got {connectivity!r}")
-            if instance_skip is None:     # the background, or the remapped ignore label: what `transparent` defaults to
-                instance_skip = (self._classes - 1,) if protocol == "cadis" else (0,)
-            instance_skip = tuple(instance_skip)
-            if any(isinstance(c, bool) or not isinstance(c, int) or not 0 <= c <= 63 for c in instance_skip):
-                raise StswinHipError(f"instance_skip holds classes 0 .. 63, got {instance_skip!r}")
-            self.instance_skip = instance_skip
-        if not isinstance(tracks, bool):
-            raise StswinHipError(f"tracks must be a bool, got {tracks!r}")
-        if not tracks and (track_iou != 100 or track_same_class is not True):
-            raise StswinHipError("track_iou and track_same_class belong to tracks=True")
-        if tracks:
-            if instances is None:
-                raise StswinHipError("tracks=True follows the instances from frame to frame: it needs instances=K")
-            if isinstance(track_iou, bool) or not isinstance(track_iou, int) or not 0 <= track_iou <= 1000:
-                raise StswinHipError(f"track_iou must be an int 0 .. 1000 (thousandths), got {track_iou!r}")
-            if not isinstance(track_same_class, bool):
-                raise StswinHipError(f"track_same_class must be a bool, got {track_same_class!r}")
+        classes = model.classifier[-1].out_channels
+        self._score_log = DeviceLog(self.device, {"counts": ((3, classes), torch.int32)})     # scores="deferred": a row per scored frame
+        self.chain = ReportChain(self.device, classes, protocol, out, report, min_area, instances, connectivity, instance_skip, tracks,
+                                 track_iou, track_same_class)
+        self.report, self.min_area, self.instances, self.connectivity, self.instance_skip = report, min_area, instances, connectivity, self.chain.instance_skip
         self.tracks, self.track_iou, self.track_same_class = tracks, track_iou, track_same_class
-        self._trk_state = None                # tracks: the hip.TrackState of the running sequence (made by the first tracked frame) ...
-        self._trk_next = 0                    # ... the next frame it takes, and the released frames that wait for it:
-        self._trk_parked = {}                 # frame -> [component map (a copy), rows [K][12], total [1], ids, started, log row or None]
-        self._trk_pool = []                   # ... whose map copies are taken from and given back to this pool
-        self._tlog = self._tlog_started = None    # report="deferred", tracks: int32 [capacity][K] and int32 [capacity], rows as _rlog's
-        self._cc_map = self._cc_ws = None     # instances: the component map and the workspace, kept across steps (a captured graph uses them)
-        self._cc_retired = []                 # ... and the smaller ones they replaced
-        self._ilog = self._ilog_total = None  # report="deferred", instances: int64 [capacity][K][12] and int32 [capacity], rows as _rlog's
-        self._rlog = None                 # report="deferred": int64 [capacity][nc][10] on the device, one row per released frame ...
-        self._rlog_rows = []              # ... and per row (sequence ordinal, frame index) on the host
-        self._rseq = 0
-        self._rseq_logged = False
         self._gt_table = None
         self._unmatched = None
         if gt_table is not None:
@@ -541,6 +400,11 @@ class VideoSegmenter:
         self._g = None
         self.reset()
 
+    @property
+    def captured(self) -> bool:
+        """graph=True: the steady step has been captured (later steady steps replay it)."""
+        return self._g is not None
+
     def _check_train(self):
         if self.model.training:
             raise StswinHipError("VideoSegmenter needs the model in eval mode (model.eval()): in train mode BatchNorm uses batch "
@@ -551,17 +415,8 @@ class VideoSegmenter:
         self._frames = {}                 # frame index -> (uint8 tensor [k][Hs][Ws][3] (or raw nv12 / uyvy), GPU or CPU, row) until its ResNet pass
         self._kept = {}                   # out="overlay": frame index -> GPU uint8 [1][Hs][Ws][3] from its ResNet pass until its clip's result
         self._gt = {}
-        if self._seq_logged:              # scores="deferred": the sequence that ends here has rows in the log
-            self._seq += 1
-            self._seq_logged = False
-        if self._rseq_logged:             # report="deferred": likewise, with its own ordinal
-            self._rseq += 1
-            self._rseq_logged = False
-        if self._trk_state is not None:   # tracks: ids restart at 0 (a fill kernel on the stream), what is parked is dropped
-            self._trk_state.reset()
-        self._trk_pool += [p[0] for p in self._trk_parked.values()]
-        self._trk_parked = {}
-        self._trk_next = 0
+        self._score_log.end_sequence()    # scores="deferred": the sequence that ends here uses up its ordinal if it has rows in the log
+        self.chain.reset()                # report="deferred": likewise, with its own ordinal; tracks: ids restart at 0
 
     def reset_metrics(self) -> None:
         """Clear what an evaluation pools and reset() keeps: the confusion matrix (protocol="cadis"), the score log and its sequence
@@ -569,12 +424,8 @@ class VideoSegmenter:
         pixels (gt_table)."""
         if self._cm is not None:
             self._cm.zero_()
-        self._log_rows = []
-        self._seq = 0
-        self._seq_logged = False
-        self._rlog_rows = []
-        self._rseq = 0
-        self._rseq_logged = False
+        self._score_log.clear()
+        self.chain.log.clear()
         if self._unmatched is not None:
             self._unmatched.zero_()
 
@@ -592,26 +443,10 @@ class VideoSegmenter:
         if self.scores != "deferred":
             raise StswinHipError("endo_scores() belongs to scores='deferred'")
         from .utils.EndoMetric import EndoScores
-        n = len(self._log_rows)
-        nc = self.model.classifier[-1].out_channels
-        counts = self._log[:n].cpu().numpy() if n else np.zeros((0, 3, nc), dtype=np.int32)
-        order = sorted(range(n), key=lambda r: self._log_rows[r])      # the log is in release order (frame 4 before frame 1 ...);
-        rows = [self._log_rows[r] for r in order]                      # the reference sums in frame order
-        res = EndoScores.from_counts(counts[order], [s for s, _ in rows])
-        res.frames = [f for _, f in rows]
+        cols, sequences, frames = self._score_log.download()            # ordered by sequence and frame: the reference sums in frame order
+        res = EndoScores.from_counts(cols["counts"], sequences)
+        res.frames = frames
         return res
-
-    def _log_counts(self, frame: int, counts: torch.Tensor) -> None:
-        """Append one frame's counts [1][3][nc] to the device log (a device copy; the log doubles when full)."""
-        n = len(self._log_rows)
-        if self._log is None or n == self._log.shape[0]:
-            grown = torch.zeros(max(64, 2 * n), *counts.shape[1:], dtype=torch.int32, device=self.device)
-            if n:
-                grown[:n].copy_(self._log)
-            self._log = grown
-        self._log[n:n + 1].copy_(counts)
-        self._log_rows.append((self._seq, frame))
-        self._seq_logged = True
 
     def instrument_report(self, names: Optional[Sequence[str]] = None):
         """report="deferred": one download of the instrument log -> utils.instruments.InstrumentReport (min_area as given to the
@@ -620,95 +455,26 @@ class VideoSegmenter:
         if self.report != "deferred":
             raise StswinHipError("instrument_report() belongs to report='deferred'")
         from .utils.instruments import InstrumentReport
-        n = len(self._rlog_rows)
-        mom = self._rlog[:n].cpu().numpy() if n else np.zeros((0, self._classes, 10), dtype=np.int64)
-        order = sorted(range(n), key=lambda r: self._rlog_rows[r])     # the log is in release order
-        rows = [self._rlog_rows[r] for r in order]
+        cols, sequences, frames = self.chain.log.download("moments")
         try:
-            return InstrumentReport.from_moments(mom[order], self.out_size or (0, 0), self.min_area, names, [f for _, f in rows],
-                                                 [s for s, _ in rows])
+            return InstrumentReport.from_moments(cols["moments"], self.out_size or (0, 0), self.min_area, names, frames, sequences)
         except ValueError as e:
             raise StswinHipError(f"instrument_report: {e}") from e
-
-    def _moments(self, labels: torch.Tensor, tracked: bool = False) -> Optional[torch.Tensor]:
-        """report: the moments int64 [B][nc][10] of a step's labels [B][*out_size], one launch behind the clearing of its buffer (a
-        fill kernel, also when captured: no memset node); None without report."""
-        if self.report is None:
-            return None
-        mom = hip.label_moments(labels, self._classes)
-        if self.instances is None:
-            return mom
-        inst = self._components(labels)
-        if tracked:                           # the graph's steady step: one frame, in frame order, the tracker's launches behind these
-            cc = self._cc_map[:labels[0].numel()].view(labels.shape[1:])
-            inst += tuple(t[None] for t in hip.track_instances(cc, inst[0][0], inst[1], self._trk_state, self.track_iou,
-                                                               self.track_same_class, self.min_area))
-        return (mom,) + inst
-
-    def _track(self, frame: int, cc: torch.Tensor, rows: torch.Tensor, total: torch.Tensor):
-        """tracks: (ids int32 [1][K], started int32 [1][1]) of a released frame whose component map `cc` [H][W], rows [K][12] and total
-        [1] have just been made.  The tracker takes frames in frame order: a frame whose predecessor has not been tracked yet is
-        parked - its map copied out of the segmenter's component map, ids handed out holding -2 - and tracked, with the frames that wait
-        on it, in the call that tracks the predecessor.  Launches on the stream only."""
-        K = self.instances
-        if self._trk_state is None or (self._trk_state.H, self._trk_state.W) != tuple(cc.shape):
-            self._trk_state = hip.TrackState(cc.shape[0], cc.shape[1], K, self.device)
-        ids = torch.empty(K, dtype=torch.int32, device=self.device)
-        started = torch.empty(1, dtype=torch.int32, device=self.device)
-        if frame != self._trk_next:
-            keep = self._trk_pool.pop() if self._trk_pool and self._trk_pool[-1].shape == cc.shape else torch.empty_like(cc)
-            keep.copy_(cc)
-            ids.fill_(-2)
-            started.fill_(-2)
-            self._trk_parked[frame] = [keep, rows, total, ids, started, None]
-            return ids[None], started[None]
-        self._track_now(cc, rows, total, ids, started)
-        while self._trk_next in self._trk_parked:
-            keep, prows, ptotal, pids, pstarted, log_row = self._trk_parked.pop(self._trk_next)
-            self._track_now(keep, prows, ptotal, pids, pstarted)
-            self._trk_pool.append(keep)
-            if log_row is not None:
-                self._tlog[log_row].copy_(pids)
-                self._tlog_started[log_row:log_row + 1].copy_(pstarted)
-        return ids[None], started[None]
-
-    def _track_now(self, cc, rows, total, ids, started) -> None:
-        hip.track_instances(cc, rows, total, self._trk_state, self.track_iou, self.track_same_class, self.min_area, out=(ids, started))
-        self._trk_next += 1
 
     def track_report(self, names: Optional[Sequence[str]] = None):
         """report="deferred" with tracks=True: one download of the track log -> utils.instruments.TrackReport over instance_report(names):
         every frame released since reset_metrics(), in its order and with its sequence ordinals; ids restart at 0 with every sequence."""
         if self.report != "deferred" or not self.tracks:
             raise StswinHipError("track_report() belongs to report='deferred' with tracks=True")
-        if self._trk_parked:
+        if self.chain.parked:
             raise StswinHipError("track_report(): released frames still wait for their predecessors (finish() the sequence first)")
         from .utils.instruments import TrackReport
         rep = self.instance_report(names)
-        n = len(self._rlog_rows)
-        ids = self._tlog[:n].cpu().numpy() if n else np.zeros((0, self.instances), dtype=np.int32)
-        started = self._tlog_started[:n].cpu().numpy() if n else np.zeros(0, dtype=np.int32)
-        order = sorted(range(n), key=lambda r: self._rlog_rows[r])     # the log is in release order
+        cols = self.chain.log.download("ids", "started")[0]        # (in the rows' order: the same keys)
         try:
-            return TrackReport.from_ids(rep, ids[order], started[order])
+            return TrackReport.from_ids(rep, cols["ids"], cols["started"])
         except ValueError as e:
             raise StswinHipError(f"track_report: {e}") from e
-
-    def _components(self, labels: torch.Tensor):
-        """instances: (rows int64 [B][K][12], total int32 [B]) of a step's labels [B][*out_size], the launches of hip.label_components
-        behind the moments launch.  The component map and the workspace are the segmenter's own and only ever grow, so the warm-up
-        frames allocate what the captured step then uses; rows and total are fresh per step (under capture: the graph's buffers)."""
-        B, H, W = labels.shape
-        need = hip.label_components_scratch(B, H, W)
-        if self._cc_ws is None or self._cc_ws.numel() < need or self._cc_map.numel() < B * H * W:
-            self._cc_retired += [t for t in (self._cc_ws, self._cc_map) if t is not None]     # (a captured step may still use them)
-            self._cc_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-            self._cc_map = torch.empty(B * H * W, dtype=torch.int32, device=self.device)
-        rows = torch.empty(B, self.instances, 12, dtype=torch.int64, device=self.device)
-        total = torch.empty(B, dtype=torch.int32, device=self.device)
-        hip.label_components(labels, self._classes, self.connectivity, self.instance_skip, self.instances,
-                             out=(self._cc_map[:B * H * W].view(B, H, W), rows, total), workspace=self._cc_ws)
-        return rows, total
 
     def instance_report(self, names: Optional[Sequence[str]] = None):
         """report="deferred" with instances=K: one download of the instance log -> utils.instruments.InstanceReport (min_area as given
@@ -717,61 +483,11 @@ class VideoSegmenter:
         if self.report != "deferred" or self.instances is None:
             raise StswinHipError("instance_report() belongs to report='deferred' with instances=K")
         from .utils.instruments import InstanceReport
-        n = len(self._rlog_rows)
-        rows = self._ilog[:n].cpu().numpy() if n else np.zeros((0, self.instances, 12), dtype=np.int64)
-        total = self._ilog_total[:n].cpu().numpy() if n else np.zeros(0, dtype=np.int32)
-        order = sorted(range(n), key=lambda r: self._rlog_rows[r])     # the log is in release order
-        where = [self._rlog_rows[r] for r in order]
+        cols, sequences, frames = self.chain.log.download("rows", "total")
         try:
-            return InstanceReport.from_rows(rows[order], total[order], self.out_size or (0, 0), self.min_area, names,
-                                            [f for _, f in where], [s for s, _ in where])
+            return InstanceReport.from_rows(cols["rows"], cols["total"], self.out_size or (0, 0), self.min_area, names, frames, sequences)
         except ValueError as e:
             raise StswinHipError(f"instance_report: {e}") from e
-
-    def _reported(self, frame: int, result, moments: Optional[torch.Tensor]):
-        """A frame's result with its moments [1][nc][10]: report="frame" appends them (on the device), "deferred" logs them."""
-        inst = None
-        if isinstance(moments, tuple):        # instances: (moments, rows [1][K][12], total [1]), with tracks: ... ids [1][K], started [1][1])
-            moments, inst = moments[0], moments[1:]
-        if self.report == "frame":
-            extra = (moments[0],) if inst is None else (moments[0], inst[0][0], inst[1][0]) + ((inst[2][0],) if self.tracks else ())
-            return result + extra if isinstance(result, tuple) else (result,) + extra
-        if self.report == "deferred":
-            n = len(self._rlog_rows)
-            if inst is not None:
-                if self._ilog is None or n == self._ilog.shape[0]:      # (grows with the moments log: the same rows)
-                    cap = max(64, 2 * n)
-                    grown = torch.zeros(cap, *inst[0].shape[1:], dtype=torch.int64, device=self.device)
-                    grown_total = torch.zeros(cap, dtype=torch.int32, device=self.device)
-                    if n:
-                        grown[:n].copy_(self._ilog[:n])
-                        grown_total[:n].copy_(self._ilog_total[:n])
-                    self._ilog, self._ilog_total = grown, grown_total
-                self._ilog[n:n + 1].copy_(inst[0])
-                self._ilog_total[n:n + 1].copy_(inst[1])
-                if self.tracks:
-                    if self._tlog is None or n == self._tlog.shape[0]:
-                        cap = max(64, 2 * n)
-                        grown = torch.zeros(cap, self.instances, dtype=torch.int32, device=self.device)
-                        grown_started = torch.zeros(cap, dtype=torch.int32, device=self.device)
-                        if n:
-                            grown[:n].copy_(self._tlog[:n])
-                            grown_started[:n].copy_(self._tlog_started[:n])
-                        self._tlog, self._tlog_started = grown, grown_started
-                    if frame in self._trk_parked:         # its row is written when it is tracked
-                        self._trk_parked[frame][5] = n
-                    else:
-                        self._tlog[n:n + 1].copy_(inst[2])
-                        self._tlog_started[n:n + 1].copy_(inst[3][0])
-            if self._rlog is None or n == self._rlog.shape[0]:      # (a device copy; the log doubles when full)
-                grown = torch.zeros(max(64, 2 * n), *moments.shape[1:], dtype=torch.int64, device=self.device)
-                if n:
-                    grown[:n].copy_(self._rlog)
-                self._rlog = grown
-            self._rlog[n:n + 1].copy_(moments)
-            self._rlog_rows.append((self._rseq, frame))
-            self._rseq_logged = True
-        return result
 
     def confusion_matrix(self) -> np.ndarray:
         """protocol="cadis": the pooled confusion matrix, float64 [metric_classes][metric_classes], rows gt, columns prediction."""
@@ -805,8 +521,8 @@ class VideoSegmenter:
     def finish(self) -> List[Tuple[int, object]]:
         self._check_train()
         res = self._run_all(self.planner.finish())
-        if self._trk_parked:
-            raise StswinHipError(f"internal error: frames {sorted(self._trk_parked)} were released and never tracked")
+        if self.chain.parked:
+            raise StswinHipError(f"internal error: frames {sorted(self.chain.parked)} were released and never tracked")
         return res
 
     def segment_sequence(self, frames, gt=None) -> list:
@@ -922,7 +638,7 @@ class VideoSegmenter:
                  tracked: bool = False):
         """ResNet on the new frames' images, clip assembly, Swin / ASPP / head: -> logits (B, nc, H, W), and with labels = True the
         labels (B, *out_size), or for out="overlay" the overlay (B, *out_size, 3) on `frames`, one uint8 [1][Hs][Ws][3] per clip, and
-        with report the labels' moments (B, nc, 10), taken before the overlay launch.
+        with report what the labels yield per clip (_finish_labels; `tracked`: the graph's steady step, the tracker's launches in it).
         Every launch on the current stream, no host synchronisation (graph-capturable)."""
         m = self.model
         hip.arena_reset(self.device)
@@ -945,10 +661,14 @@ class VideoSegmenter:
         hip.clip_assemble(self._ring, tok, clips, table, B, n_new)
         logits = m.forward_frame_tokens(clips, h, w, self.size[0], self.size[1])
         if labels:
-            lab = self._labels(logits)
-            mom = self._moments(lab, tracked)
-            return logits, lab if self._table is None else self._overlay(lab, frames), mom
+            return (logits,) + self._finish_labels(self._labels(logits), frames, steady=tracked)
         return logits, None, None
+
+    def _finish_labels(self, lab: torch.Tensor, frames, clips: Optional[List[int]] = None, steady: bool = False):
+        """Labels (B, *out_size) of a step, or of the one clip `clips` names (made by a scoring launch) -> (the result form of out="labels"
+        | "overlay", what the report chain makes of them per clip).  The one statement of the order: moments, components, (tracks), overlay."""
+        ys = self.chain.labelled(lab, clips, steady)
+        return lab if self._table is None else self._overlay(lab, frames), ys
 
     def _overlay(self, labels: torch.Tensor, frames) -> torch.Tensor:
         """labels (B, *out_size) blended onto the clips' own frames: one launch per clip (the frames live in separate tensors);
@@ -987,23 +707,21 @@ class VideoSegmenter:
         B, n_new = len(st.clips), len(st.new)
         want_labels = self.out != "logits" and not any(g in self._gt for g in st.clips)
         if self.graph and self._steady(st):
-            logits, labels, moments, replayed, frames = self._run_graph(st, want_labels)
+            logits, labels, extras, replayed, frames = self._run_graph(st, want_labels)
         else:
             img = self._ingest_new(st.new) if n_new else None
             frames = [self._kept.pop(g) for g in st.clips] if self._table is not None else None
-            logits, labels, moments = self._compute(img, self._upload_table(st.table()), B, n_new, want_labels, frames)
+            logits, labels, extras = self._compute(img, self._upload_table(st.table()), B, n_new, want_labels, frames)
             replayed = False
-        return self._results(st.clips, logits, labels, frames, moments), replayed
+        return self._results(st.clips, logits, labels, frames, extras), replayed
 
     def _run_graph(self, st: Step, want_labels: bool):
         src, r = self._frames.pop(st.new[0])
         g = self._g
         tracked = self.tracks and want_labels     # the tracker's launches are part of the step: the steady state is in frame order
         if tracked:
-            if self._trk_state is None or self._trk_parked or self._trk_next != st.new[0]:
-                raise StswinHipError(f"internal error: the steady step of frame {st.new[0]} found the tracker at frame {self._trk_next}")
-            self._trk_next += 1
-        if g is None or g[5] != want_labels:
+            self.chain.step_is_steady(st.new[0])
+        if g is None or g.want_labels != want_labels:
             # first steady-state step (or first of the other output form): one eager warm-up on the static buffers (on a side stream,
             # as graph.py's GraphedStep does), then the capture; this step's result is the warm-up's
             u8 = torch.empty(1, *self.frame_shape, 3, dtype=torch.uint8, device=self.device)
@@ -1016,7 +734,7 @@ class VideoSegmenter:
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
-                logits, labels, moments = self._compute(self._static_image(raw, u8), table, 1, 1, want_labels, frames, tracked)
+                logits, labels, extras = self._compute(self._static_image(raw, u8), table, 1, 1, want_labels, frames, tracked)
                 logits = logits.clone()
             torch.cuda.current_stream().wait_stream(side)
             torch.cuda.synchronize()
@@ -1024,68 +742,50 @@ class VideoSegmenter:
             graph = torch.cuda.CUDAGraph()
             autocast = torch.is_autocast_enabled()
             with torch.cuda.graph(graph):
-                out, out_labels, out_moments = self._compute(self._static_image(raw, u8), table, 1, 1, want_labels, frames, tracked)
-            self._g = (graph, raw, table, out, out_labels, want_labels, autocast, u8, out_moments)
-            return logits, labels, moments, False, frames
-        graph, raw, table, out, out_labels, _, autocast, u8, out_moments = g
-        if torch.is_autocast_enabled() != autocast:
+                out, out_labels, out_extras = self._compute(self._static_image(raw, u8), table, 1, 1, want_labels, frames, tracked)
+            self._g = Captured(graph, raw, table, out, out_labels, want_labels, autocast, u8, out_extras)
+            return logits, labels, extras, False, frames
+        if torch.is_autocast_enabled() != g.autocast:
             raise StswinHipError("autocast differs from the state the step was captured under: make a new VideoSegmenter")
-        self._put_frames(src, r, 1, raw)
-        self._upload_table(st.table(), table)
-        graph.replay()
-        return out, out_labels, out_moments, True, [u8] if self._table is not None else None
+        self._put_frames(src, r, 1, g.raw)
+        self._upload_table(st.table(), g.table)
+        g.graph.replay()
+        return g.out, g.labels, g.extras, True, [g.u8] if self._table is not None else None
 
     def _results(self, clips: List[int], logits: torch.Tensor, labels: Optional[torch.Tensor], frames=None,
-                 moments: Optional[torch.Tensor] = None) -> List[Tuple[int, object]]:
-        """`labels`: the step's labels (out="overlay": its overlays) and with report their `moments`, or None when some clip has ground
-        truth or out="logits"."""
+                 extras: Optional[List[Yield]] = None) -> List[Tuple[int, object]]:
+        """`labels`: the step's labels (out="overlay": its overlays) and with report their `extras` per clip, or None when some clip
+        has ground truth or out="logits": each clip's labels then come from its own (scoring) launch."""
         if labels is not None:
-            if moments is None:
-                return [(g, labels[b]) for b, g in enumerate(clips)]
-            if self.tracks and len(moments) == 3:         # (five: the graph's steady step, tracked inside it)
-                hw = self.out_size[0] * self.out_size[1]
-                parts = [_rows_of(moments, b) for b in range(len(clips))]
-                moments = [m + self._track(g, self._cc_map[b * hw:(b + 1) * hw].view(self.out_size), m[1][0], m[2])
-                           for b, (g, m) in enumerate(zip(clips, parts))]
-                return [(g, self._reported(g, labels[b], moments[b])) for b, g in enumerate(clips)]
-            return [(g, self._reported(g, labels[b], _rows_of(moments, b))) for b, g in enumerate(clips)]
-        res = []
-        mom = {}                              # report: the moments of the labels that final() last saw, per clip
-
-        def final(b, lab):                    # labels (1, *out_size) -> the result form of out="labels" | "overlay"
-            mom[b] = self._moments(lab)       # (before the overlay launch: it reads the labels)
-            if self.tracks:                   # (the component map is this clip's until the next clip's labels are made)
-                mom[b] += self._track(clips[b], self._cc_map[:lab[0].numel()].view(lab.shape[1:]), mom[b][1][0], mom[b][2])
-            return lab[0] if self._table is None else self._overlay(lab, frames[b:b + 1])[0]
-
-        for b, g in enumerate(clips):
-            gt = self._gt.pop(g, None)
-            lg = logits[b]
-            if gt is None:
-                res.append((g, lg if self.out == "logits" else final(b, self._labels(logits[b:b + 1]))))
-                continue
-            if self.cadis:
-                lab = self._labels(logits[b:b + 1], gt, want=self.out != "logits")
-                res.append((g, lg if self.out == "logits" else final(b, lab)))
-                continue
-            if self.scores == "deferred":         # the counts stay on the device: no download, no synchronisation
-                lab, counts = hip.upsample_argmax(logits[b:b + 1], *self.out_size, gt)
-                self._log_counts(g, counts)
-                res.append((g, lg if self.out == "logits" else final(b, lab)))
-                continue
-            from .utils.EndoMetric import predict_and_score
-            lab, dices, ious = predict_and_score(logits[b:b + 1], self.out_size, gt)
-            res.append((g, (lg if self.out == "logits" else final(b, lab), dices[0], ious[0])))
-        if self.report is not None:
-            res = [(g, self._reported(g, r, mom[b])) for b, (g, r) in enumerate(res)]
-        return res
+            results = list(labels)
+        else:
+            results, extras = [], []
+            for b, g in enumerate(clips):
+                gt = self._gt.pop(g, None)
+                scored = ()
+                if gt is None:
+                    lab = self._labels(logits[b:b + 1]) if self.out != "logits" else None
+                elif self.cadis:
+                    lab = self._labels(logits[b:b + 1], gt, want=self.out != "logits")
+                elif self.scores == "deferred":       # the counts stay on the device: no download, no synchronisation
+                    lab, counts = hip.upsample_argmax(logits[b:b + 1], *self.out_size, gt)
+                    self._score_log.append(g, counts=counts)
+                else:
+                    from .utils.EndoMetric import predict_and_score
+                    lab, dices, ious = predict_and_score(logits[b:b + 1], self.out_size, gt)
+                    scored = (dices[0], ious[0])
+                r, y = logits[b], None
+                if self.out != "logits":
+                    out, ys = self._finish_labels(lab, frames and frames[b:b + 1], [g])
+                    r, y = out[0], ys and ys[0]
+                results.append((r,) + scored if scored else r)
+                extras.append(y)
+        return list(zip(clips, self.chain.released(clips, results, extras)))
 
 
-def _rows_of(moments, b: int):
-    """Clip b's part [1][...] of a step's moments, or of its (moments, rows, total) with instances."""
-    if isinstance(moments, tuple):
-        return tuple(m[b:b + 1] for m in moments)
-    return moments[b:b + 1]
+# The graph's steady step: the static buffers it reads (raw: the pushed frame; u8: the RGB frame, the same tensor for pixel_format="rgb";
+# the slot table) and writes (out: the logits; with want_labels the labels or overlays and the report chain's extras), its autocast state
+Captured = namedtuple("Captured", "graph raw table out labels want_labels autocast u8 extras")
 
 
 def _clone(r):

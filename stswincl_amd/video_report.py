@@ -1,0 +1,269 @@
+"""What a VideoSegmenter makes of its label maps beside the result (its docstring states the keywords): the chain moments -> instances
+-> tracks with its buffers (ReportChain), its record (Yield), the tracker's frame order (TrackSequencer) and the device log."""
+from __future__ import annotations
+
+from collections import namedtuple
+from types import SimpleNamespace
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import torch
+
+from . import hip
+from .hip import StswinHipError
+
+
+class DeviceLog:
+    """An append-only log on a device: column tensors [capacity][*row shape] that share their rows, and on the host one key
+    (sequence ordinal, frame index) per row; a sequence's ordinal is the number of earlier sequences that logged a row since clear().
+    Appending is a device copy, no synchronisation; full columns double (zeros of max(64, 2 n) rows, the first n copied).
+    `groups`: dicts name -> (row shape, dtype), in the order in which a row's values are copied; a group's columns grow together."""
+
+    def __init__(self, device, *groups: Dict[str, Tuple[Tuple[int, ...], torch.dtype]]):
+        self.device, self.groups, self.columns = device, groups, {name: c for g in groups for name, c in g.items()}
+        self.data: Dict[str, torch.Tensor] = {}
+        self.capacity = 0
+        self.clear()
+
+    def clear(self) -> None:                  # forget every row, restart the ordinal (the device tensors are kept and overwritten)
+        self.keys: List[Tuple[int, int]] = []
+        self.sequence = 0
+
+    def end_sequence(self) -> None:           # the running sequence ends: the next one gets the next ordinal if this one logged a row
+        if self.keys and self.keys[-1][0] == self.sequence:
+            self.sequence += 1
+
+    def append(self, frame: int, **values: torch.Tensor) -> int:
+        """One row for `frame` of the running sequence -> its index.  A column without a value is left for write()."""
+        n = len(self.keys)
+        self.keys.append((self.sequence, frame))
+        grow = n == self.capacity
+        if grow:
+            self.capacity = max(64, 2 * n)
+        for group in self.groups:
+            for name, (shape, dtype) in group.items() if grow else ():
+                grown = torch.zeros(self.capacity, *shape, dtype=dtype, device=self.device)
+                if n:
+                    grown[:n].copy_(self.data[name][:n])
+                self.data[name] = grown
+            self.write(n, **{name: values.get(name) for name in group})
+        return n
+
+    def write(self, row: int, **values: torch.Tensor) -> None:
+        """Values of an appended row, now or later (a parked frame's track row), in the columns' order."""
+        for name in self.columns:
+            if values.get(name) is not None:
+                dst = self.data[name][row:row + 1]
+                dst.copy_(values[name].reshape(dst.shape))
+
+    def download(self, *names: str):
+        """-> (name -> numpy array [rows][*row shape], sequences, frames) for the columns named (default: all), rows ordered by
+        (sequence, frame) - the log itself is in release order; without rows the empty arrays of the columns' shapes."""
+        n = len(self.keys)
+        order = sorted(range(n), key=self.keys.__getitem__)
+        cols = {}
+        for name in names or self.columns:
+            shape, dtype = self.columns[name]
+            cols[name] = self.data[name][:n].cpu().numpy()[order] if n else torch.zeros(0, *shape, dtype=dtype).numpy()
+        return cols, [self.keys[r][0] for r in order], [self.keys[r][1] for r in order]
+
+
+class Yield(namedtuple("Yield", "moments rows total ids started", defaults=(None,) * 4)):
+    """What the labels [B][*out_size] of a step (or of one clip, B = 1) yield on the device: moments int64 [B][nc][10]; with instances
+    rows int64 [B][K][12] and total int32 [B]; once tracked ids int32 [B][K] and started int32 [B][1].  Absent fields are None."""
+    __slots__ = ()
+
+    def clip(self, b: int) -> "Yield":
+        """Clip b's part [1][...]."""
+        return Yield(*(None if t is None else t[b:b + 1] for t in self))
+
+    def appended(self, result):
+        """report="frame": a clip's result r -> r + (moments, rows, total, ids), what there is of them, all on the device."""
+        extra = tuple(t[0] for t in self[:4] if t is not None)
+        return result + extra if isinstance(result, tuple) else (result,) + extra
+
+    def logged(self, log: DeviceLog, frame: int, tracked: bool = True) -> int:
+        """report="deferred": a clip's row in the log -> its index (tracked = False: ids and started are written when it is tracked)."""
+        return log.append(frame, moments=self.moments, rows=self.rows, total=self.total, ids=self.ids if tracked else None,
+                          started=self.started if tracked else None)
+
+
+class TrackSequencer:
+    """The tracker's frame-order rule.  The tracker takes the frames of a sequence in frame order, which is not the order of release
+    (endovis18 releases 0, 1, 4, 2, 5, 3, 6, ..., cadis 0, 1, 2, 5, 3, 6, 4, 7, ..., a batch in the planner's order): a released frame
+    whose predecessor has not been tracked is parked, and tracked when the predecessor is."""
+
+    def __init__(self):
+        self.reset()
+
+    def reset(self) -> None:                                  # a new sequence: frame 0 is next, nothing is parked
+        self.next = 0
+        self.parked = set()
+
+    def release(self, frame: int) -> List[int]:
+        """Frame `frame` is released -> the frames to track now, in order: the frame itself and the parked frames that drain behind
+        it, or [] when the frame is parked."""
+        if frame != self.next:
+            self.parked.add(frame)
+            return []
+        now = [frame]
+        self.next += 1
+        while self.next in self.parked:
+            self.parked.remove(self.next)
+            now.append(self.next)
+            self.next += 1
+        return now
+
+
+class ReportChain:
+    """report / instances / tracks of a VideoSegmenter: hip.label_moments, then the launches of hip.label_components, then those of
+    hip.track_instances on every label map the segmenter makes.  The segmenter calls labelled() where a step's labels exist and
+    released() where its frames are handed out (step_is_steady() is the check in front of the graph's steady step, which tracks inside
+    itself).  Owns what persists across steps: the component map and the workspace (they only grow; the ones they replaced are kept, a
+    captured step may still use them), the tracker's state, the parked frames, the pool of their map copies, and the deferred log."""
+
+    def __init__(self, device, classes: int, protocol: str, out: str, report, min_area, instances, connectivity, instance_skip, tracks,
+                 track_iou, track_same_class):
+        if report not in (None, "frame", "deferred"):
+            raise StswinHipError(f"report must be None, 'frame' or 'deferred', got {report!r}")
+        if report is not None and out == "logits":
+            raise StswinHipError("report belongs to out='labels' and out='overlay' (the moments are taken over the label map)")
+        if isinstance(min_area, bool) or not isinstance(min_area, int) or min_area < 1:
+            raise StswinHipError(f"min_area must be an int >= 1, got {min_area!r}")
+        if report is not None and not 1 <= classes <= 64:
+            raise StswinHipError(f"report: the model has {classes} classes, hip.label_moments takes 1 .. 64")
+        if instances is None:
+            if connectivity != 8 or instance_skip is not None:
+                raise StswinHipError("connectivity and instance_skip belong to instances=K")
+        else:
+            if report is None:
+                raise StswinHipError("instances=K splits the instrument report: it needs report='frame' or 'deferred'")
+            if isinstance(instances, bool) or not isinstance(instances, int) or not 1 <= instances <= 1024:
+                raise StswinHipError(f"instances must be None or an int 1 .. 1024, got {instances!r}")
+            if isinstance(connectivity, bool) or connectivity not in (4, 8):
+                raise StswinHipError(f"connectivity must be 4 or 8, got {connectivity!r}")
+            if instance_skip is None:     # the background, or the remapped ignore label: what `transparent` defaults to
+                instance_skip = (classes - 1,) if protocol == "cadis" else (0,)
+            instance_skip = tuple(instance_skip)
+            if any(isinstance(c, bool) or not isinstance(c, int) or not 0 <= c <= 63 for c in instance_skip):
+                raise StswinHipError(f"instance_skip holds classes 0 .. 63, got {instance_skip!r}")
+        if not isinstance(tracks, bool):
+            raise StswinHipError(f"tracks must be a bool, got {tracks!r}")
+        if not tracks and (track_iou != 100 or track_same_class is not True):
+            raise StswinHipError("track_iou and track_same_class belong to tracks=True")
+        if tracks:
+            if instances is None:
+                raise StswinHipError("tracks=True follows the instances from frame to frame: it needs instances=K")
+            if isinstance(track_iou, bool) or not isinstance(track_iou, int) or not 0 <= track_iou <= 1000:
+                raise StswinHipError(f"track_iou must be an int 0 .. 1000 (thousandths), got {track_iou!r}")
+            if not isinstance(track_same_class, bool):
+                raise StswinHipError(f"track_same_class must be a bool, got {track_same_class!r}")
+        self.device, self.classes, self.report, self.min_area = device, classes, report, min_area
+        self.instances, self.connectivity, self.instance_skip = instances, connectivity, instance_skip
+        self.tracks, self.track_iou, self.track_same_class = tracks, track_iou, track_same_class
+        self.cc_map = self.cc_ws = None       # instances: the component map and the workspace ...
+        self.cc_retired = []                  # ... and the smaller ones they replaced
+        self.state = None                     # tracks: the hip.TrackState of the running sequence (made by the first tracked frame)
+        self.order = TrackSequencer()
+        self.parked = {}                      # frame -> a released frame that waits for the tracker: cc (a copy of its component map),
+        self.pool = []                        # rows [K][12], total [1], ids and started (handed out holding -2), log_row; the copies' pool
+        self.log = DeviceLog(device,          # report="deferred": one row per released frame (a parked frame's ids and started later)
+                             dict(rows=((instances, 12), torch.int64), total=((), torch.int32)) if instances is not None else {},
+                             dict(ids=((instances,), torch.int32), started=((), torch.int32)) if tracks else {},
+                             dict(moments=((classes, 10), torch.int64)))
+
+    def reset(self) -> None:
+        """The sequence ends: its ordinal in the log, ids restart at 0 (a fill kernel on the stream), what is parked is dropped."""
+        self.log.end_sequence()
+        if self.state is not None:
+            self.state.reset()
+        self.pool += [p.cc for p in self.parked.values()]
+        self.parked = {}
+        self.order.reset()
+
+    def labelled(self, labels: torch.Tensor, frames: Optional[Sequence[int]] = None, steady: bool = False) -> Optional[List[Yield]]:
+        """A step's labels [B][*out_size] exist -> what they yield, per clip (None without report): the moments, one launch behind the
+        clearing of their buffer (a fill kernel, also when captured: no memset node), the component launches behind it, and the
+        tracker's behind those for clips whose frame indices `frames` names (labels made per clip: the component map is that clip's
+        until the next clip's labels) or in the graph's steady step (`steady`: one frame, in frame order); released() tracks the rest."""
+        if self.report is None:
+            return None
+        rows = total = ids = started = None
+        moments = hip.label_moments(labels, self.classes)
+        if self.instances is not None:
+            rows, total = self._components(labels)
+        if steady:
+            ids, started = (t[None] for t in self._track_now(self._map(0), rows[0], total))
+        y = Yield(moments, rows, total, ids, started)
+        ys = [y.clip(b) for b in range(labels.shape[0])]
+        if self.tracks and frames is not None:
+            ys = [self._track(g, b, c) for b, (g, c) in enumerate(zip(frames, ys))]
+        return ys
+
+    def released(self, frames: Sequence[int], results: list, ys: Optional[List[Yield]]) -> list:
+        """The clips of `frames` are released with `results` and what their labels yielded: clips not tracked yet are, in the step's
+        order; then report="frame" appends to each result (on the device), "deferred" logs a row.  -> the results."""
+        if self.report is None:
+            return results
+        if self.tracks:
+            ys = [y if y.ids is not None else self._track(g, b, y) for b, (g, y) in enumerate(zip(frames, ys))]
+        if self.report == "frame":
+            return [y.appended(r) for r, y in zip(results, ys)]
+        for g, y in zip(frames, ys):
+            row = y.logged(self.log, g, g not in self.parked)
+            if g in self.parked:
+                self.parked[g].log_row = row
+        return results
+
+    def step_is_steady(self, frame: int) -> None:
+        """tracks: the graph's steady step holds the tracker's launches, so its frame must be the tracker's next one."""
+        at = self.order.next
+        if self.state is None or self.order.parked or self.order.release(frame) != [frame]:
+            raise StswinHipError(f"internal error: the steady step of frame {frame} found the tracker at frame {at}")
+
+    def _map(self, b: int) -> torch.Tensor:                   # clip b's component map [H][W], a view of the chain's own
+        hw = self.hw[0] * self.hw[1]
+        return self.cc_map[b * hw:(b + 1) * hw].view(self.hw)
+
+    def _components(self, labels: torch.Tensor):
+        """(rows int64 [B][K][12], total int32 [B]) of labels [B][H][W].  The component map and the workspace only ever grow, so the
+        warm-up frames allocate what the captured step then uses; rows and total are fresh per step (under capture: the graph's)."""
+        B, H, W = labels.shape
+        need = hip.label_components_scratch(B, H, W)
+        if self.cc_ws is None or self.cc_ws.numel() < need or self.cc_map.numel() < B * H * W:
+            self.cc_retired += [t for t in (self.cc_ws, self.cc_map) if t is not None]
+            self.cc_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            self.cc_map = torch.empty(B * H * W, dtype=torch.int32, device=self.device)
+        self.hw = (H, W)
+        rows = torch.empty(B, self.instances, 12, dtype=torch.int64, device=self.device)
+        total = torch.empty(B, dtype=torch.int32, device=self.device)
+        hip.label_components(labels, self.classes, self.connectivity, self.instance_skip, self.instances,
+                             out=(self.cc_map[:B * H * W].view(B, H, W), rows, total), workspace=self.cc_ws)
+        return rows, total
+
+    def _track(self, frame: int, b: int, y: Yield) -> Yield:
+        """y with the ids [1][K] and started [1][1] of released frame `frame`, whose components clip b of the map holds.  A frame the
+        sequencer parks has its map copied out and its tensors handed out holding -2; the call that tracks its predecessor tracks it."""
+        cc = self._map(b)
+        if self.state is None or (self.state.H, self.state.W) != tuple(cc.shape):
+            self.state = hip.TrackState(cc.shape[0], cc.shape[1], self.instances, self.device)
+        ids = torch.empty(self.instances, dtype=torch.int32, device=self.device)
+        started = torch.empty(1, dtype=torch.int32, device=self.device)
+        now = self.order.release(frame)
+        if not now:
+            keep = self.pool.pop() if self.pool and self.pool[-1].shape == cc.shape else torch.empty_like(cc)
+            keep.copy_(cc)
+            ids.fill_(-2)
+            started.fill_(-2)
+            self.parked[frame] = SimpleNamespace(cc=keep, rows=y.rows[0], total=y.total, ids=ids, started=started, log_row=None)
+        else:
+            self._track_now(cc, y.rows[0], y.total, ids, started)
+            for g in now[1:]:
+                p = self.parked.pop(g)
+                self._track_now(p.cc, p.rows, p.total, p.ids, p.started)
+                self.pool.append(p.cc)
+                if p.log_row is not None:
+                    self.log.write(p.log_row, ids=p.ids, started=p.started)
+        return y._replace(ids=ids[None], started=started[None])
+
+    def _track_now(self, cc, rows, total, *out):
+        return hip.track_instances(cc, rows, total, self.state, self.track_iou, self.track_same_class, self.min_area, out=out or None)

@@ -364,3 +364,65 @@ def test_segmenter_tracks_refusals():
                    dict(out="labels")):
         with pytest.raises(StswinHipError, match="tracks"):
             video.VideoSegmenter(m, **kwargs).track_report()
+
+
+def _all_features_inputs():
+    """Two NV12 sequences made from the shared frames, and the second one's ground truth as an RGBA picture under the first 12
+    colours of the default palette (a few pixels in a colour the table lacks: unmatched).  Computed once, never changed."""
+    if "all" not in _CASES:
+        from stswincl_amd.utils import groundtruth as G, visualize as V, yuv as Y
+        c = _case("endovis18")
+        nv12 = [Y.rgb_to_nv12(s["fr"], Y.to_yuv_matrix()) for s in c["seqs"]]
+        rgb = [Y.yuv_to_rgb(x, "nv12", Y.to_rgb_matrix(), "replicate") for x in nv12]
+        palette = V.default_palette()[:12]
+        gt = c["seqs"][1]["gt"].numpy()
+        rgba = np.concatenate([palette[gt], np.full((N, *SIZE, 1), 255, dtype=np.uint8)], axis=3)
+        rgba[:, 5, 7:11, :3] = (1, 2, 3)
+        _CASES["all"] = dict(nv12=nv12, rgb=rgb, rgba=rgba, table=G.colour_table(palette))
+    return _CASES["all"]
+
+
+@pytest.mark.parametrize("mode", list(C._MODES))
+def test_segmenter_all_features_at_once_equal_each_feature_alone(mode):
+    """Every option of the segmenter switched on together - NV12 in, NV12 overlays out, stored ground truth with deferred scores, the
+    deferred report with instances and tracks - gives, bit for bit and row for row, what the segmenters give that switch on one
+    concern each (and that the tests of those concerns pin)."""
+    c, x = _case("endovis18"), _all_features_inputs()
+    m, kw = c["m"], C._MODES[mode]
+    report = dict(report="deferred", min_area=3, instances=K, tracks=True)
+    with torch.no_grad():
+        full = video.VideoSegmenter(m, pixel_format="nv12", out="overlay", out_format="nv12", gt_table=x["table"], scores="deferred",
+                                    **report, **kw)
+        got = [full.segment_sequence(x["nv12"][0]), full.segment_sequence(x["nv12"][1], gt=x["rgba"])]
+        overlay = video.VideoSegmenter(m, pixel_format="nv12", out="overlay", out_format="nv12", **kw)
+        scored = video.VideoSegmenter(m, out="labels", out_size=SIZE, gt_table=x["table"], scores="deferred", **kw)
+        reported = video.VideoSegmenter(m, out="labels", out_size=SIZE, **report, **kw)
+        for s in range(2):
+            want = overlay.segment_sequence(x["nv12"][s])
+            assert len(got[s]) == len(want) == N
+            for f in range(N):
+                assert isinstance(got[s][f], torch.Tensor) and got[s][f].shape == (SIZE[0] * 3 // 2, SIZE[1]), (s, f)
+                assert got[s][f].dtype == torch.uint8 and torch.equal(got[s][f], want[f]), (s, f)
+            scored.segment_sequence(x["rgb"][s], gt=x["rgba"] if s else None)
+            reported.segment_sequence(x["rgb"][s])
+    a, b = full.endo_scores(), scored.endo_scores()
+    assert a.count == b.count == N and a.dices == b.dices and a.ious == b.ious and a.frames == b.frames == list(range(N))
+    assert a.sequences == b.sequences == [0] * N and np.array_equal(a.dice, b.dice, equal_nan=True) and np.array_equal(a.iou, b.iou, equal_nan=True)
+    assert full.unmatched() == scored.unmatched() == 4 * N
+    a, b = full.instrument_report(), reported.instrument_report()
+    assert a.sequences == b.sequences == [0] * N + [1] * N and a.frames == b.frames == list(range(N)) * 2
+    assert np.array_equal(a.moments, b.moments) and a.size == b.size == SIZE and a.min_area == b.min_area == 3
+    assert np.array_equal(a.presence(), b.presence()) and np.array_equal(a.box, b.box, equal_nan=True)
+    assert np.array_equal(a.angle, b.angle, equal_nan=True)
+    a, b = full.instance_report(), reported.instance_report()
+    assert a.sequences == b.sequences == [0] * N + [1] * N and a.frames == b.frames == list(range(N)) * 2
+    assert np.array_equal(a.rows, b.rows) and np.array_equal(a.total, b.total) and a.size == b.size and a.min_area == b.min_area
+    assert np.array_equal(a.present, b.present) and np.array_equal(a.box, b.box, equal_nan=True)
+    assert np.array_equal(a.angle, b.angle, equal_nan=True) and np.array_equal(a.counts(), b.counts())
+    assert a.as_rows() == b.as_rows() and np.array_equal(a.truncated, b.truncated)
+    a, b = full.track_report(), reported.track_report()
+    assert np.array_equal(a.ids, b.ids) and np.array_equal(a.started, b.started) and a.as_rows() == b.as_rows()
+    assert len(a.tracks) == len(b.tracks) >= 2 and int(a.ids.max()) >= 1
+    for t, w in zip(a.tracks, b.tracks):
+        assert {k: v for k, v in t.items() if not isinstance(v, np.ndarray)} == {k: v for k, v in w.items() if not isinstance(v, np.ndarray)}
+        assert all(np.array_equal(t[k], w[k]) for k in ("frames", "centroids", "areas"))

@@ -1,5 +1,6 @@
 """Host side of stswincl_amd.video (no GPU): the Pillow resize restatement the ingest kernel is checked against, the host
-coefficient tables, the reference's clip rule and release schedule, and the frame-feature ring plan."""
+coefficient tables, the reference's clip rule and release schedule, the frame-feature ring plan, the device log (on the CPU) and
+the tracker's frame order over the planner's release order."""
 import os
 import random
 import sys
@@ -162,3 +163,117 @@ def test_finish_refuses_a_sequence_too_short_for_the_rule():
 def test_ring_smaller_than_needed_is_refused():
     with pytest.raises(StswinHipError):
         video.ClipPlanner(batch=6, slots=8)
+
+
+# ------------------------------------------------------------------------------------------------ the device log, on the CPU
+def _log():
+    import torch
+    from stswincl_amd.video_report import DeviceLog
+    return torch, DeviceLog("cpu", {"rows": ((2, 3), torch.int64), "ids": ((2,), torch.int32), "total": ((), torch.int32)})
+
+
+def _row(torch, v):
+    return dict(rows=torch.full((1, 2, 3), v, dtype=torch.int64), ids=torch.tensor([[v, -v]], dtype=torch.int32),
+                total=torch.tensor([v + 1000], dtype=torch.int32))
+
+
+def test_device_log_empty_download_has_the_columns_shapes_and_dtypes():
+    torch, log = _log()
+    cols, sequences, frames = log.download()
+    assert list(cols) == ["rows", "ids", "total"] and sequences == [] and frames == []
+    assert cols["rows"].shape == (0, 2, 3) and cols["rows"].dtype == np.int64
+    assert cols["ids"].shape == (0, 2) and cols["ids"].dtype == np.int32
+    assert cols["total"].shape == (0,) and cols["total"].dtype == np.int32
+    assert list(log.download("ids")[0]) == ["ids"]
+
+
+def test_device_log_grows_past_64_and_128_rows_and_keeps_its_contents():
+    torch, log = _log()
+    for f in range(130):
+        assert log.append(f, **_row(torch, f)) == f
+        assert log.capacity == (64 if f < 64 else 128 if f < 128 else 256)         # zeros of max(64, 2 n) rows
+        assert all(t.shape[0] == log.capacity for t in log.data.values())
+    cols, sequences, frames = log.download()
+    assert frames == list(range(130)) and sequences == [0] * 130
+    assert np.array_equal(cols["rows"], np.arange(130)[:, None, None].repeat(2, 1).repeat(3, 2))
+    assert np.array_equal(cols["ids"], np.stack([np.arange(130), -np.arange(130)], 1)) and np.array_equal(cols["total"], np.arange(130) + 1000)
+    assert int(log.data["rows"][130:].abs().sum()) == 0                        # what was never written is zero
+
+
+def test_device_log_writes_a_row_after_later_rows_were_appended():
+    torch, log = _log()
+    log.append(0, **_row(torch, 0))
+    late = log.append(4, rows=_row(torch, 4)["rows"], total=_row(torch, 4)["total"])         # (a parked frame: its ids come later)
+    for f in (1, 2):
+        log.append(f, **_row(torch, f))
+    assert log.download("ids")[0]["ids"].tolist() == [[0, 0], [1, -1], [2, -2], [0, 0]]
+    log.write(late, ids=torch.tensor([4, -4], dtype=torch.int32))              # [K], as the tracker hands it out
+    cols, _, frames = log.download()
+    assert frames == [0, 1, 2, 4] and cols["ids"].tolist() == [[0, 0], [1, -1], [2, -2], [4, -4]]
+    assert cols["total"].tolist() == [1000, 1001, 1002, 1004] and cols["rows"][:, 0, 0].tolist() == [0, 1, 2, 4]
+
+
+def test_device_log_orders_by_sequence_and_frame_and_counts_only_sequences_that_logged():
+    torch, log = _log()
+    for f in (0, 1, 4, 2, 5, 3):                                               # release order, not frame order
+        log.append(f, **_row(torch, f))
+    log.end_sequence()
+    log.end_sequence()                                                         # a sequence that logged nothing uses up no ordinal
+    log.end_sequence()
+    for f in (1, 0, 2):
+        log.append(f, **_row(torch, 10 + f))
+    cols, sequences, frames = log.download()
+    assert sequences == [0] * 6 + [1] * 3 and frames == [0, 1, 2, 3, 4, 5, 0, 1, 2]
+    assert cols["total"].tolist() == [1000, 1001, 1002, 1003, 1004, 1005, 1010, 1011, 1012]
+    assert cols["ids"][:, 0].tolist() == [0, 1, 2, 3, 4, 5, 10, 11, 12]
+    log.end_sequence()
+    assert log.sequence == 2
+
+
+def test_device_log_clear_forgets_the_rows_and_restarts_the_ordinal():
+    torch, log = _log()
+    for f in range(70):
+        log.append(f, **_row(torch, f))
+    log.end_sequence()
+    log.clear()
+    assert log.sequence == 0 and log.download()[1:] == ([], []) and log.download()[0]["rows"].shape == (0, 2, 3)
+    log.end_sequence()                                                         # nothing logged since clear()
+    log.append(3, **_row(torch, 7))
+    cols, sequences, frames = log.download()
+    assert sequences == [0] and frames == [3] and cols["total"].tolist() == [1007] and log.capacity == 128
+
+
+# ------------------------------------------------------------------------------------------------ the tracker's frame order
+@pytest.mark.parametrize("chunk", [1, 3])
+@pytest.mark.parametrize("batch", [1, 2, 3, 4])
+@pytest.mark.parametrize("rule", video.RULES)
+def test_track_sequencer_over_the_planner_s_release_order(rule, batch, chunk):
+    """Driven with ClipPlanner's real release order: every frame is tracked exactly once, in frame order; at batch 1 exactly the
+    frames VideoSegmenter's docstring names are parked; nothing is parked after finish()."""
+    from stswincl_amd.video_report import TrackSequencer
+    seq = TrackSequencer()
+    for n in range(video.min_frames(rule), video.min_frames(rule) + 10):
+        p = video.ClipPlanner(batch=batch, rule=rule)
+        seq.reset()
+        assert seq.next == 0 and not seq.parked
+        tracked, parked, released = [], [], []
+        steps = []
+        for lo in range(0, n, chunk):
+            steps += p.push(min(chunk, n - lo))
+        for st in steps + p.finish():
+            for g in st.clips:
+                released.append(g)
+                now = seq.release(g)
+                assert (now == []) == (g != len(tracked)) and now[:1] in ([], [g])       # parked unless its predecessor is tracked
+                if not now:
+                    parked.append(g)
+                    assert g in seq.parked
+                tracked += now
+                assert sorted(seq.parked) == sorted(set(released) - set(tracked))
+        assert sorted(released) == list(range(n))
+        assert tracked == list(range(n)), (rule, batch, n)
+        assert not seq.parked and seq.next == n
+        if batch == 1:
+            assert parked == ([5, 6] if rule == "cadis" else [4, 5]), (rule, n)
+        else:
+            assert len(parked) >= 2

@@ -37,6 +37,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+from online_loop import endovis_model, noisy_frames, take_turns  # noqa: E402
 from stswincl_amd import hip, video  # noqa: E402
 from stswincl_amd.utils import groundtruth  # noqa: E402
 from stswincl_amd.utils.visualize import default_palette  # noqa: E402
@@ -118,17 +119,12 @@ def launch_cost(case, dtype, a):
 
 def evaluation(a):
     (H, W), classes = (1024, 1280), COLOURS
-    torch.manual_seed(a.seed)
-    from stswincl_amd.net.Ours.base18 import TswinPlus
-    model, name = TswinPlus(classes, (64, 80)).cuda().eval(), f"TswinPlus({classes}, (64, 80))"
+    model, name = endovis_model(a.seed, classes)
     gen = np.random.default_rng(a.seed)
     n = 16
-    base = gen.integers(0, 256, (1, H, W, 3), dtype=np.int64)
-    frames = torch.from_numpy(np.clip(base + gen.integers(-24, 25, (n, H, W, 3)), 0, 255).astype(np.uint8)).cuda()
+    frames = noisy_frames(gen, n, H, W)
     stored = rgba_pictures(gen, blob_labels(gen, n, H, W, classes))            # host memory: what a PNG decoder hands over
     table = groundtruth.colour_table(default_palette()[:COLOURS])
-    sync = torch.cuda.synchronize
-    paths = ("host_int64_frame", "stored_deferred", "no_gt")
     res = {"model": name, "frame": [H, W], "autocast": "bf16", "frames_per_window": a.frames, "windows": a.online_windows,
            "gt_bytes_uploaded_per_frame": {"host_int64_frame": H * W * 8, "stored_deferred": H * W * 4}}
     with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16):
@@ -136,12 +132,10 @@ def evaluation(a):
         segs = {"host_int64_frame": video.VideoSegmenter(model, **kw),
                 "stored_deferred": video.VideoSegmenter(model, gt_table=table, scores="deferred", **kw),
                 "no_gt": video.VideoSegmenter(model, **kw)}
-        pushed = {p: 0 for p in paths}
-        fps = {p: [] for p in paths}
         frame_scores = {}                                    # host_int64_frame: frame index -> (dice list, iou list)
 
-        def push(p):
-            k = pushed[p] % n
+        def push(p, k):
+            k %= n
             if p == "host_int64_frame":
                 gt = torch.from_numpy(groundtruth.decode_colours(stored[k], table)[0].astype(np.int64))
                 for f, (_, dice, iou) in segs[p].push(frames[k], gt=gt):
@@ -150,25 +144,12 @@ def evaluation(a):
                 segs[p].push(frames[k], gt=stored[k])
             else:
                 segs[p].push(frames[k])
-            pushed[p] += 1
-            sync()
 
-        for p in paths:                                      # the eager steps, the capture and a few replays
-            for _ in range(video.min_frames("endovis18") + 4):
-                push(p)
-        for _ in range(a.online_windows):
-            for p in paths:
-                t0 = time.perf_counter()
-                for _ in range(a.frames):
-                    push(p)
-                fps[p].append(a.frames / (time.perf_counter() - t0))
+        fps = take_turns(segs, push, a.frames, a.online_windows)
         t0 = time.perf_counter()
         scores = segs["stored_deferred"].endo_scores()
         res["endo_scores_ms"] = round((time.perf_counter() - t0) * 1e3, 2)
-        for p, seg in segs.items():
-            assert seg._g is not None
-            res[p + "_frames_per_s"] = round(float(np.median(fps[p])), 2)
-            res[p + "_frames_per_s_range"] = [round(min(fps[p]), 2), round(max(fps[p]), 2)]
+        res.update(fps)
     same = scores.frames == sorted(frame_scores) and all(scores.dices[r] == frame_scores[f][0] and scores.ious[r] == frame_scores[f][1]
                                                           for r, f in enumerate(scores.frames))
     res["scored_frames"] = scores.count

@@ -35,6 +35,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+from online_loop import endovis_model, noisy_frames, take_turns  # noqa: E402
 from stswincl_amd import hip, video  # noqa: E402
 from stswincl_amd.utils import instruments  # noqa: E402
 
@@ -139,46 +140,26 @@ def launch_cost(case, a):
 
 def online(a):
     (H, W), classes = (1024, 1280), 12
-    torch.manual_seed(a.seed)
-    from stswincl_amd.net.Ours.base18 import TswinPlus
-    model, name = TswinPlus(classes, (64, 80)).cuda().eval(), f"TswinPlus({classes}, (64, 80))"
-    gen = np.random.default_rng(a.seed)
+    model, name = endovis_model(a.seed, classes)
     n = 16
-    base = gen.integers(0, 256, (1, H, W, 3), dtype=np.int64)
-    frames = torch.from_numpy(np.clip(base + gen.integers(-24, 25, (n, H, W, 3)), 0, 255).astype(np.uint8)).cuda()
-    sync = torch.cuda.synchronize
+    frames = noisy_frames(np.random.default_rng(a.seed), n, H, W)
     paths = ("none", "frame", "deferred")
     res = {"model": name, "frame": [H, W], "autocast": "bf16", "frames_per_window": a.frames, "windows": a.online_windows}
     with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16):
         segs = {p: video.VideoSegmenter(model, graph=True, out="labels", out_size=(H, W), report=None if p == "none" else p) for p in paths}
-        pushed = {p: 0 for p in paths}
-        fps = {p: [] for p in paths}
         frame_moments = {}
 
-        def push(p):
-            out = segs[p].push(frames[pushed[p] % n])
+        def push(p, k):
+            out = segs[p].push(frames[k % n])
             if p == "frame":
                 for f, (_, mom) in out:
                     frame_moments[f] = mom.clone()                       # stays on the device: no download in the timed loop
-            pushed[p] += 1
-            sync()
 
-        for p in paths:                                      # the eager steps, the capture and a few replays
-            for _ in range(video.min_frames("endovis18") + 4):
-                push(p)
-        for _ in range(a.online_windows):
-            for p in paths:
-                t0 = time.perf_counter()
-                for _ in range(a.frames):
-                    push(p)
-                fps[p].append(a.frames / (time.perf_counter() - t0))
+        fps = take_turns(segs, push, a.frames, a.online_windows)
         t0 = time.perf_counter()
         rep = segs["deferred"].instrument_report()
         res["instrument_report_ms"] = round((time.perf_counter() - t0) * 1e3, 2)
-        for p, seg in segs.items():
-            assert seg._g is not None
-            res[p + "_frames_per_s"] = round(float(np.median(fps[p])), 2)
-            res[p + "_frames_per_s_range"] = [round(min(fps[p]), 2), round(max(fps[p]), 2)]
+        res.update(fps)
     same = rep.frames == sorted(frame_moments) and all(np.array_equal(rep.moments[r], frame_moments[f].cpu().numpy())
                                                        for r, f in enumerate(rep.frames))
     res["reported_frames"] = len(rep)

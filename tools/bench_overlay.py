@@ -32,6 +32,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+from online_loop import endovis_model, noisy_frames, take_turns  # noqa: E402
 from stswincl_amd import hip, video  # noqa: E402
 from stswincl_amd.utils.visualize import default_palette, overlay_table  # noqa: E402
 
@@ -126,37 +127,13 @@ def online(protocol, a):
         from stswincl_amd.net.Ours.base_cata_np import TswinPlusv5
         model, name = TswinPlusv5(classes).cuda().eval(), f"base_cata_np.TswinPlusv5({classes})"
     else:
-        from stswincl_amd.net.Ours.base18 import TswinPlus
-        model, name = TswinPlus(classes, (64, 80)).cuda().eval(), f"TswinPlus({classes}, (64, 80))"
-    gen = np.random.default_rng(a.seed)
+        model, name = endovis_model(a.seed, classes)
     n = 16
-    base = gen.integers(0, 256, (1, H, W, 3), dtype=np.int64)
-    frames = torch.from_numpy(np.clip(base + gen.integers(-24, 25, (n, H, W, 3)), 0, 255).astype(np.uint8)).cuda()
-    sync = torch.cuda.synchronize
+    frames = noisy_frames(np.random.default_rng(a.seed), n, H, W)
     res = {"model": name, "frame": [H, W], "autocast": "bf16", "frames_per_window": a.frames, "windows": a.online_windows}
     with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16):
         segs = {out: video.VideoSegmenter(model, graph=True, out=out, out_size=(H, W), protocol=protocol) for out in ("labels", "overlay")}
-        pushed = {out: 0 for out in segs}
-        fps = {out: [] for out in segs}
-
-        def push(out):
-            segs[out].push(frames[pushed[out] % n])
-            pushed[out] += 1
-            sync()
-
-        for out in segs:                                     # the eager steps, the capture and a few replays
-            for _ in range(video.min_frames(protocol) + 4):
-                push(out)
-        for _ in range(a.online_windows):
-            for out in segs:
-                t0 = time.perf_counter()
-                for _ in range(a.frames):
-                    push(out)
-                fps[out].append(a.frames / (time.perf_counter() - t0))
-        for out, seg in segs.items():
-            assert seg._g is not None and seg._g[4] is not None
-            res[out + "_frames_per_s"] = round(float(np.median(fps[out])), 2)
-            res[out + "_frames_per_s_range"] = [round(min(fps[out]), 2), round(max(fps[out]), 2)]
+        res.update(take_turns(segs, lambda out, k: segs[out].push(frames[k % n]), a.frames, a.online_windows, protocol))
     res["overlay_over_labels"] = round(res["overlay_frames_per_s"] / res["labels_frames_per_s"], 4)
     res["overlay_extra_us_per_frame"] = round(1e6 / res["overlay_frames_per_s"] - 1e6 / res["labels_frames_per_s"], 1)
     return res

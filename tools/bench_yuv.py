@@ -34,6 +34,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+from online_loop import endovis_model, take_turns  # noqa: E402
 from stswincl_amd import hip, video  # noqa: E402
 from stswincl_amd.utils import yuv  # noqa: E402
 
@@ -115,34 +116,14 @@ def _pictures(a, n, H, W):
 
 def _turns(segs, frames, a, name):
     """Every segmenter pushes its own form of the same pictures, one frame per push, push -> synchronise; windows take turns."""
-    sync = torch.cuda.synchronize
     n = len(next(iter(frames.values())))
-    pushed = {p: 0 for p in segs}
-    fps = {p: [] for p in segs}
     last = {}
 
-    def push(p):
-        k = pushed[p] % n
-        for f, r in segs[p].push(frames[p][k]):
+    def push(p, k):
+        for f, r in segs[p].push(frames[p][k % n]):
             last[p] = (f, r)
-        pushed[p] += 1
-        sync()
 
-    for p in segs:                                       # the eager steps, the capture and a few replays
-        for _ in range(video.min_frames("endovis18") + 4):
-            push(p)
-    for _ in range(a.online_windows):
-        for p in segs:
-            t0 = time.perf_counter()
-            for _ in range(a.frames):
-                push(p)
-            fps[p].append(a.frames / (time.perf_counter() - t0))
-    res = {}
-    for p, seg in segs.items():
-        assert seg._g is not None
-        res[f"{name}_{p}_frames_per_s"] = round(float(np.median(fps[p])), 2)
-        res[f"{name}_{p}_frames_per_s_range"] = [round(min(fps[p]), 2), round(max(fps[p]), 2)]
-    return res, last
+    return take_turns(segs, push, a.frames, a.online_windows, prefix=name + "_"), last
 
 
 def _criterion(res, name, base, others):
@@ -157,11 +138,9 @@ def _criterion(res, name, base, others):
 
 def segmenter(a):
     (H, W), classes, n = (1024, 1280), 12, 16
-    torch.manual_seed(a.seed)
-    from stswincl_amd.net.Ours.base18 import TswinPlus
-    model = TswinPlus(classes, (64, 80)).cuda().eval()
+    model, name = endovis_model(a.seed, classes)
     pics = _pictures(a, n, H, W)
-    res = {"model": f"TswinPlus({classes}, (64, 80))", "frame": [H, W], "autocast": "bf16", "frames_per_window": a.frames,
+    res = {"model": name, "frame": [H, W], "autocast": "bf16", "frames_per_window": a.frames,
            "windows": a.online_windows, "bytes_uploaded_per_frame": {"rgb": 3 * H * W, "nv12": H * W * 3 // 2, "uyvy": 2 * H * W}}
     with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16):
         kw = dict(graph=True, out="labels", out_size=(H, W))
