@@ -653,6 +653,31 @@ int stswin_track_reset(void* state, long state_bytes, int H, int W, int K, void*
 int stswin_track_instances(const int* components /*[H][W]*/, const long long* rows /*[K][12]*/, const int* total /*[1]*/, void* state,
                            long state_bytes, int H, int W, int K, int min_iou, int same_class, int min_area, int* ids /*[K]*/,
                            int* started /*[1]*/, void* stream);
+/* ---- run-length masks (stswincl_amd/utils/rle.py encode, VideoSegmenter(masks=...)): a map uint8 (elem_bytes 1: a label map) or int32
+ * (elem_bytes 4: the components of stswin_label_components) [n][H][W] -> runs int32 [n][cap][2], count int32 [n].  Frame f is read in
+ * column-major order, v[p] = map[f][y][x] with p = x H + y (COCO's order: a run continues from the bottom of column x - 1 into the top
+ * of column x).  A run starts at p = 0 and wherever v[p] != v[p - 1]; R is the number of run starts.
+ *   count[f]    R, not bounded by cap
+ *   runs[f][i]  for i < min(R, cap): (p_i, v[p_i]) of the i-th run start in ascending p, a uint8 value zero-extended, an int32 value
+ *               as it is (-1 included); all zero from min(R, cap) on.  With R > cap the runs kept are the first cap, whatever the order
+ *               of execution; count is complete even then.
+ * Both outputs are written in full by the call (the tail of runs by the third launch, no memset node).  workspace: caller-owned,
+ * 4-byte aligned, >= stswin_rle_encode_scratch(n, H, W) bytes (the starts per column and segment of 32 rows, int32 [n][W][S]); nothing
+ * in it needs clearing and nothing survives the call.  Three launches - count per column and segment, one workgroup per frame scans,
+ * the same walk again stores - no synchronisation, no allocation, no host read (graph-capturable); no kernel waits on another
+ * workgroup.  No atomics: every word has one writer (bit-reproducible).  1 <= H, W <= 16384 (p < 2^28), 1 <= cap <= 1048576, any W;
+ * map aligned to elem_bytes: 16-byte aligned with rows of a multiple of 16 bytes takes the body with one 16-byte load per thread and
+ * row, anything else the element body.  The buffers must not overlap (the host wrapper checks).
+ * Errors, before anything is launched: -1850 n, H or W <= 0, or H or W > 16384 (or more workgroups than a grid holds; also what
+ * stswin_rle_encode_scratch returns for such a shape); -1851 map, runs, count or workspace NULL; -1852 elem_bytes not 1 or 4; -1853 cap
+ * outside 1 .. 1048576; -1854 workspace_bytes too small or workspace not 4-byte aligned; -1855 map not aligned to elem_bytes, or runs
+ * or count not 4-byte aligned. */
+long stswin_rle_encode_scratch(int n, int H, int W);
+int stswin_rle_encode(const void* map /*[n][H][W]*/, int elem_bytes /*1: uint8, 4: int32*/, int* runs /*[n][cap][2]*/,
+                      int* count /*[n]*/, int n, int H, int W, int cap, void* workspace, long workspace_bytes, void* stream);
+/* the geometry of stswin_rle_encode (the tests place their shapes around it): which = 0: rows of a segment (32), 1: columns of a
+ * workgroup's band (256), 2: pixels per thread and row (16 for uint8; a thread of an int32 map takes 4); anything else: -1. */
+int stswin_rle_geometry(int which);
 /* ---- frames as a video source delivers them (stswincl_amd/utils/yuv.py, VideoSegmenter(pixel_format=..., out_format="nv12")):
  * stswin_yuv_to_rgb makes the HWC RGB frame uint8 [n][Hs][Ws][3] that stswin_frame_ingest and stswin_labels_overlay read,
  * stswin_rgb_to_nv12 turns such a frame into NV12.  Hs (NV12) and Ws are even.

@@ -2313,6 +2313,221 @@ extern "C" int stswin_track_instances(const int* components, const long long* ro
   return 0;
 }
 
+// Run-length masks (stswincl_amd/utils/rle.py, encode, states the result; VideoSegmenter(masks=...)): a uint8 label map or an int32
+// component map [n][H][W] -> per frame the runs (p, v) of its column-major reading p = x H + y, sorted by p, the first `cap` of them.
+// Pixel (y, x) starts a run iff it differs from the pixel above it, for y = 0 from the last pixel of the column to its left, and
+// p = 0 always does: the flags come from row-major reads although the order of the result is column-major.  The height is cut into
+// segments of RLE_SH rows, the width into bands of RLE_TW columns; a thread owns V adjacent columns of one segment (V = RLE_V = 16
+// uint8 or 4 int32: 16 bytes per row) and walks the segment's rows with the previous row in registers, RLE_ROWS loads in flight.
+//   1 rle_walk_kernel<.., false>  counts the starts per (column, segment) into a table laid out [W][S]: column-major run order is
+//                                 linear table order
+//   2 rle_scan_kernel             one workgroup per frame: exclusive scan of the table (in place, through LDS) and count[f]
+//   3 rle_walk_kernel<.., true>   the same walk with a running rank per column that starts from the table's offset: stores (p, v)
+//                                 where the rank is below cap; the frame's threads also zero runs from min(count, cap) on
+// WIDE (map 16-byte aligned and a row a multiple of 16 bytes) takes one 16-byte load per row, anything else element loads.  No atomics:
+// every word of the result has one writer.  No kernel uses scratch memory or waits on another workgroup.
+#define RLE_SH 32
+#define RLE_TW 256
+#define RLE_V 16
+#define RLE_THREADS 256
+#define RLE_ROWS 4
+#define RLE_SCAN_THREADS 1024
+#define RLE_SCAN_ITEMS 8
+
+template <int EB>
+__device__ __forceinline__ int rle_value(const uint4& v, int i) {               // (i is a constant after unrolling)
+  if (EB == 4) return (int)(i == 0 ? v.x : i == 1 ? v.y : i == 2 ? v.z : v.w);
+  return (int)lm_byte(v, i);
+}
+
+// elements xs .. xs + V - 1 of the row at `row`, zero where the column is outside 0 .. W - 1 (xs may be -1)
+template <int EB>
+__device__ __forceinline__ uint4 rle_gather(const unsigned char* __restrict__ row, int xs, int W) {
+  unsigned w[4] = {0u, 0u, 0u, 0u};
+  if (EB == 4) {
+    const unsigned* r = reinterpret_cast<const unsigned*>(row);
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      if (xs + i >= 0 && xs + i < W) w[i] = r[xs + i];
+  } else {
+#pragma unroll
+    for (int i = 0; i < 16; ++i)
+      if (xs + i >= 0 && xs + i < W) w[i >> 2] |= (unsigned)row[xs + i] << (8 * (i & 3));
+  }
+  return make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+template <int EB, bool WIDE>
+__device__ __forceinline__ uint4 rle_load(const unsigned char* __restrict__ row, int x0, int W) {
+  if (WIDE) return *reinterpret_cast<const uint4*>(row + (long)x0 * EB);
+  return rle_gather<EB>(row, x0, W);
+}
+
+template <int EB, bool WIDE, bool WRITE>
+__global__ __launch_bounds__(RLE_THREADS) void rle_walk_kernel(const unsigned char* __restrict__ map, int* table, int* __restrict__ runs,
+                                                               const int* __restrict__ count, int H, int W, int S, int cap, int bands,
+                                                               int segblocks) {
+  constexpr int V = EB == 1 ? RLE_V : 4, GPB = RLE_TW / V, SPB = RLE_THREADS / GPB;
+  unsigned b = blockIdx.x;
+  const int band = (int)(b % (unsigned)bands);
+  b /= (unsigned)bands;
+  const int sb = (int)(b % (unsigned)segblocks), f = (int)(b / (unsigned)segblocks);
+  const int s = sb * SPB + (int)threadIdx.x / GPB, x0 = band * RLE_TW + ((int)threadIdx.x % GPB) * V;
+  int* fr = runs + 2 * (long)f * cap;             // (p, v) pairs; runs is only known to be 4-byte aligned: word stores
+  if (WRITE) {                                   // the tail: every thread of the frame's workgroups takes its share
+    const int R = count[f];
+    const long tpf = (long)bands * segblocks * RLE_THREADS;
+    for (long i = (long)min(R, cap) + ((long)sb * bands + band) * RLE_THREADS + threadIdx.x; i < cap; i += tpf) fr[2 * i] = 0, fr[2 * i + 1] = 0;
+  }
+  if (s >= S || x0 >= W) return;
+  int* tb = table + (long)f * W * S;
+  int rank[V];
+#pragma unroll
+  for (int i = 0; i < V; ++i) rank[i] = WRITE && x0 + i < W ? tb[(x0 + i) * S + s] : 0;
+  const long pitch = (long)W * EB;
+  const unsigned char* fm = map + (long)f * H * pitch;
+  const int y0 = s * RLE_SH, y1 = min(H, y0 + RLE_SH);
+  const unsigned colmask = W - x0 >= V ? (1u << V) - 1u : (1u << (W - x0)) - 1u;
+  // the row above the segment; above row 0 every column sees the last pixel of the column to its left
+  uint4 prev = y0 > 0 ? rle_load<EB, WIDE>(fm + (y0 - 1) * pitch, x0, W) : rle_gather<EB>(fm + (H - 1) * pitch, x0 - 1, W);
+  for (int y = y0; y < y1; y += RLE_ROWS) {
+    uint4 cur[RLE_ROWS];
+#pragma unroll
+    for (int r = 0; r < RLE_ROWS; ++r)
+      cur[r] = y + r < y1 ? rle_load<EB, WIDE>(fm + (y + r) * pitch, x0, W) : make_uint4(0u, 0u, 0u, 0u);
+#pragma unroll
+    for (int r = 0; r < RLE_ROWS; ++r) {
+      if (y + r >= y1) continue;
+      const uint4 c = cur[r];
+      unsigned m = 0;
+      if (((c.x ^ prev.x) | (c.y ^ prev.y) | (c.z ^ prev.z) | (c.w ^ prev.w)) != 0u) {
+#pragma unroll
+        for (int i = 0; i < V; ++i)
+          if (rle_value<EB>(c, i) != rle_value<EB>(prev, i)) m |= 1u << i;
+        m &= colmask;
+      }
+      if (y + r == 0 && x0 == 0) m |= 1u;        // p = 0 starts a run whatever the map's last pixel holds
+      if (m) {
+#pragma unroll
+        for (int i = 0; i < V; ++i)
+          if (m >> i & 1u) {
+            if (WRITE && rank[i] < cap) fr[2 * (long)rank[i]] = (x0 + i) * H + y + r, fr[2 * (long)rank[i] + 1] = rle_value<EB>(c, i);
+            ++rank[i];
+          }
+      }
+      prev = c;
+    }
+  }
+  if (!WRITE) {
+#pragma unroll
+    for (int i = 0; i < V; ++i)
+      if (x0 + i < W) tb[(x0 + i) * S + s] = rank[i];
+  }
+}
+
+// One workgroup of 16 waves: a round scans 1024 x 8 entries.  The entries come in and go out through LDS so that the lanes of a wave
+// touch consecutive words of the table (a thread that read its own 8 consecutive entries from memory would cost a cache-line access
+// per lane and entry, and the one compute unit's 2 W S of them were the longest part of the call); in LDS entry i lies at i + i / 8, so
+// that the threads' runs of 8 start 9 words apart and hit distinct banks.  A thread sums its 8 entries, the waves scan the sums with
+// shuffles, the 16 wave totals go through LDS.
+__global__ __launch_bounds__(RLE_SCAN_THREADS) void rle_scan_kernel(int* table, int* __restrict__ count, int entries) {
+  constexpr int ROUND = RLE_SCAN_THREADS * RLE_SCAN_ITEMS;
+  __shared__ unsigned buf[ROUND + ROUND / RLE_SCAN_ITEMS];
+  __shared__ unsigned red[RLE_SCAN_THREADS / 64];
+  int* t = table + (long)blockIdx.x * entries;
+  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  unsigned* mine = buf + tid * (RLE_SCAN_ITEMS + 1);
+  unsigned carry = 0;
+  for (int base = 0; base < entries; base += ROUND) {
+#pragma unroll
+    for (int k = 0; k < RLE_SCAN_ITEMS; ++k) {
+      const int i = k * RLE_SCAN_THREADS + tid;
+      buf[i + i / RLE_SCAN_ITEMS] = base + i < entries ? (unsigned)t[base + i] : 0u;
+    }
+    __syncthreads();
+    unsigned v[RLE_SCAN_ITEMS], sum = 0;
+#pragma unroll
+    for (int k = 0; k < RLE_SCAN_ITEMS; ++k) {
+      v[k] = mine[k];
+      sum += v[k];
+    }
+    unsigned incl = sum;                         // inclusive over the wave
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const unsigned up = __shfl_up(incl, d);
+      if (lane >= d) incl += up;
+    }
+    if (lane == 63) red[wave] = incl;
+    __syncthreads();
+    unsigned before = 0, all = 0;                // the totals of the waves in front, and of all of them
+#pragma unroll
+    for (int k = 0; k < RLE_SCAN_THREADS / 64; ++k) {
+      const unsigned r = red[k];
+      if (k < wave) before += r;
+      all += r;
+    }
+    unsigned o = carry + before + incl - sum;
+#pragma unroll
+    for (int k = 0; k < RLE_SCAN_ITEMS; ++k) {
+      mine[k] = o;
+      o += v[k];
+    }
+    carry += all;
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < RLE_SCAN_ITEMS; ++k) {
+      const int i = k * RLE_SCAN_THREADS + tid;
+      if (base + i < entries) t[base + i] = (int)buf[i + i / RLE_SCAN_ITEMS];
+    }
+    __syncthreads();                             // (buf and red are free for the next round)
+  }
+  if (threadIdx.x == 0) count[blockIdx.x] = (int)carry;
+}
+
+extern "C" int stswin_rle_geometry(int which) { return which == 0 ? RLE_SH : which == 1 ? RLE_TW : which == 2 ? RLE_V : -1; }
+
+extern "C" long stswin_rle_encode_scratch(int n, int H, int W) {
+  if (n <= 0 || H <= 0 || W <= 0 || H > 16384 || W > 16384) return -1850;
+  return 4 * (long)n * W * ((H + RLE_SH - 1) / RLE_SH);               // the table [n][W][S]
+}
+
+template <int EB, bool WIDE>
+static void rle_launch(const unsigned char* map, int* table, int* runs, int* count, int n, int H, int W, int S, int cap, int bands,
+                       int segblocks, hipStream_t st) {
+  const dim3 grid((unsigned)((long)bands * segblocks * n));
+  hipLaunchKernelGGL((rle_walk_kernel<EB, WIDE, false>), grid, dim3(RLE_THREADS), 0, st, map, table, runs, (const int*)count, H, W, S, cap, bands,
+                     segblocks);
+  hipLaunchKernelGGL(rle_scan_kernel, dim3((unsigned)n), dim3(RLE_SCAN_THREADS), 0, st, table, count, W * S);
+  hipLaunchKernelGGL((rle_walk_kernel<EB, WIDE, true>), grid, dim3(RLE_THREADS), 0, st, map, table, runs, (const int*)count, H, W, S, cap, bands,
+                     segblocks);
+}
+
+extern "C" int stswin_rle_encode(const void* map, int elem_bytes, int* runs, int* count, int n, int H, int W, int cap, void* workspace,
+                                 long workspace_bytes, void* stream) {
+  if (n <= 0 || H <= 0 || W <= 0 || H > 16384 || W > 16384) return -1850;
+  if (map == nullptr || runs == nullptr || count == nullptr || workspace == nullptr) return -1851;
+  if (elem_bytes != 1 && elem_bytes != 4) return -1852;
+  if (cap < 1 || cap > 1048576) return -1853;
+  if (workspace_bytes < stswin_rle_encode_scratch(n, H, W) || ((uintptr_t)workspace & 3)) return -1854;
+  if (((uintptr_t)map & (uintptr_t)(elem_bytes - 1)) || ((uintptr_t)runs & 3) || ((uintptr_t)count & 3)) return -1855;
+  const int S = (H + RLE_SH - 1) / RLE_SH, bands = (W + RLE_TW - 1) / RLE_TW;
+  const int spb = RLE_THREADS / (RLE_TW / (elem_bytes == 1 ? RLE_V : 4)), segblocks = (S + spb - 1) / spb;
+  if ((long)bands * segblocks * n > 0x7fffffffL) return -1850;
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned char* m = reinterpret_cast<const unsigned char*>(map);
+  int* table = reinterpret_cast<int*>(workspace);
+  const bool wide = ((uintptr_t)map & 15) == 0 && ((long)W * elem_bytes) % 16 == 0;
+  if (elem_bytes == 1) {
+    if (wide) rle_launch<1, true>(m, table, runs, count, n, H, W, S, cap, bands, segblocks, st);
+    else rle_launch<1, false>(m, table, runs, count, n, H, W, S, cap, bands, segblocks, st);
+  } else {
+    if (wide) rle_launch<4, true>(m, table, runs, count, n, H, W, S, cap, bands, segblocks, st);
+    else rle_launch<4, false>(m, table, runs, count, n, H, W, S, cap, bands, segblocks, st);
+  }
+  STSWIN_CHECK_LAUNCH();
+  return 0;
+}
+
 // Frames as a video source delivers them (stswincl_amd/utils/yuv.py states the arithmetic): NV12 or UYVY -> the HWC RGB frame that
 // stswin_frame_ingest and stswin_labels_overlay read, and RGB -> NV12.  matrix int32 [3][4]: out_c = clamp((m[c][0] t0 + m[c][1] t1 +
 // m[c][2] t2 + m[c][3]) >> 14, 0, 255) in int32 (|sum| < 2^25).  A thread owns YUV_PPT = 8 (wide body) or 2 (byte body) consecutive

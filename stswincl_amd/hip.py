@@ -1667,6 +1667,74 @@ def track_instances(components: torch.Tensor, rows: torch.Tensor, total: torch.T
     return tuple(out)
 
 
+RLE_MAX_RUNS = 1 << 20       # stswin_rle_encode: the largest cap
+
+
+def rle_geometry():
+    """(rows of a segment, columns of a workgroup's band, pixels per thread and row) of stswin_rle_encode."""
+    return tuple(int(load().stswin_rle_geometry(i)) for i in range(3))
+
+
+def rle_encode_scratch(n: int, H: int, W: int) -> int:
+    """Bytes of workspace hip.rle_encode needs for maps [n][H][W]."""
+    b = int(load().stswin_rle_encode_scratch(n, H, W))
+    if b < 0:
+        raise StswinHipError(f"rle_encode: {n} maps of {H} x {W}, the kernel takes up to 16384 x 16384")
+    return b
+
+
+def rle_encode(maps: torch.Tensor, cap: int, out=None, workspace: Optional[torch.Tensor] = None):
+    """uint8 (a label map) or int32 (hip.label_components' map) maps [n][H][W] -> (runs int32 [n][cap][2], count int32 [n]): per frame
+    the runs of its column-major reading v[p] = maps[f][y][x], p = x H + y (COCO's order).  count[f] is the number of runs, not bounded
+    by cap; runs[f][i] = (p_i, v[p_i]) for i < min(count[f], cap) in ascending p, zero from there on - the first cap runs are kept
+    (utils.rle.encode is the numpy definition, matched bit for bit).  out: the pair (runs, count), written in full; workspace: uint8, >=
+    rle_encode_scratch(n, H, W) bytes.  With both given the call allocates nothing, and it never synchronises (graph-capturable).
+    Three launches.  Returns the pair (include/stswin_hip.h, stswin_rle_encode)."""
+    if not isinstance(maps, torch.Tensor) or maps.dtype not in (torch.uint8, torch.int32) or maps.dim() != 3 or not maps.is_contiguous():
+        got = f"{maps.dtype} {tuple(maps.shape)}" if isinstance(maps, torch.Tensor) else type(maps).__name__
+        raise StswinHipError(f"rle_encode: maps must be contiguous uint8 or int32 [n][H][W], got {got}")
+    if not maps.is_cuda:
+        raise StswinHipError("rle_encode: maps must be on the GPU (no CPU path exists; utils.rle.encode is the numpy definition)")
+    n, H, W = maps.shape
+    if n <= 0 or H <= 0 or W <= 0:
+        raise StswinHipError(f"rle_encode: empty maps {tuple(maps.shape)}")
+    if H > 16384 or W > 16384:
+        raise StswinHipError(f"rle_encode: a {H} x {W} map, the kernel takes up to 16384 x 16384")
+    if isinstance(cap, bool) or not isinstance(cap, int) or not 1 <= cap <= RLE_MAX_RUNS:
+        raise StswinHipError(f"rle_encode: cap must be an int 1 .. {RLE_MAX_RUNS}, got {cap!r}")
+    dev = maps.device
+    want = (("runs", torch.int32, (n, cap, 2)), ("count", torch.int32, (n,)))
+    if out is None:
+        out = tuple(torch.empty(shape, dtype=dt, device=dev) for _, dt, shape in want)
+    else:
+        if not isinstance(out, (tuple, list)) or len(out) != 2:
+            raise StswinHipError("rle_encode: out must be the pair (runs, count)")
+        for t, (what, dt, shape) in zip(out, want):
+            if not isinstance(t, torch.Tensor) or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
+                got = f"{t.dtype} {tuple(t.shape)} on {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__
+                form = "".join(f"[{d}]" for d in shape)
+                raise StswinHipError(f"rle_encode: {what} must be contiguous {dt} {form} on {dev}, got {got}")
+    need = rle_encode_scratch(n, H, W)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.dim() != 1 or not workspace.is_contiguous()
+          or workspace.device != dev):
+        got = f"{workspace.dtype} {tuple(workspace.shape)} on {workspace.device}" if isinstance(workspace, torch.Tensor) else type(workspace).__name__
+        raise StswinHipError(f"rle_encode: workspace must be contiguous uint8 [bytes] on {dev}, got {got}")
+    elif workspace.numel() < need:
+        raise StswinHipError(f"rle_encode: a workspace of {workspace.numel()} bytes, {n} maps of {H} x {W} need {need}")
+    elif workspace.data_ptr() % 4:
+        raise StswinHipError("rle_encode: workspace must be 4-byte aligned")
+    bufs = (("maps", maps), ("runs", out[0]), ("count", out[1]), ("workspace", workspace))
+    for i, (wa, a) in enumerate(bufs):
+        for wb, b in bufs[i + 1:]:
+            if _same_memory(a, b):
+                raise StswinHipError(f"rle_encode: {wb} shares memory with {wa}")
+    _check(load().stswin_rle_encode(_p(maps), maps.element_size(), _p(out[0]), _p(out[1]), n, H, W, cap, _p(workspace), workspace.numel(),
+                                    _stream()), "rle_encode")
+    return tuple(out)
+
+
 YUV_NV12, YUV_UYVY = 0, 1                    # stswin_yuv_to_rgb's `format` (plain integers in the header's comment, not #defines)
 YUV_REPLICATE, YUV_LINEAR = 0, 1               # ... and its `chroma`
 _YUV_FORMATS = {"nv12": YUV_NV12, "uyvy": YUV_UYVY}

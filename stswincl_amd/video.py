@@ -194,7 +194,8 @@ def ingest(frames: torch.Tensor, size: Tuple[int, int], out: Optional[torch.Tens
 class VideoSegmenter:
     """Segment video sequences with an eval-mode TswinPlus, one result per frame, each frame's ResNet features computed once.
 
-    seg = VideoSegmenter(model, batch=1, out="logits" | "labels" | "overlay", out_size=None, graph=False, report=None, instances=None)
+    seg = VideoSegmenter(model, batch=1, out="logits" | "labels" | "overlay", out_size=None, graph=False, report=None, instances=None,
+                         tracks=False, masks=None)
 
     push(frames, gt=None) takes uint8 RGB frames [n][Hs][Ws][3] (or one [Hs][Ws][3]; torch tensor on the model's GPU or the CPU, or
     a numpy array; NV12 or UYVY frames with pixel_format, below) and returns [(frame_index, result), ...] for the frames whose clip is now complete.  finish() runs what is
@@ -300,6 +301,29 @@ class VideoSegmenter:
     utils.instruments.TrackReport over every frame released since reset_metrics(), in instance_report()'s order.  tracks=False:
     every result, launch and captured graph is what it is without the keyword.
 
+    masks="frame" | "deferred" (out="labels" | "overlay", both protocols; does not need report; mask_runs=16384): the masks themselves in
+    the form their consumers read, run-length encoded in column-major order (COCO's `counts`, the rle field of MOTS files), so that
+    storing what was segmented needs no download of a map per frame.  Behind the tracker's launches - or the component launches, or the
+    moments launch, or the label launch, whatever the chain ends with - run the three of hip.rle_encode (utils.rle.encode defines the
+    result) on the chain's int32 component map with instances=K, the only thing that tells two shafts apart, and on the uint8 label map
+    otherwise, wherever a step's label map is made, the scoring paths with ground truth included: runs int32 [mask_runs][2] = (start p =
+    x H + y, value) in ascending p, zero behind the last run, and count, an int32 scalar tensor that counts every run although only the
+    first mask_runs are kept (a truncated frame shows as count > mask_runs).  mask_runs defaults to 16384, 128 KB per frame against
+    the 1.3 MB (labels) or 5.2 MB (components) of a 1024 x 1280 map; the basis is an estimate, not a measurement of surgical video - a
+    map of a handful of instruments crosses each of its W columns a few times, a few thousand runs - and tools/bench_masks.py
+    records the largest count it sees.  The deferred log holds 8 mask_runs bytes per frame and grows by doubling from 64 rows, so its
+    first row allocates 8 MB at the default and 512 MB at mask_runs = 1048576: choose mask_runs by the counts, not by the limit.  The
+    log holds columns only for what is deferred (masks="deferred" beside report=None or "frame" logs runs and counts alone).  The encoder needs nothing from the tracker: a frame the tracker parks is encoded when its
+    labels exist.  masks="frame": a result r becomes r + (runs, count) behind whatever report="frame" appends, both on the device - no
+    download and no synchronisation.  Under graph=True the captured steady step holds the encoder's launches behind the tracker's;
+    the workspace is the segmenter's own, allocated by the warm-up frames, and runs and count of the last replayed step of a push are
+    views of the graph's buffers, as rows and total are; with ground truth they are made after the replay.  masks="deferred": results
+    are unchanged and runs and counts go into the device log beside the report's (report and masks choose their modes independently;
+    a row is logged when either is deferred); mask_report(names=None) downloads once and returns utils.rle.MaskReport over every frame
+    released since reset_metrics(), in instrument_report()'s order and with its sequence ordinals - dense(r), objects(r) with each
+    object's COCO RLE, mots_lines(sequence) - joined with instance_report() when instances and report="deferred" are set and with
+    track_report() when tracks is.  masks=None: every result, launch and captured graph is what it is without the keyword.
+
     Runs under torch.no_grad().  Refuses (StswinHipError): a model in train mode, a model or frames not on the GPU, a frame size
     that differs from the earlier frames'."""
 
@@ -309,7 +333,8 @@ class VideoSegmenter:
                  gt_table=None, scores: str = "frame", pixel_format: str = "rgb", yuv_standard: str = "bt709", full_range: bool = False,
                  chroma: str = "replicate", out_format: str = "rgb", report: Optional[str] = None, min_area: int = 1,
                  instances: Optional[int] = None, connectivity: int = 8, instance_skip: Optional[Sequence[int]] = None,
-                 tracks: bool = False, track_iou: int = 100, track_same_class: bool = True):
+                 tracks: bool = False, track_iou: int = 100, track_same_class: bool = True, masks: Optional[str] = None,
+                 mask_runs: int = 16384):
         if out not in ("logits", "labels", "overlay"):
             raise StswinHipError(f"out must be 'logits', 'labels' or 'overlay', got {out!r}")
         if pixel_format not in PIXEL_FORMATS:
@@ -359,9 +384,10 @@ class VideoSegmenter:
         classes = model.classifier[-1].out_channels
         self._score_log = DeviceLog(self.device, {"counts": ((3, classes), torch.int32)})     # scores="deferred": a row per scored frame
         self.chain = ReportChain(self.device, classes, protocol, out, report, min_area, instances, connectivity, instance_skip, tracks,
-                                 track_iou, track_same_class)
+                                 track_iou, track_same_class, masks, mask_runs)
         self.report, self.min_area, self.instances, self.connectivity, self.instance_skip = report, min_area, instances, connectivity, self.chain.instance_skip
         self.tracks, self.track_iou, self.track_same_class = tracks, track_iou, track_same_class
+        self.masks, self.mask_runs = masks, mask_runs
         self._gt_table = None
         self._unmatched = None
         if gt_table is not None:
@@ -421,7 +447,7 @@ class VideoSegmenter:
     def reset_metrics(self) -> None:
         """Clear what an evaluation pools and reset() keeps: the confusion matrix (protocol="cadis"), the score log and its sequence
         ordinal (scores="deferred"), the instrument log and its ordinal (report="deferred"), the count of unmatched ground-truth
-        pixels (gt_table)."""
+        pixels (gt_table); masks="deferred" logs into the instrument log."""
         if self._cm is not None:
             self._cm.zero_()
         self._score_log.clear()
@@ -475,6 +501,32 @@ class VideoSegmenter:
             return TrackReport.from_ids(rep, cols["ids"], cols["started"])
         except ValueError as e:
             raise StswinHipError(f"track_report: {e}") from e
+
+    def mask_report(self, names: Optional[Sequence[str]] = None):
+        """masks="deferred": one download of the mask log -> utils.rle.MaskReport over every frame released since reset_metrics(), rows
+        ordered by sequence and frame as instrument_report()'s; with instances=K and report="deferred" joined with instance_report(names),
+        with tracks=True with track_report(names) too (objects(r) then carry class and track, mots_lines() works)."""
+        if self.masks != "deferred":
+            raise StswinHipError("mask_report() belongs to masks='deferred'")
+        if self.tracks and self.chain.parked:
+            raise StswinHipError("mask_report(): released frames still wait for their predecessors (finish() the sequence first)")
+        from .utils.instruments import InstanceReport, TrackReport
+        from .utils.rle import MaskReport
+        joined = self.instances is not None and self.report == "deferred"
+        wanted = ("runs", "count") + (("rows", "total") if joined else ()) + (("ids", "started") if joined and self.tracks else ())
+        cols, sequences, frames = self.chain.log.download(*wanted)          # the one download: every column the report is made of
+        size = self.out_size or (0, 0)         # (out="overlay" before its first frame: no size yet, and no row that would need one)
+        skip = self.instance_skip if self.instance_skip is not None else (self.chain.classes - 1,) if self.cadis else (0,)
+        inst = trk = None
+        try:
+            if joined:
+                inst = InstanceReport.from_rows(cols["rows"], cols["total"], size, self.min_area, names, frames, sequences)
+                if self.tracks:
+                    trk = TrackReport.from_ids(inst, cols["ids"], cols["started"])
+            return MaskReport(cols["runs"], cols["count"], size, "labels" if self.instances is None else "instances", frames, sequences,
+                              inst, trk, self.min_area, skip, names)
+        except ValueError as e:
+            raise StswinHipError(f"mask_report: {e}") from e
 
     def instance_report(self, names: Optional[Sequence[str]] = None):
         """report="deferred" with instances=K: one download of the instance log -> utils.instruments.InstanceReport (min_area as given
@@ -666,7 +718,7 @@ class VideoSegmenter:
 
     def _finish_labels(self, lab: torch.Tensor, frames, clips: Optional[List[int]] = None, steady: bool = False):
         """Labels (B, *out_size) of a step, or of the one clip `clips` names (made by a scoring launch) -> (the result form of out="labels"
-        | "overlay", what the report chain makes of them per clip).  The one statement of the order: moments, components, (tracks), overlay."""
+        | "overlay", what the report chain makes of them per clip).  The one statement of the order: moments, components, (tracks), masks, overlay."""
         ys = self.chain.labelled(lab, clips, steady)
         return lab if self._table is None else self._overlay(lab, frames), ys
 

@@ -1,5 +1,5 @@
 """What a VideoSegmenter makes of its label maps beside the result (its docstring states the keywords): the chain moments -> instances
--> tracks with its buffers (ReportChain), its record (Yield), the tracker's frame order (TrackSequencer) and the device log."""
+-> tracks -> masks with its buffers (ReportChain), its record (Yield), the tracker's frame order (TrackSequencer) and the device log."""
 from __future__ import annotations
 
 from collections import namedtuple
@@ -67,24 +67,32 @@ class DeviceLog:
         return cols, [self.keys[r][0] for r in order], [self.keys[r][1] for r in order]
 
 
-class Yield(namedtuple("Yield", "moments rows total ids started", defaults=(None,) * 4)):
+class Yield(namedtuple("Yield", "moments rows total ids started runs count", defaults=(None,) * 7)):
     """What the labels [B][*out_size] of a step (or of one clip, B = 1) yield on the device: moments int64 [B][nc][10]; with instances
-    rows int64 [B][K][12] and total int32 [B]; once tracked ids int32 [B][K] and started int32 [B][1].  Absent fields are None."""
+    rows int64 [B][K][12] and total int32 [B]; once tracked ids int32 [B][K] and started int32 [B][1]; with masks runs int32
+    [B][cap][2] and count int32 [B].  Absent fields are None."""
     __slots__ = ()
 
     def clip(self, b: int) -> "Yield":
         """Clip b's part [1][...]."""
         return Yield(*(None if t is None else t[b:b + 1] for t in self))
 
-    def appended(self, result):
-        """report="frame": a clip's result r -> r + (moments, rows, total, ids), what there is of them, all on the device."""
-        extra = tuple(t[0] for t in self[:4] if t is not None)
+    def appended(self, result, report: bool = True, masks: bool = False):
+        """report="frame": a clip's result r -> r + (moments, rows, total, ids), what there is of them; masks="frame": then
+        + (runs, count); all on the device."""
+        extra = tuple(t[0] for t in self[:4] if t is not None) if report else ()
+        if masks:
+            extra += (self.runs[0], self.count[0])
         return result + extra if isinstance(result, tuple) else (result,) + extra
 
-    def logged(self, log: DeviceLog, frame: int, tracked: bool = True) -> int:
-        """report="deferred": a clip's row in the log -> its index (tracked = False: ids and started are written when it is tracked)."""
-        return log.append(frame, moments=self.moments, rows=self.rows, total=self.total, ids=self.ids if tracked else None,
-                          started=self.started if tracked else None)
+    def logged(self, log: DeviceLog, frame: int, tracked: bool = True, report: bool = True, masks: bool = False) -> int:
+        """report="deferred" and / or masks="deferred": a clip's row in the log -> its index (tracked = False: ids and started are
+        written when it is tracked); the columns of the one that is not deferred are left alone."""
+        values = dict(moments=self.moments, rows=self.rows, total=self.total, ids=self.ids if tracked else None,
+                      started=self.started if tracked else None) if report else {}
+        if masks:
+            values.update(runs=self.runs, count=self.count)
+        return log.append(frame, **values)
 
 
 class TrackSequencer:
@@ -115,14 +123,15 @@ class TrackSequencer:
 
 
 class ReportChain:
-    """report / instances / tracks of a VideoSegmenter: hip.label_moments, then the launches of hip.label_components, then those of
-    hip.track_instances on every label map the segmenter makes.  The segmenter calls labelled() where a step's labels exist and
+    """report / instances / tracks / masks of a VideoSegmenter: hip.label_moments, then the launches of hip.label_components, then those
+    of hip.track_instances, then those of hip.rle_encode (on the component map with instances, else on the labels) on every label map
+    the segmenter makes.  The segmenter calls labelled() where a step's labels exist and
     released() where its frames are handed out (step_is_steady() is the check in front of the graph's steady step, which tracks inside
-    itself).  Owns what persists across steps: the component map and the workspace (they only grow; the ones they replaced are kept, a
+    itself).  Owns what persists across steps: the component map and the workspaces (they only grow; the ones they replaced are kept, a
     captured step may still use them), the tracker's state, the parked frames, the pool of their map copies, and the deferred log."""
 
     def __init__(self, device, classes: int, protocol: str, out: str, report, min_area, instances, connectivity, instance_skip, tracks,
-                 track_iou, track_same_class):
+                 track_iou, track_same_class, masks=None, mask_runs=16384):
         if report not in (None, "frame", "deferred"):
             raise StswinHipError(f"report must be None, 'frame' or 'deferred', got {report!r}")
         if report is not None and out == "logits":
@@ -157,7 +166,17 @@ class ReportChain:
                 raise StswinHipError(f"track_iou must be an int 0 .. 1000 (thousandths), got {track_iou!r}")
             if not isinstance(track_same_class, bool):
                 raise StswinHipError(f"track_same_class must be a bool, got {track_same_class!r}")
+        if masks not in (None, "frame", "deferred"):
+            raise StswinHipError(f"masks must be None, 'frame' or 'deferred', got {masks!r}")
+        if masks is not None and out == "logits":
+            raise StswinHipError("masks belongs to out='labels' and out='overlay' (the runs are taken over the label map)")
+        if isinstance(mask_runs, bool) or not isinstance(mask_runs, int) or not 1 <= mask_runs <= hip.RLE_MAX_RUNS:
+            raise StswinHipError(f"mask_runs must be an int 1 .. {hip.RLE_MAX_RUNS}, got {mask_runs!r}")
+        if masks is None and mask_runs != 16384:
+            raise StswinHipError("mask_runs belongs to masks='frame' or 'deferred'")
         self.device, self.classes, self.report, self.min_area = device, classes, report, min_area
+        self.masks, self.mask_runs = masks, mask_runs
+        self.rle_ws = None                    # masks: the encoder's workspace (retired ones go where the component map's do)
         self.instances, self.connectivity, self.instance_skip = instances, connectivity, instance_skip
         self.tracks, self.track_iou, self.track_same_class = tracks, track_iou, track_same_class
         self.cc_map = self.cc_ws = None       # instances: the component map and the workspace ...
@@ -166,10 +185,12 @@ class ReportChain:
         self.order = TrackSequencer()
         self.parked = {}                      # frame -> a released frame that waits for the tracker: cc (a copy of its component map),
         self.pool = []                        # rows [K][12], total [1], ids and started (handed out holding -2), log_row; the copies' pool
-        self.log = DeviceLog(device,          # report="deferred": one row per released frame (a parked frame's ids and started later)
-                             dict(rows=((instances, 12), torch.int64), total=((), torch.int32)) if instances is not None else {},
-                             dict(ids=((instances,), torch.int32), started=((), torch.int32)) if tracks else {},
-                             dict(moments=((classes, 10), torch.int64)))
+        logged = report == "deferred"         # the log holds the columns of what is deferred, nothing else: one row per released frame
+        self.log = DeviceLog(device,          # (a parked frame's ids and started later)
+                             dict(rows=((instances, 12), torch.int64), total=((), torch.int32)) if logged and instances is not None else {},
+                             dict(ids=((instances,), torch.int32), started=((), torch.int32)) if logged and tracks else {},
+                             dict(moments=((classes, 10), torch.int64)) if logged else {},
+                             dict(runs=((mask_runs, 2), torch.int32), count=((), torch.int32)) if masks == "deferred" else {})
 
     def reset(self) -> None:
         """The sequence ends: its ordinal in the log, ids restart at 0 (a fill kernel on the stream), what is parked is dropped."""
@@ -181,14 +202,17 @@ class ReportChain:
         self.order.reset()
 
     def labelled(self, labels: torch.Tensor, frames: Optional[Sequence[int]] = None, steady: bool = False) -> Optional[List[Yield]]:
-        """A step's labels [B][*out_size] exist -> what they yield, per clip (None without report): the moments, one launch behind the
+        """A step's labels [B][*out_size] exist -> what they yield, per clip (None without report and masks): the moments, one launch behind the
         clearing of their buffer (a fill kernel, also when captured: no memset node), the component launches behind it, and the
         tracker's behind those for clips whose frame indices `frames` names (labels made per clip: the component map is that clip's
-        until the next clip's labels) or in the graph's steady step (`steady`: one frame, in frame order); released() tracks the rest."""
-        if self.report is None:
+        until the next clip's labels) or in the graph's steady step (`steady`: one frame, in frame order); released() tracks the rest.
+        The encoder's launches come last: they need nothing from the tracker, so a frame that is parked is encoded here, before the
+        next clip's components overwrite the map."""
+        if self.report is None and self.masks is None:
             return None
-        rows = total = ids = started = None
-        moments = hip.label_moments(labels, self.classes)
+        moments = rows = total = ids = started = None
+        if self.report is not None:
+            moments = hip.label_moments(labels, self.classes)
         if self.instances is not None:
             rows, total = self._components(labels)
         if steady:
@@ -197,21 +221,27 @@ class ReportChain:
         ys = [y.clip(b) for b in range(labels.shape[0])]
         if self.tracks and frames is not None:
             ys = [self._track(g, b, c) for b, (g, c) in enumerate(zip(frames, ys))]
+        if self.masks is not None:
+            B, H, W = labels.shape
+            runs, count = self._runs(self.cc_map[:B * H * W].view(B, H, W) if self.instances is not None else labels)
+            ys = [c._replace(runs=runs[b:b + 1], count=count[b:b + 1]) for b, c in enumerate(ys)]
         return ys
 
     def released(self, frames: Sequence[int], results: list, ys: Optional[List[Yield]]) -> list:
         """The clips of `frames` are released with `results` and what their labels yielded: clips not tracked yet are, in the step's
-        order; then report="frame" appends to each result (on the device), "deferred" logs a row.  -> the results."""
-        if self.report is None:
+        order; then report="frame" and masks="frame" append to each result (on the device), and a row is logged when either is
+        "deferred".  -> the results."""
+        if self.report is None and self.masks is None:
             return results
         if self.tracks:
             ys = [y if y.ids is not None else self._track(g, b, y) for b, (g, y) in enumerate(zip(frames, ys))]
-        if self.report == "frame":
-            return [y.appended(r) for r, y in zip(results, ys)]
-        for g, y in zip(frames, ys):
-            row = y.logged(self.log, g, g not in self.parked)
-            if g in self.parked:
-                self.parked[g].log_row = row
+        if "frame" in (self.report, self.masks):
+            results = [y.appended(r, self.report == "frame", self.masks == "frame") for r, y in zip(results, ys)]
+        if "deferred" in (self.report, self.masks):
+            for g, y in zip(frames, ys):
+                row = y.logged(self.log, g, g not in self.parked, self.report == "deferred", self.masks == "deferred")
+                if g in self.parked and self.report == "deferred":
+                    self.parked[g].log_row = row
         return results
 
     def step_is_steady(self, frame: int) -> None:
@@ -239,6 +269,18 @@ class ReportChain:
         hip.label_components(labels, self.classes, self.connectivity, self.instance_skip, self.instances,
                              out=(self.cc_map[:B * H * W].view(B, H, W), rows, total), workspace=self.cc_ws)
         return rows, total
+
+    def _runs(self, maps: torch.Tensor):
+        """(runs int32 [B][cap][2], count int32 [B]) of maps [B][H][W], uint8 labels or the int32 component map.  The workspace only
+        ever grows, as the component launches' does; runs and count are fresh per step (under capture: the graph's)."""
+        need = hip.rle_encode_scratch(*maps.shape)
+        if self.rle_ws is None or self.rle_ws.numel() < need:
+            if self.rle_ws is not None:
+                self.cc_retired.append(self.rle_ws)
+            self.rle_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        runs = torch.empty(maps.shape[0], self.mask_runs, 2, dtype=torch.int32, device=self.device)
+        count = torch.empty(maps.shape[0], dtype=torch.int32, device=self.device)
+        return hip.rle_encode(maps, self.mask_runs, out=(runs, count), workspace=self.rle_ws)
 
     def _track(self, frame: int, b: int, y: Yield) -> Yield:
         """y with the ids [1][K] and started [1][1] of released frame `frame`, whose components clip b of the map holds.  A frame the
