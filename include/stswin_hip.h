@@ -653,6 +653,41 @@ int stswin_track_reset(void* state, long state_bytes, int H, int W, int K, void*
 int stswin_track_instances(const int* components /*[H][W]*/, const long long* rows /*[K][12]*/, const int* total /*[1]*/, void* state,
                            long state_bytes, int H, int W, int K, int min_iou, int same_class, int min_area, int* ids /*[K]*/,
                            int* started /*[1]*/, void* stream);
+/* ---- the tracker with a memory (stswincl_amd/utils/instruments.py MemoryTracker, VideoSegmenter(tracks=True, track_max_gap=g)): the
+ * same inputs and outputs as stswin_track_instances, with a state of its own.  A track that no instance is matched to stays alive for
+ * up to max_gap calls, and instances are matched against the mask the track had when it was last seen: mem[p] is the track pixel p is
+ * remembered for.  Instance j takes part as above.  ov[t][j] = the pixels with mem == t that carry ordinal j in this call's map, u =
+ * area[t] + area[j] - ov with area[t] the track's area at its last sighting.  (t, j) is a candidate iff ov > 0, the classes are equal
+ * (same_class = 1) and 1000 ov >= min_iou u.  (t, j) is preferred to (t', j') iff ov u' > ov' u (int64 products), then the smaller
+ * track id, then smaller j.  Repeatedly the most preferred candidate whose t and j are both unmatched is matched and ids[j] = t; the
+ * participants left over take next, next + 1, ... in ascending j; every other entry of ids is -1; started = next after the call.  A
+ * matched track takes the instance's class and area and age 0, a new track has age 0, every other live track ages by one and ends
+ * when its age exceeds max_gap.  If more than K tracks live then, lost ones (age >= 1) end until K do, the largest age first, then the
+ * smallest id.  A pixel of a participant j then takes ids[j]; any other pixel becomes -1 if its track ended or was matched in this
+ * call and stays otherwise.  Bit for bit MemoryTracker.update, whatever the order of execution (integer atomics only); with max_gap =
+ * 0 every unmatched track ends at once.
+ * state: caller-owned, 16-byte aligned, >= stswin_track_memory_state_bytes(H, W, K) bytes, int32 words.  The live tracks sit in K
+ * slots; which slot a track has shows in no output:
+ *   [0] next id   [1] listed pairs   [2], [3] unused   cls[K] (-1: a free slot), area[K], id[K], age[K] of the slots   slot_of[K]: the
+ *   slot of each ordinal of the last call (-1: took no part)   keep[K]: 1 for the slots whose remembered pixels the last call kept
+ *   ov[K][K] (slot, ordinal)   list[K K]: the pairs slot << 10 | j with ov != 0   then, 16-byte aligned, the memory map [H W] of slots,
+ *   padded with -1 to a multiple of four pixels.
+ * stswin_track_memory_reset (one fill kernel, no memset node) starts a sequence: next = 0, every slot free, a memory map of -1, ov and
+ * the list cleared; a state must be reset once before its first use.  stswin_track_memory is three launches: the overlap pass of
+ * stswin_track_instances over the memory map and `components`, which writes neither; one workgroup that matches, writes ids and
+ * started, ages, ends and evicts tracks, gives births the free slots, leaves slot_of and keep and clears what the overlap pass
+ * counted; and a commit pass over both maps, four pixels per thread with both tables in LDS, mem = the pixel's instance takes part ?
+ * slot_of[components] : (mem >= 0 and keep[mem] ? mem : -1).  No allocation, no synchronisation, `total` is read on the device only
+ * (graph-capturable); no kernel waits on another workgroup.  The buffers must not overlap (the host wrapper checks).
+ * Errors, before anything is launched: -1860 H or W <= 0 or > 16384; -1861 K outside 1 .. 1024 (stswin_track_memory_state_bytes
+ * returns these two as well); -1862 a NULL pointer; -1863 state_bytes too small or state not 16-byte aligned; -1864 components, total,
+ * ids or started not 4-byte aligned, or rows not 8-byte aligned; -1865 min_iou outside 0 .. 1000, same_class not 0 or 1, or min_area
+ * < 1; -1866 max_gap outside 0 .. 1000000. */
+long stswin_track_memory_state_bytes(int H, int W, int K);
+int stswin_track_memory_reset(void* state, long state_bytes, int H, int W, int K, void* stream);
+int stswin_track_memory(const int* components /*[H][W]*/, const long long* rows /*[K][12]*/, const int* total /*[1]*/, void* state,
+                        long state_bytes, int H, int W, int K, int max_gap, int min_iou, int same_class, int min_area, int* ids /*[K]*/,
+                        int* started /*[1]*/, void* stream);
 /* ---- run-length masks (stswincl_amd/utils/rle.py encode, VideoSegmenter(masks=...)): a map uint8 (elem_bytes 1: a label map) or int32
  * (elem_bytes 4: the components of stswin_label_components) [n][H][W] -> runs int32 [n][cap][2], count int32 [n].  Frame f is read in
  * column-major order, v[p] = map[f][y][x] with p = x H + y (COCO's order: a run continues from the bottom of column x - 1 into the top

@@ -2105,7 +2105,9 @@ __device__ __forceinline__ void trk_add(int* tag, unsigned* cnt, int* ov, int* l
   else trk_global(ov, list, npairs, K, key, c);
 }
 
-template <bool VEC>
+// COPY: the tracker without memory, which writes the current map over the previous one; !COPY: the memory tracker's first launch, which
+// reads the memory map (slot indices) and writes nothing but the counts.
+template <bool VEC, bool COPY>
 __global__ __launch_bounds__(TRK_THREADS) void trk_overlap_kernel(const int* __restrict__ cur, int* __restrict__ prev, int* ov, int* list,
                                                                   int* npairs, long HW, int K) {
   __shared__ int tag[TRK_SLOTS];
@@ -2129,7 +2131,7 @@ __global__ __launch_bounds__(TRK_THREADS) void trk_overlap_kernel(const int* __r
         if (p0 + 2 < HW) c.z = cur[p0 + 2];
         if (p0 + 3 < HW) c.w = cur[p0 + 3];
       }
-      *reinterpret_cast<int4*>(prev + p0) = c;                 // (each pixel's old value was read by this thread; the padding stays -1)
+      if (COPY) *reinterpret_cast<int4*>(prev + p0) = c;       // (each pixel's old value was read by this thread; the padding stays -1)
     }
     const unsigned uk = (unsigned)K;
     const int k0 = (unsigned)p.x < uk && (unsigned)c.x < uk ? (p.x << 10) | c.x : -1;
@@ -2172,19 +2174,28 @@ __global__ __launch_bounds__(TRK_THREADS) void trk_overlap_kernel(const int* __r
 }
 
 // a (overlap oa, union ua, key ka) is preferred to b: oa / ua > ob / ub as an exact int64 product (< 2^57), then the smaller (i, j)
-__device__ __forceinline__ bool trk_better(long oa, long ua, int ka, long ob, long ub, int kb) {
+__device__ __forceinline__ bool trk_better(long oa, long ua, long ka, long ob, long ub, long kb) {
   const long l = oa * ub, r = ob * ua;
   return l > r || (l == r && ka < kb);
 }
 
+// what breaks a tie between equally preferred pairs: the pair itself (i, j), or with BYID (the memory tracker, whose i is a slot)
+// (the id of i's track, j)
+template <bool BYID>
+__device__ __forceinline__ long trk_rank(int key, const int* pids) {
+  return BYID ? ((long)pids[key >> 10] << 10) | (key & 1023) : (long)key;
+}
+
 // the pair `key` becomes *best unless a better one holds it.  Each turn ends or continues against a strictly better holder.
-__device__ __forceinline__ void trk_contend(int* best, int key, long o, long u, const int* ov, const int* parea, const int* carea, int K) {
+template <bool BYID>
+__device__ __forceinline__ void trk_contend(int* best, int key, long o, long u, const int* ov, const int* parea, const int* carea, const int* pids,
+                                            int K) {
   int cur = *(volatile int*)best;
   for (;;) {
     if (cur >= 0) {
       const int ci = cur >> 10, cj = cur & 1023;
       const long co = ov[(long)ci * K + cj];
-      if (!trk_better(o, u, key, co, (long)parea[ci] + carea[cj] - co, cur)) return;
+      if (!trk_better(o, u, trk_rank<BYID>(key, pids), co, (long)parea[ci] + carea[cj] - co, trk_rank<BYID>(cur, pids))) return;
     }
     const int old = atomicCAS(best, cur, key);
     if (old == cur) return;
@@ -2233,8 +2244,8 @@ __global__ __launch_bounds__(TRK_THREADS) void trk_match_kernel(const long long*
         continue;
       }
       const long o = ov[(long)i * K + j], u = (long)parea[i] + carea[j] - o;
-      trk_contend(rbest + i, key, o, u, ov, parea, carea, K);
-      trk_contend(cbest + j, key, o, u, ov, parea, carea, K);
+      trk_contend<false>(rbest + i, key, o, u, ov, parea, carea, pids, K);
+      trk_contend<false>(cbest + j, key, o, u, ov, parea, carea, pids, K);
     }
     __syncthreads();
     for (int p = tid; p < np; p += TRK_THREADS) {
@@ -2304,11 +2315,265 @@ extern "C" int stswin_track_instances(const int* components, const long long* ro
   const long HW = (long)H * W, nvec = (HW + 3) >> 2;
   const unsigned blocks = (unsigned)((nvec + TRK_THREADS * TRK_VPT - 1) / (TRK_THREADS * TRK_VPT));       // <= 2^17
   if ((uintptr_t)components & 15)
-    hipLaunchKernelGGL(trk_overlap_kernel<false>, dim3(blocks), dim3(TRK_THREADS), 0, st, components, s + l.map, s + l.ov, s + l.list, s + 1, HW, K);
+    hipLaunchKernelGGL((trk_overlap_kernel<false, true>), dim3(blocks), dim3(TRK_THREADS), 0, st, components, s + l.map, s + l.ov, s + l.list, s + 1, HW, K);
   else
-    hipLaunchKernelGGL(trk_overlap_kernel<true>, dim3(blocks), dim3(TRK_THREADS), 0, st, components, s + l.map, s + l.ov, s + l.list, s + 1, HW, K);
+    hipLaunchKernelGGL((trk_overlap_kernel<true, true>), dim3(blocks), dim3(TRK_THREADS), 0, st, components, s + l.map, s + l.ov, s + l.list, s + 1, HW, K);
   hipLaunchKernelGGL(trk_match_kernel, dim3(1), dim3(TRK_THREADS), 0, st, rows, total, s, s + l.cls, s + l.area, s + l.ids, s + l.ov, s + l.list,
                      K, min_iou, same_class, min_area, ids, started);
+  STSWIN_CHECK_LAUNCH();
+  return 0;
+}
+
+// The tracker with a memory (stswincl_amd/utils/instruments.py, MemoryTracker, states the result; VideoSegmenter(tracks=True,
+// track_max_gap=g)): a track that no instance was matched to stays alive for up to max_gap frames, and instances are matched against
+// the mask it had when it was last seen.  The live tracks sit in K slots - which slot a track has shows in no output - and the memory
+// map holds, per pixel, the slot of the track it is remembered for.  The state buffer, in int32 words (include/stswin_hip.h too):
+//   [0] next id  [1] number of listed pairs  [2], [3] unused      cls[K] (-1: a free slot), area[K], id[K], age[K] of the slots
+//   slot_of[K] the slot of each current ordinal (-1: takes no part)      keep[K] per slot: 1 if its remembered pixels stay
+//   ov[K][K] overlap counts (slot, ordinal)      list[K K] the pairs (slot << 10 | j) whose count is non-zero      the memory map,
+//   16-byte aligned and padded with -1 to a multiple of four pixels
+// Between two calls ov is all zero and the list is empty, as above.
+//   1 trk_overlap_kernel<.., false>  the overlap pass above over the memory map and the component map; it writes neither
+//   2 trk_mem_match_kernel           one workgroup: the candidate filter and the rounds of trk_match_kernel with the track's id in the
+//                                    tie-break; ids and started; then per slot matched (takes the instance's class and area, age 0),
+//                                    aged or ended; if more than K tracks would live, the lost ones are ranked by (age descending,
+//                                    id ascending) among themselves and the first ones end; births take the free slots in ascending
+//                                    order of both; slot_of and keep for the third launch; ov and the list cleared
+//   3 trk_commit_kernel              four pixels per thread, slot_of and keep in LDS: mem = the pixel's instance takes part ?
+//                                    slot_of[comp] : (mem >= 0 and keep[mem] ? mem : -1), stored where it changes anything
+// Integer atomics only.  No kernel uses scratch memory or waits on another workgroup.
+#define TRK_CVPT 4
+
+struct TrkMemLayout {
+  long cls, area, ids, age, slot_of, keep, ov, list, map, words;
+};
+static inline TrkMemLayout trk_mem_layout(int H, int W, int K) {
+  TrkMemLayout l;
+  const long KK = (long)K * K;
+  l.cls = 4, l.area = 4 + (long)K, l.ids = 4 + 2L * K, l.age = 4 + 3L * K, l.slot_of = 4 + 4L * K, l.keep = 4 + 5L * K, l.ov = 4 + 6L * K;
+  l.list = l.ov + KK;
+  l.map = (l.list + KK + 3) & ~3L;
+  l.words = l.map + (((long)H * W + 3) & ~3L);
+  return l;
+}
+
+__global__ __launch_bounds__(TRK_THREADS) void trk_mem_reset_kernel(int* __restrict__ s, long cls, long area, long ids, long age, long slot_of,
+                                                                    long keep, long map, long words) {
+  for (long i = (long)blockIdx.x * TRK_THREADS + threadIdx.x; i < words; i += (long)gridDim.x * TRK_THREADS)
+    s[i] = (i >= cls && i < area) || (i >= ids && i < age) || (i >= slot_of && i < keep) || i >= map ? -1 : 0;
+}
+
+__global__ __launch_bounds__(TRK_THREADS) void trk_mem_match_kernel(const long long* __restrict__ rows, const int* __restrict__ total, int* hdr,
+                                                                    int* pcls, int* parea, int* pids, int* page, int* slot_of, int* keep,
+                                                                    int* ov, int* list, int K, int max_gap, int min_iou, int same_class,
+                                                                    int min_area, int* __restrict__ ids, int* __restrict__ started) {
+  __shared__ int ccls[TRK_MAXK], carea[TRK_MAXK], rbest[TRK_MAXK], cbest[TRK_MAXK], rmatch[TRK_MAXK], cmatch[TRK_MAXK];
+  __shared__ long lostkey[TRK_MAXK];       // a lost slot: age << 32 | (2^31 - 1 - id), the larger one ends first; 0: not lost
+  __shared__ int ends[TRK_MAXK], freel[TRK_MAXK];
+  __shared__ unsigned red[4];
+  __shared__ int changed, nkept[2];
+  const int tid = (int)threadIdx.x;
+  const int n = min(max(total[0], 0), K), np = min(max(hdr[1], 0), K * K), next = hdr[0];
+  for (int j = tid; j < K; j += TRK_THREADS) {
+    const long long a = j < n ? rows[(long)j * 12 + 2] : 0ll;
+    const bool part = j < n && a >= (long long)min_area;
+    ccls[j] = part ? (int)rows[(long)j * 12] : -1;
+    carea[j] = part ? (int)a : 0;
+    rmatch[j] = cmatch[j] = -1;
+  }
+  if (tid < 2) nkept[tid] = 0;
+  __syncthreads();
+  for (int p = tid; p < np; p += TRK_THREADS) {               // the listed pairs that are no candidates leave the list
+    const int key = list[p], i = key >> 10, j = key & 1023;
+    if (key < 0 || i >= K || j >= K) {                         // (only a state that was never reset holds such a key)
+      list[p] = -1;
+      continue;
+    }
+    const long o = ov[(long)i * K + j];
+    const int pc = pcls[i], cc = ccls[j];
+    bool ok = pc >= 0 && cc >= 0 && (!same_class || pc == cc);
+    if (ok) ok = 1000l * o >= (long)min_iou * ((long)parea[i] + carea[j] - o);
+    if (!ok) ov[(long)i * K + j] = 0, list[p] = -1;
+  }
+  for (;;) {
+    for (int j = tid; j < K; j += TRK_THREADS) rbest[j] = cbest[j] = -1;
+    if (tid == 0) changed = 0;
+    __syncthreads();
+    for (int p = tid; p < np; p += TRK_THREADS) {
+      const int key = list[p];
+      if (key < 0) continue;
+      const int i = key >> 10, j = key & 1023;
+      if (rmatch[i] >= 0 || cmatch[j] >= 0) {                 // matched, or beaten for good: done with
+        ov[(long)i * K + j] = 0, list[p] = -1;
+        continue;
+      }
+      const long o = ov[(long)i * K + j], u = (long)parea[i] + carea[j] - o;
+      trk_contend<true>(rbest + i, key, o, u, ov, parea, carea, pids, K);
+      trk_contend<true>(cbest + j, key, o, u, ov, parea, carea, pids, K);
+    }
+    __syncthreads();
+    for (int p = tid; p < np; p += TRK_THREADS) {
+      const int key = list[p];
+      if (key < 0) continue;
+      const int i = key >> 10, j = key & 1023;
+      if (rbest[i] == key && cbest[j] == key) rmatch[i] = j, cmatch[j] = i, changed = 1;
+    }
+    __syncthreads();
+    const int c = changed;
+    __syncthreads();
+    if (!c) break;
+  }
+  for (int p = tid; p < np; p += TRK_THREADS) {               // (none is left at the fixed point; the state's invariant does not rest on it)
+    const int key = list[p];
+    if (key >= 0) ov[(long)(key >> 10) * K + (key & 1023)] = 0, list[p] = -1;
+  }
+  unsigned births = 0;                                         // births: the unmatched participants, numbered in ascending j
+  for (int base = 0; base < K; base += TRK_THREADS) {
+    const int j = base + tid;
+    const int m = j < K ? cmatch[j] : -1;
+    const unsigned b = j < K && ccls[j] >= 0 && m < 0 ? 1u : 0u;
+    const unsigned incl = cc_block_scan(b, red);
+    if (j < K) {
+      rbest[j] = m >= 0 ? pids[m] : b ? next + (int)(births + incl - 1u) : -1;      // the id of ordinal j ...
+      cbest[j] = b ? (int)(births + incl - 1u) : -1;                                 // ... and which birth it is
+    }
+    births += red[0] + red[1] + red[2] + red[3];
+  }
+  for (int i = tid; i < K; i += TRK_THREADS) {                 // the slots: matched, lost (age 1 .. max_gap) or over
+    const bool live = pcls[i] >= 0, matched = live && rmatch[i] >= 0;
+    const int age = live && !matched ? page[i] + 1 : 0;
+    const bool lost = age >= 1 && age <= max_gap;
+    lostkey[i] = lost ? ((long)age << 32) | (long)(0x7fffffff - pids[i]) : 0l;
+    ends[i] = 0;
+    if (matched) atomicAdd(&nkept[0], 1);
+    if (lost) atomicAdd(&nkept[1], 1);
+  }
+  __syncthreads();
+  const int over = nkept[0] + nkept[1] + (int)births - K;      // more than K tracks: the `over` oldest lost ones end, the smaller id first
+  if (over > 0) {
+    for (int i = tid; i < K; i += TRK_THREADS) {
+      const long key = lostkey[i];
+      if (key == 0l) continue;
+      int before = 0;
+#pragma unroll 8
+      for (int o = 0; o < K; ++o) before += lostkey[o] > key ? 1 : 0;
+      ends[i] = before < over ? 1 : 0;
+    }
+    __syncthreads();
+  }
+  unsigned nfree = 0;                                          // the slots' new state; the free ones, listed in ascending order
+  for (int base = 0; base < K; base += TRK_THREADS) {
+    const int i = base + tid;
+    unsigned f = 0u;
+    if (i < K) {
+      const int j = pcls[i] >= 0 ? rmatch[i] : -1;
+      const bool stays = lostkey[i] != 0l && !ends[i];
+      if (j >= 0) pcls[i] = ccls[j], parea[i] = carea[j], page[i] = 0, keep[i] = 0;
+      else if (stays) page[i] = (int)(lostkey[i] >> 32), keep[i] = 1;
+      else pcls[i] = -1, parea[i] = 0, pids[i] = -1, page[i] = 0, keep[i] = 0, f = 1u;
+    }
+    const unsigned incl = cc_block_scan(f, red);
+    if (f) freel[nfree + incl - 1u] = i;
+    nfree += red[0] + red[1] + red[2] + red[3];
+  }
+  __syncthreads();                                             // (the free list is complete, every slot's state is written)
+  for (int j = tid; j < K; j += TRK_THREADS) {
+    const int id = rbest[j], b = cbest[j];
+    int slot = cmatch[j];
+    if (b >= 0) {                                              // (a birth always finds a free slot: at most K tracks live)
+      slot = (unsigned)b < nfree ? freel[b] : -1;
+      if (slot >= 0) pcls[slot] = ccls[j], parea[slot] = carea[j], pids[slot] = id, page[slot] = 0;
+    }
+    ids[j] = id;
+    slot_of[j] = ccls[j] >= 0 ? slot : -1;
+  }
+  if (tid == 0) hdr[0] = next + (int)births, hdr[1] = 0, started[0] = next + (int)births;
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(TRK_THREADS) void trk_commit_kernel(const int* __restrict__ cur, int* __restrict__ mem, const int* __restrict__ slot_of,
+                                                                 const int* __restrict__ keep, long HW, int K) {
+  __shared__ int so[TRK_MAXK], kp[TRK_MAXK];
+  for (int j = (int)threadIdx.x; j < K; j += TRK_THREADS) so[j] = slot_of[j], kp[j] = keep[j];
+  __syncthreads();
+  const long nvec = (HW + 3) >> 2;
+  const unsigned uk = (unsigned)K;
+#pragma unroll
+  for (int it = 0; it < TRK_CVPT; ++it) {
+    const long v = ((long)blockIdx.x * TRK_CVPT + it) * TRK_THREADS + threadIdx.x;
+    if (v >= nvec) continue;
+    const long p0 = 4 * v;
+    int4 c = make_int4(-1, -1, -1, -1);
+    const int4 m = *reinterpret_cast<const int4*>(mem + p0);   // (the state's map is padded: in range)
+    if (VEC && p0 + 4 <= HW) {
+      c = *reinterpret_cast<const int4*>(cur + p0);
+    } else {
+      if (p0 < HW) c.x = cur[p0];
+      if (p0 + 1 < HW) c.y = cur[p0 + 1];
+      if (p0 + 2 < HW) c.z = cur[p0 + 2];
+      if (p0 + 3 < HW) c.w = cur[p0 + 3];
+    }
+    int4 r;                                                    // (the padding has c = -1 and m = -1: it stays -1)
+    int s;
+    s = (unsigned)c.x < uk ? so[c.x] : -1, r.x = s >= 0 ? s : (unsigned)m.x < uk && kp[m.x] ? m.x : -1;
+    s = (unsigned)c.y < uk ? so[c.y] : -1, r.y = s >= 0 ? s : (unsigned)m.y < uk && kp[m.y] ? m.y : -1;
+    s = (unsigned)c.z < uk ? so[c.z] : -1, r.z = s >= 0 ? s : (unsigned)m.z < uk && kp[m.z] ? m.z : -1;
+    s = (unsigned)c.w < uk ? so[c.w] : -1, r.w = s >= 0 ? s : (unsigned)m.w < uk && kp[m.w] ? m.w : -1;
+    if (r.x != m.x || r.y != m.y || r.z != m.z || r.w != m.w) *reinterpret_cast<int4*>(mem + p0) = r;
+  }
+}
+
+static int trk_mem_shape(int H, int W, int K) {
+  if (H <= 0 || W <= 0 || H > 16384 || W > 16384) return -1860;
+  if (K < 1 || K > TRK_MAXK) return -1861;
+  return 0;
+}
+
+extern "C" long stswin_track_memory_state_bytes(int H, int W, int K) {
+  const int e = trk_mem_shape(H, W, K);
+  return e ? e : 4 * trk_mem_layout(H, W, K).words;
+}
+
+extern "C" int stswin_track_memory_reset(void* state, long state_bytes, int H, int W, int K, void* stream) {
+  const int e = trk_mem_shape(H, W, K);
+  if (e) return e;
+  if (state == nullptr) return -1862;
+  const TrkMemLayout l = trk_mem_layout(H, W, K);
+  if (state_bytes < 4 * l.words || ((uintptr_t)state & 15)) return -1863;
+  long blocks = (l.words + TRK_THREADS - 1) / TRK_THREADS;
+  if (blocks > 2048) blocks = 2048;
+  hipLaunchKernelGGL(trk_mem_reset_kernel, dim3((unsigned)blocks), dim3(TRK_THREADS), 0, (hipStream_t)stream, reinterpret_cast<int*>(state), l.cls,
+                     l.area, l.ids, l.age, l.slot_of, l.keep, l.map, l.words);
+  STSWIN_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int stswin_track_memory(const int* components, const long long* rows, const int* total, void* state, long state_bytes, int H, int W,
+                                   int K, int max_gap, int min_iou, int same_class, int min_area, int* ids, int* started, void* stream) {
+  const int e = trk_mem_shape(H, W, K);
+  if (e) return e;
+  if (components == nullptr || rows == nullptr || total == nullptr || state == nullptr || ids == nullptr || started == nullptr) return -1862;
+  const TrkMemLayout l = trk_mem_layout(H, W, K);
+  if (state_bytes < 4 * l.words || ((uintptr_t)state & 15)) return -1863;
+  if (((uintptr_t)components & 3) || ((uintptr_t)rows & 7) || ((uintptr_t)total & 3) || ((uintptr_t)ids & 3) || ((uintptr_t)started & 3)) return -1864;
+  if (min_iou < 0 || min_iou > 1000 || (same_class != 0 && same_class != 1) || min_area < 1) return -1865;
+  if (max_gap < 0 || max_gap > 1000000) return -1866;
+  hipStream_t st = (hipStream_t)stream;
+  int* s = reinterpret_cast<int*>(state);
+  const long HW = (long)H * W, nvec = (HW + 3) >> 2;
+  const bool vec = ((uintptr_t)components & 15) == 0;
+  const unsigned blocks = (unsigned)((nvec + TRK_THREADS * TRK_VPT - 1) / (TRK_THREADS * TRK_VPT));       // <= 2^17
+  const unsigned cblocks = (unsigned)((nvec + TRK_THREADS * TRK_CVPT - 1) / (TRK_THREADS * TRK_CVPT));
+  if (vec)
+    hipLaunchKernelGGL((trk_overlap_kernel<true, false>), dim3(blocks), dim3(TRK_THREADS), 0, st, components, s + l.map, s + l.ov, s + l.list, s + 1, HW, K);
+  else
+    hipLaunchKernelGGL((trk_overlap_kernel<false, false>), dim3(blocks), dim3(TRK_THREADS), 0, st, components, s + l.map, s + l.ov, s + l.list, s + 1, HW, K);
+  hipLaunchKernelGGL(trk_mem_match_kernel, dim3(1), dim3(TRK_THREADS), 0, st, rows, total, s, s + l.cls, s + l.area, s + l.ids, s + l.age,
+                     s + l.slot_of, s + l.keep, s + l.ov, s + l.list, K, max_gap, min_iou, same_class, min_area, ids, started);
+  if (vec)
+    hipLaunchKernelGGL(trk_commit_kernel<true>, dim3(cblocks), dim3(TRK_THREADS), 0, st, components, s + l.map, s + l.slot_of, s + l.keep, HW, K);
+  else
+    hipLaunchKernelGGL(trk_commit_kernel<false>, dim3(cblocks), dim3(TRK_THREADS), 0, st, components, s + l.map, s + l.slot_of, s + l.keep, HW, K);
   STSWIN_CHECK_LAUNCH();
   return 0;
 }

@@ -1591,6 +1591,9 @@ def label_components(labels: torch.Tensor, nc: int, connectivity: int = 8, skip=
     return tuple(out)
 
 
+TRACK_MAX_GAP = 1000000      # stswin_track_memory: the largest max_gap
+
+
 def _track_shape(what: str, H, W, K) -> None:
     for name, v in (("H", H), ("W", W)):
         if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= 16384:
@@ -1603,23 +1606,37 @@ class TrackState:
     """What hip.track_instances keeps between the frames of a sequence, for maps [H][W] and K instances: one device buffer of
     stswin_track_state_bytes(H, W, K) bytes (the previous map, classes, areas and ids, the next id and the overlap counts; layout:
     include/stswin_hip.h).  Made reset: the first frame it sees is all births from id 0.  reset() starts the next sequence (a fill
-    kernel on the current stream, graph-capturable)."""
+    kernel on the current stream, graph-capturable).
 
-    def __init__(self, H: int, W: int, K: int, device):
+    max_gap >= 1 (frames, up to 1000000): the state of the tracker with a memory (utils.instruments.MemoryTracker), which keeps a
+    track alive for up to max_gap frames in which no instance was matched to it - stswin_track_memory_state_bytes(H, W, K) bytes (the
+    tracks' slots, the table of the last frame's ordinals, the overlap counts and the memory map), sized and reset through the memory
+    entry points.  memory=True takes that path with max_gap=0 too, where every unmatched track ends at once."""
+
+    def __init__(self, H: int, W: int, K: int, device, max_gap: int = 0, memory: bool = False):
         _track_shape("TrackState", H, W, K)
+        if isinstance(max_gap, bool) or not isinstance(max_gap, int) or not 0 <= max_gap <= TRACK_MAX_GAP:
+            raise StswinHipError(f"TrackState: max_gap must be an int 0 .. {TRACK_MAX_GAP} (frames), got {max_gap!r}")
+        if not isinstance(memory, bool):
+            raise StswinHipError(f"TrackState: memory must be a bool, got {memory!r}")
         device = _device(device)
         if device.type != "cuda":
             raise StswinHipError("TrackState: the state lives on the GPU (utils.instruments.InstanceTracker is the numpy definition)")
         self.H, self.W, self.K, self.device = H, W, K, device
-        self.bytes = int(load().stswin_track_state_bytes(H, W, K))
+        self.max_gap, self.memory = max_gap, memory or max_gap > 0
+        size = load().stswin_track_memory_state_bytes if self.memory else load().stswin_track_state_bytes
+        self.bytes = int(size(H, W, K))
         if self.bytes < 0:
-            raise StswinHipError(f"TrackState: stswin_track_state_bytes({H}, {W}, {K}) failed with code {self.bytes}")
+            raise StswinHipError(f"TrackState: {size.__name__}({H}, {W}, {K}) failed with code {self.bytes}")
         self.buffer = torch.empty(self.bytes, dtype=torch.uint8, device=device)      # (the caching allocator aligns to 512 bytes)
         self.reset()
 
     def reset(self) -> None:
         with torch.cuda.device(self.device):
-            _check(load().stswin_track_reset(_p(self.buffer), self.bytes, self.H, self.W, self.K, _stream()), "track_reset")
+            if self.memory:
+                _check(load().stswin_track_memory_reset(_p(self.buffer), self.bytes, self.H, self.W, self.K, _stream()), "track_memory_reset")
+            else:
+                _check(load().stswin_track_reset(_p(self.buffer), self.bytes, self.H, self.W, self.K, _stream()), "track_reset")
 
 
 def track_instances(components: torch.Tensor, rows: torch.Tensor, total: torch.Tensor, state: TrackState, min_iou: int = 100,
@@ -1631,7 +1648,11 @@ def track_instances(components: torch.Tensor, rows: torch.Tensor, total: torch.T
     instances below min_area and rows past min(total, K); started = the ids handed out since the state's reset().  Frames go in
     frame order.  utils.instruments.InstanceTracker is the numpy definition, matched bit for bit.  out: the pair (ids, started),
     written in full; with it the call allocates nothing, and it never synchronises (graph-capturable).  Two launches
-    (include/stswin_hip.h, stswin_track_instances)."""
+    (include/stswin_hip.h, stswin_track_instances).
+
+    A state made with max_gap >= 1 (or memory=True) goes through the tracker with a memory instead: a track that no instance was
+    matched to stays alive for up to state.max_gap frames, and instances are matched against the mask each track had when it was last
+    seen.  utils.instruments.MemoryTracker is the numpy definition, matched bit for bit.  Three launches (stswin_track_memory)."""
     if not isinstance(state, TrackState):
         raise StswinHipError(f"track_instances: state must be a hip.TrackState, got {type(state).__name__}")
     H, W, K, dev = state.H, state.W, state.K, state.device
@@ -1662,8 +1683,12 @@ def track_instances(components: torch.Tensor, rows: torch.Tensor, total: torch.T
         for wb, b in bufs[i + 1:]:
             if _same_memory(a, b):
                 raise StswinHipError(f"track_instances: {wb} shares memory with {wa}")
-    _check(load().stswin_track_instances(_p(components), _p(rows), _p(total), _p(state.buffer), state.bytes, H, W, K, min_iou,
-                                         int(same_class), min_area, _p(out[0]), _p(out[1]), _stream()), "track_instances")
+    if state.memory:
+        _check(load().stswin_track_memory(_p(components), _p(rows), _p(total), _p(state.buffer), state.bytes, H, W, K, state.max_gap, min_iou,
+                                          int(same_class), min_area, _p(out[0]), _p(out[1]), _stream()), "track_memory")
+    else:
+        _check(load().stswin_track_instances(_p(components), _p(rows), _p(total), _p(state.buffer), state.bytes, H, W, K, min_iou,
+                                             int(same_class), min_area, _p(out[0]), _p(out[1]), _stream()), "track_instances")
     return tuple(out)
 
 

@@ -408,6 +408,122 @@ class InstanceTracker:
         return ids, self.next
 
 
+class MemoryTracker:
+    """InstanceTracker with a memory: a track whose instrument is out of view stays alive for up to max_gap frames and is matched
+    against the mask it had when it was last seen.  The numpy statement of what hip.track_instances computes on a
+    hip.TrackState(..., max_gap=g), in integers throughout, matched bit for bit (VideoSegmenter(tracks=True, track_max_gap=g)).
+
+    State: next, the next id; the live tracks id -> (class, area, age), age = the frames since the track was last matched; mem
+    [H][W], the id of the track a pixel is remembered for, -1 for none.  update(components int32 [H][W], rows int64 [K][12], total) ->
+    (ids int32 [K], started), one frame:
+      1 an instance takes part if its ordinal j < min(total, K) and rows[j][2] >= min_area, as with InstanceTracker
+      2 ov[t][j] = the pixels with mem == t and components == j, u = area[t] + area[j] - ov with area[t] the track's area at its
+        last sighting, even where other instruments have overwritten part of its remembered mask since
+      3 (t, j) is a candidate iff ov > 0, the classes are equal (dropped with same_class=False) and 1000 ov >= min_iou u
+      4 (t, j) is preferred to (t', j') iff ov u' > ov' u in exact integers, then smaller track id, then smaller j
+      5 repeatedly the most preferred candidate whose t and j are both free is matched: ids[j] = t
+      6 the participants left over take next, next + 1, ... in ascending j; every other entry of ids is -1; started = next
+      7 a matched track takes the instance's class and area and age 0; a new track has age 0; every other live track ages by one and
+        ends when its age exceeds max_gap
+      8 if more than K tracks are live now, lost tracks (age >= 1) end until K are: the largest age first, then the smallest id
+      9 a pixel of a participant j takes ids[j]; any other pixel becomes -1 if its track ended or was matched in this frame (a
+        matched track's mask is replaced, not extended) and stays as it is otherwise: only lost tracks keep a remembered mask
+    With max_gap=0 every unmatched track ends at once and the result is InstanceTracker's wherever track ids ascend with the previous
+    frame's ordinals among equally preferred pairs (the tie-break is the id here, the ordinal there).
+
+    Two properties are deliberate.  An instrument of the same class that moves onto a lost track's remembered place inherits its id:
+    the memory cannot tell a returning tool from one that takes its place.  And there is still no motion model: a track is looked
+    for where it was last seen."""
+
+    def __init__(self, K: int, max_gap: int, min_iou: int = 100, same_class: bool = True, min_area: int = 1):
+        if isinstance(K, bool) or int(K) != K or not 1 <= K <= 1024:
+            raise ValueError(f"MemoryTracker: K is 1 .. 1024, got {K!r}")
+        if isinstance(max_gap, bool) or int(max_gap) != max_gap or not 0 <= max_gap <= 1000000:
+            raise ValueError(f"MemoryTracker: max_gap is an integer 0 .. 1000000 (frames), got {max_gap!r}")
+        if isinstance(min_iou, bool) or int(min_iou) != min_iou or not 0 <= min_iou <= 1000:
+            raise ValueError(f"MemoryTracker: min_iou is an integer 0 .. 1000 (thousandths), got {min_iou!r}")
+        if isinstance(min_area, bool) or int(min_area) != min_area or min_area < 1:
+            raise ValueError(f"MemoryTracker: min_area is an integer >= 1, got {min_area!r}")
+        self.K, self.max_gap, self.min_iou = int(K), int(max_gap), int(min_iou)
+        self.same_class, self.min_area = bool(same_class), int(min_area)
+        self.reset()
+
+    def reset(self) -> None:
+        self.next = 0
+        self.mem = None                   # int64 [H][W]: the track a pixel is remembered for
+        self.live = {}                    # id -> (class, area, age)
+
+    def update(self, components, rows, total):
+        comp = np.asarray(components)
+        rw = np.asarray(rows)
+        K = self.K
+        if comp.ndim != 2 or comp.dtype.kind not in "iu" or min(comp.shape) < 1:
+            raise ValueError(f"MemoryTracker: components are integers [H][W], got {comp.dtype} {comp.shape}")
+        if rw.shape != (K, INSTANCE_ROW) or rw.dtype.kind not in "iu":
+            raise ValueError(f"MemoryTracker: rows are integers [{K}][{INSTANCE_ROW}], got {rw.dtype} {rw.shape}")
+        if self.mem is not None and self.mem.shape != comp.shape:
+            raise ValueError(f"MemoryTracker: a {comp.shape} map after {self.mem.shape} ones (reset() starts a new sequence)")
+        total = int(np.asarray(total).reshape(-1)[0])
+        comp = comp.astype(np.int64)
+        if self.mem is None:
+            self.mem = np.full(comp.shape, -1, dtype=np.int64)
+        n = min(max(total, 0), K)
+        cur = {j: (int(rw[j, 0]), int(rw[j, 2])) for j in range(n) if int(rw[j, 2]) >= self.min_area}
+        cand = []
+        if self.live and cur:
+            both = (self.mem >= 0) & (comp >= 0) & (comp < K)
+            pairs, counts = np.unique(self.mem[both] * K + comp[both], return_counts=True)
+            for key, ov in zip(pairs.tolist(), counts.tolist()):
+                t, j = divmod(key, K)
+                if t not in self.live or j not in cur:
+                    continue
+                ct, at, _ = self.live[t]
+                cc, ac = cur[j]
+                u = at + ac - ov
+                if (ct == cc or not self.same_class) and 1000 * ov >= self.min_iou * u:
+                    cand.append((ov, u, t, j))
+        ids = np.full(K, -1, dtype=np.int32)
+        used_t, used_j = set(), set()
+        while True:                           # the most preferred candidate whose t and j are both still free (Python integers: exact)
+            best = None
+            for c in cand:
+                if c[2] in used_t or c[3] in used_j:
+                    continue
+                if best is None or c[0] * best[1] > best[0] * c[1] or (c[0] * best[1] == best[0] * c[1] and c[2:] < best[2:]):
+                    best = c
+            if best is None:
+                break
+            used_t.add(best[2])
+            used_j.add(best[3])
+            ids[best[3]] = best[2]
+        for j in sorted(cur):
+            if j not in used_j:
+                ids[j] = self.next
+                self.next += 1
+        gone = set(used_t)                    # the tracks whose remembered pixels go: matched (replaced by the instance) or ended
+        live = {int(ids[j]): (cur[j][0], cur[j][1], 0) for j in cur}
+        for t, (ct, at, age) in self.live.items():
+            if t in used_t:
+                continue
+            if age + 1 > self.max_gap:
+                gone.add(t)
+            else:
+                live[t] = (ct, at, age + 1)
+        lost = sorted((t for t in live if live[t][2] >= 1), key=lambda t: (-live[t][2], t))
+        for t in lost[:max(len(live) - K, 0)]:
+            del live[t]
+            gone.add(t)
+        self.live = live
+        if gone:
+            self.mem[np.isin(self.mem, sorted(gone))] = -1
+        of = np.full(K, -1, dtype=np.int64)   # ordinal -> its track, participants only
+        for j in cur:
+            of[j] = int(ids[j])
+        new = np.where((comp >= 0) & (comp < K), of[np.clip(comp, 0, K - 1)], -1)
+        self.mem = np.where(new >= 0, new, self.mem)
+        return ids, self.next
+
+
 class TrackReport:
     """The instance report with identities: from an InstanceReport and the ids of InstanceTracker (hip.track_instances,
     VideoSegmenter(tracks=True).track_report()), row for row:

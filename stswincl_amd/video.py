@@ -301,6 +301,14 @@ class VideoSegmenter:
     utils.instruments.TrackReport over every frame released since reset_metrics(), in instance_report()'s order.  tracks=False:
     every result, launch and captured graph is what it is without the keyword.
 
+    track_max_gap=g (tracks=True; an int >= 0, frames): with g >= 1 a track that no instance was matched to stays alive for up to g
+    frames, and instances are matched against the mask each track had when it was last seen, kept per pixel on the device: a shaft
+    that drops below min_area for a frame, or is hidden by smoke for two, comes back under its id.  The tracker's launches are then the
+    three of the tracker with a memory (utils.instruments.MemoryTracker defines the result; hip.TrackState(..., max_gap=g)), under
+    graph=True three in the captured steady step; frame order, parking, both report modes, masks, ground truth and batch > 1 are as
+    above.  Deliberately, an instrument of the same class that moves onto a lost track's remembered place inherits its id, and there
+    is still no motion model.  track_max_gap=0: every result, launch and captured graph is what it is without the keyword.
+
     masks="frame" | "deferred" (out="labels" | "overlay", both protocols; does not need report; mask_runs=16384): the masks themselves in
     the form their consumers read, run-length encoded in column-major order (COCO's `counts`, the rle field of MOTS files), so that
     storing what was segmented needs no download of a map per frame.  Behind the tracker's launches - or the component launches, or the
@@ -334,7 +342,7 @@ class VideoSegmenter:
                  chroma: str = "replicate", out_format: str = "rgb", report: Optional[str] = None, min_area: int = 1,
                  instances: Optional[int] = None, connectivity: int = 8, instance_skip: Optional[Sequence[int]] = None,
                  tracks: bool = False, track_iou: int = 100, track_same_class: bool = True, masks: Optional[str] = None,
-                 mask_runs: int = 16384):
+                 mask_runs: int = 16384, track_max_gap: int = 0):
         if out not in ("logits", "labels", "overlay"):
             raise StswinHipError(f"out must be 'logits', 'labels' or 'overlay', got {out!r}")
         if pixel_format not in PIXEL_FORMATS:
@@ -384,9 +392,10 @@ class VideoSegmenter:
         classes = model.classifier[-1].out_channels
         self._score_log = DeviceLog(self.device, {"counts": ((3, classes), torch.int32)})     # scores="deferred": a row per scored frame
         self.chain = ReportChain(self.device, classes, protocol, out, report, min_area, instances, connectivity, instance_skip, tracks,
-                                 track_iou, track_same_class, masks, mask_runs)
+                                 track_iou, track_same_class, masks, mask_runs, track_max_gap)
         self.report, self.min_area, self.instances, self.connectivity, self.instance_skip = report, min_area, instances, connectivity, self.chain.instance_skip
         self.tracks, self.track_iou, self.track_same_class = tracks, track_iou, track_same_class
+        self.track_max_gap = track_max_gap
         self.masks, self.mask_runs = masks, mask_runs
         self._gt_table = None
         self._unmatched = None

@@ -131,7 +131,7 @@ class ReportChain:
     captured step may still use them), the tracker's state, the parked frames, the pool of their map copies, and the deferred log."""
 
     def __init__(self, device, classes: int, protocol: str, out: str, report, min_area, instances, connectivity, instance_skip, tracks,
-                 track_iou, track_same_class, masks=None, mask_runs=16384):
+                 track_iou, track_same_class, masks=None, mask_runs=16384, track_max_gap=0):
         if report not in (None, "frame", "deferred"):
             raise StswinHipError(f"report must be None, 'frame' or 'deferred', got {report!r}")
         if report is not None and out == "logits":
@@ -159,6 +159,10 @@ class ReportChain:
             raise StswinHipError(f"tracks must be a bool, got {tracks!r}")
         if not tracks and (track_iou != 100 or track_same_class is not True):
             raise StswinHipError("track_iou and track_same_class belong to tracks=True")
+        if isinstance(track_max_gap, bool) or not isinstance(track_max_gap, int) or not 0 <= track_max_gap <= hip.TRACK_MAX_GAP:
+            raise StswinHipError(f"track_max_gap must be an int 0 .. {hip.TRACK_MAX_GAP} (frames), got {track_max_gap!r}")
+        if not tracks and track_max_gap != 0:
+            raise StswinHipError("track_max_gap belongs to tracks=True")
         if tracks:
             if instances is None:
                 raise StswinHipError("tracks=True follows the instances from frame to frame: it needs instances=K")
@@ -179,6 +183,7 @@ class ReportChain:
         self.rle_ws = None                    # masks: the encoder's workspace (retired ones go where the component map's do)
         self.instances, self.connectivity, self.instance_skip = instances, connectivity, instance_skip
         self.tracks, self.track_iou, self.track_same_class = tracks, track_iou, track_same_class
+        self.track_max_gap = track_max_gap    # tracks: > 0 takes the tracker with a memory (hip.TrackState(..., max_gap))
         self.cc_map = self.cc_ws = None       # instances: the component map and the workspace ...
         self.cc_retired = []                  # ... and the smaller ones they replaced
         self.state = None                     # tracks: the hip.TrackState of the running sequence (made by the first tracked frame)
@@ -287,7 +292,7 @@ class ReportChain:
         sequencer parks has its map copied out and its tensors handed out holding -2; the call that tracks its predecessor tracks it."""
         cc = self._map(b)
         if self.state is None or (self.state.H, self.state.W) != tuple(cc.shape):
-            self.state = hip.TrackState(cc.shape[0], cc.shape[1], self.instances, self.device)
+            self.state = hip.TrackState(cc.shape[0], cc.shape[1], self.instances, self.device, max_gap=self.track_max_gap)
         ids = torch.empty(self.instances, dtype=torch.int32, device=self.device)
         started = torch.empty(1, dtype=torch.int32, device=self.device)
         now = self.order.release(frame)

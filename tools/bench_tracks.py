@@ -21,6 +21,12 @@
                  difference is read against), tracks_over_instances and instances_over_report
 
     python tools/bench_tracks.py [--reps 300] [--windows 7] [--frames 48]   -> one JSON line, also written to profiles/bench_tracks_line.json
+
+--max-gap g (g >= 1) adds the tracker with a memory (stswin_track_memory, VideoSegmenter(track_max_gap=g)) to the same run: per case
+`memory_us_per_frame`, its three launches at max_gap = g on a state of their own, over the same cold maps in the same rotation as
+`tracks_us_per_frame` (the two launches at max_gap = 0) and after one cycle against utils.instruments.MemoryTracker, with
+memory_over_tracks; online gains the path `gap` (tracks=True, track_max_gap=g) beside `tracks`, with gap_over_tracks.  The line then
+goes to profiles/bench_tracks_memory_line.json.
 """
 from __future__ import annotations
 
@@ -86,6 +92,25 @@ def launch_cost(case, a):
            "started_per_cycle": before,
            "buffer_sets": sets, "buffer_bytes": sets * 4 * H * W, "state_bytes": state.bytes,
            "tracks_us_per_frame": round(us, 2), "tracks_us_range": [round(min(w), 2), round(max(w), 2)]}
+    if a.max_gap:
+        mstate = hip.TrackState(H, W, K, "cuda", max_gap=a.max_gap)
+        mhost = instruments.MemoryTracker(K, a.max_gap)
+        for i in range(cycle):                                    # one cycle against the definition
+            ids, started = hip.track_instances(comps[i], rows[i], total[i:i + 1], mstate, out=out)
+            want_ids, want_started = mhost.update(comp[i].cpu().numpy(), rows[i].cpu().numpy(), int(total[i]))
+            if not np.array_equal(ids.cpu().numpy(), want_ids) or int(started[0]) != want_started:
+                raise SystemExit(f"FAIL: the kernels and utils.instruments.MemoryTracker differ at {case}, frame {i}")
+        mstate.reset()
+
+        def memory(k):
+            hip.track_instances(comps[k], rows[k % cycle], total[k % cycle:k % cycle + 1], mstate, out=out)
+
+        w = _windows(memory, sets, a.reps, a.windows)
+        mus = float(np.median(w))
+        res.update({"max_gap": a.max_gap, "memory_started_per_cycle": want_started, "memory_state_bytes": mstate.bytes,
+                    "memory_us_per_frame": round(mus, 2), "memory_us_range": [round(min(w), 2), round(max(w), 2)],
+                    "memory_over_tracks": round(mus / us, 3)})
+        del mstate
     del comps
     torch.cuda.empty_cache()
     lsets = max(2, -(-COLD_BYTES // (H * W)))
@@ -120,6 +145,8 @@ def online(a):
     n = 16
     frames = noisy_frames(np.random.default_rng(a.seed), n, H, W)
     paths = {"instances": dict(instances=K), "tracks": dict(instances=K, tracks=True), "report": {}}
+    if a.max_gap:
+        paths["gap"] = dict(instances=K, tracks=True, track_max_gap=a.max_gap)
     res = {"model": name, "frame": [H, W], "autocast": "bf16", "frames_per_window": a.frames, "windows": a.online_windows, "max_instances": K}
     with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16):
         segs = {p: video.VideoSegmenter(model, graph=True, out="labels", out_size=(H, W), report="deferred", **kw) for p, kw in paths.items()}
@@ -132,6 +159,9 @@ def online(a):
     res["tracks_in_the_sequence"] = len(rep.tracks)
     res["tracks_over_instances"] = round(res["tracks_frames_per_s"] / res["instances_frames_per_s"], 4)
     res["instances_over_report"] = round(res["instances_frames_per_s"] / res["report_frames_per_s"], 4)
+    if a.max_gap:
+        res["max_gap"] = a.max_gap
+        res["gap_over_tracks"] = round(res["gap_frames_per_s"] / res["tracks_frames_per_s"], 4)
     return res
 
 
@@ -145,8 +175,13 @@ def main():
     ap.add_argument("--online-windows", type=int, default=5)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--no-online", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bench_tracks_line.json"))
+    ap.add_argument("--max-gap", type=int, default=0, help="g >= 1: measure the tracker with a memory at max_gap = g as well")
+    ap.add_argument("--out", default=None, help="profiles/bench_tracks_line.json, with --max-gap profiles/bench_tracks_memory_line.json")
     a = ap.parse_args()
+    if not 0 <= a.max_gap <= hip.TRACK_MAX_GAP:
+        raise SystemExit(f"--max-gap is 0 .. {hip.TRACK_MAX_GAP}")
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "bench_tracks_memory_line.json" if a.max_gap else "bench_tracks_line.json")
     if not torch.cuda.is_available():
         raise SystemExit("bench_tracks.py measures on the GPU: no device found")
     res = {"launch": []}
