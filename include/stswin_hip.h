@@ -713,6 +713,37 @@ int stswin_rle_encode(const void* map /*[n][H][W]*/, int elem_bytes /*1: uint8, 
 /* the geometry of stswin_rle_encode (the tests place their shapes around it): which = 0: rows of a segment (32), 1: columns of a
  * workgroup's band (256), 2: pixels per thread and row (16 for uint8; a thread of an int32 map takes 4); anything else: -1. */
 int stswin_rle_geometry(int which);
+/* ---- boundary scores (stswincl_amd/utils/boundary.py boundary_counts, VideoSegmenter(boundary=...)): gt int64 [n][H][W] and pred uint8
+ * [n][H][W] -> out int32 [n][nc][2][2 + bins], what the normalised surface distance and the Hausdorff distance are made of.  For a map M
+ * and a class c < nc the contour B_c(M) is the set of pixels with M == c that have a 4-neighbour with M != c, a neighbour outside the
+ * image counting as different (mask & ~binary_erosion(mask)); a value outside 0 .. nc-1 belongs to no class.  Row out[f][c][d], d = 0:
+ * the contour of gt measured against the one of pred, d = 1: pred against gt; d2(p) = the minimum over the pixels q of the other contour
+ * of |p - q|^2, an exact integer:
+ *     0: the number of pixels of the own contour          1: the maximum of d2 over them, -1 when either contour is empty
+ *     2 + k, k < bins - 1: the own contour pixels whose ceil(sqrt(d2)) == k (the smallest k with k^2 >= d2)
+ *     2 + bins - 1: those with ceil(sqrt(d2)) >= bins - 1           (the histogram is all zero when either contour is empty)
+ * The rows of the classes whose bit of skip_mask is set are all zero.  out is written in full by the call (a fill kernel on the stream,
+ * no memset node); nothing needs clearing beforehand.  workspace: caller-owned, 8-byte aligned, >= stswin_boundary_scratch(n, H, W, nc)
+ * = 16 n (S W + 1) + 2 n H W (2 nc + 1) bytes with S = ceil(H / 64) (per map, segment of 64 rows and column the classes with a contour
+ * pixel there, uint64 [2][n][S][W]; each map's classes, uint64 [2][n]; per map and class the column distances uint16
+ * [2][n][nc][H][W]; the contour codes uint8 [2][n][H][W]);
+ * nothing in it needs clearing and nothing survives the call.  Five launches whatever nc and the maps hold - fill, mark the contours,
+ * classes per segment, column distances, query - no synchronisation, no allocation, no host read (graph-capturable); no kernel waits
+ * on another workgroup.  Integer arithmetic and integer atomics only (add and max into out, or into the workspace): exact, independent of the order (bit-reproducible); the
+ * float square root only seeds the ceiling, integer comparisons decide it.  gt 8-byte and out 4-byte aligned, pred at any address, any
+ * W; 1 <= H, W <= 16384 (d2 < 2^30), 1 <= nc <= 64, 2 <= bins <= 256.  The buffers must not overlap (the host wrapper checks).
+ * Errors, before anything is launched: -1870 n, H or W <= 0, or H or W > 16384 (or more workgroups than a grid holds; also what
+ * stswin_boundary_scratch returns for such a shape); -1871 gt, pred, out or workspace NULL; -1872 nc outside 1 .. 64 (from
+ * stswin_boundary_scratch too); -1873 bins outside 2 .. 256; -1874 workspace_bytes too small or workspace not 8-byte aligned; -1875 gt
+ * not 8-byte or out not 4-byte aligned. */
+long stswin_boundary_scratch(int n, int H, int W, int nc);
+int stswin_boundary_counts(const long long* gt /*[n][H][W]*/, const unsigned char* pred /*[n][H][W]*/, int* out /*[n][nc][2][2+bins]*/,
+                           int n, int H, int W, int nc, int bins, long skip_mask, void* workspace, long workspace_bytes, void* stream);
+/* the geometry of stswin_boundary_counts (the tests place their shapes around it): which = 0, 1: height and width in pixels of the tile
+ * a workgroup of the query pass owns (16, 64), 2: the columns of a workgroup of the column pass (64), 3: the rows of a segment of the
+ * column pass (64); anything else: -1.  The query pass
+ * gathers in LDS while nc (2 + bins) <= 8192 words and adds to out directly above that. */
+int stswin_boundary_geometry(int which);
 /* ---- frames as a video source delivers them (stswincl_amd/utils/yuv.py, VideoSegmenter(pixel_format=..., out_format="nv12")):
  * stswin_yuv_to_rgb makes the HWC RGB frame uint8 [n][Hs][Ws][3] that stswin_frame_ingest and stswin_labels_overlay read,
  * stswin_rgb_to_nv12 turns such a frame into NV12.  Hs (NV12) and Ws are even.

@@ -2793,6 +2793,291 @@ extern "C" int stswin_rle_encode(const void* map, int elem_bytes, int* runs, int
   return 0;
 }
 
+// Boundary scores (stswincl_amd/utils/boundary.py, boundary_counts, states the result; VideoSegmenter(boundary=...)): per class the
+// exact squared Euclidean distance from every contour pixel of one label map to the nearest contour pixel of the other, as counts
+// per ceil(distance) and the maximum, in both directions.  Five launches whatever nc and the maps hold:
+//   1 bnd_fill_kernel    out: rows of skipped classes 0, elsewhere count 0, maximum -1, histogram 0
+//   2 bnd_mark_kernel    both maps -> code maps uint8 [2][n][H][W]: the pixel's class where it is a contour pixel of a scored class
+//                        (a 4-neighbour holds another value, or lies outside the image), BND_NONE elsewhere
+//   3 bnd_mask_kernel    per map, column and segment of BND_SEG rows the classes with a contour pixel there, one bit each: the table
+//                        uint64 [2][n][S][W] that lets the next pass find the nearest contour row outside a segment without walking
+//                        the column
+//   4 bnd_column_kernel  per map and scored class the plane g uint16 [H][W]: the vertical distance to the nearest contour pixel of the
+//                        class in the column, BND_FAR without one.  A thread owns one segment of one column of one plane, lanes are
+//                        adjacent columns (coalesced); no sweep carries anything from row to row
+//   5 bnd_query_kernel   a workgroup owns a tile of BND_TH x BND_TW pixels of one code map, a wave rows of it.  For a contour pixel (y, x)
+//                        of class c, best = min over dx of dx^2 + g[y][x +- dx]^2 in the other map's plane c, dx = 0, 1, ... while
+//                        dx^2 < best: exact, because a nearest contour pixel in column x' is the nearest one of that column.  Every
+//                        lane first widens for its own pixel up to BND_NEAR columns, which settles contours that lie close; the
+//                        pixels left over the wave takes one after the other and searches together, lane l at dx = base + l, a wave
+//                        minimum, base += 64.  A class the other map has no contour of (present) is not searched for at all.  Count, maximum and histogram gather in an LDS copy of the tile's rows of `out` when nc
+//                        (2 + bins) <= BND_LDS_WORDS (LDS = true) and leave as one atomic per non-zero word, else they go out directly
+// Integer arithmetic and integer atomics (add, max) only.  No kernel uses scratch memory or waits on another workgroup.
+#define BND_TH 16
+#define BND_TW 64
+#define BND_THREADS 256
+#define BND_COLS 64
+#define BND_SEG 64
+#define BND_NEAR 8
+#define BND_LDS_WORDS 8192
+#define BND_NONE 255u
+#define BND_FAR 65535u
+#define BND_INF 0x7fffffff
+
+__global__ __launch_bounds__(BND_THREADS) void bnd_fill_kernel(int* __restrict__ out, long words, int nc, int row, unsigned long long skip,
+                                                               unsigned long long* __restrict__ present, int maps) {
+  const long i = (long)blockIdx.x * BND_THREADS + threadIdx.x;
+  if (i < maps) present[i] = 0ull;                                        // (bnd_mask_kernel gathers into them)
+  if (i >= words) return;
+  const int j = (int)(i % row), c = (int)((i / (2 * row)) % nc);
+  out[i] = (skip >> c & 1ull) ? 0 : j == 1 ? -1 : 0;
+}
+
+// the class of value v, BND_NONE for a value outside 0 .. nc-1 or a skipped class
+__device__ __forceinline__ unsigned bnd_class(long long v, int nc, unsigned long long skip) {
+  return v >= 0 && v < nc && !(skip >> v & 1ull) ? (unsigned)v : BND_NONE;
+}
+
+template <typename T>
+__device__ __forceinline__ unsigned bnd_code(const T* __restrict__ m, int y, int x, int H, int W, int nc, unsigned long long skip) {
+  const T* p = m + (long)y * W + x;
+  const T v = *p;
+  const unsigned c = bnd_class((long long)v, nc, skip);
+  if (c == BND_NONE) return BND_NONE;
+  const bool edge = y == 0 || y == H - 1 || x == 0 || x == W - 1 || p[-W] != v || p[W] != v || p[-1] != v || p[1] != v;
+  return edge ? c : BND_NONE;
+}
+
+__global__ __launch_bounds__(BND_THREADS) void bnd_mark_kernel(const long long* __restrict__ gt, const unsigned char* __restrict__ pred,
+                                                               unsigned char* __restrict__ codes, long pixels, int n, int H, int W, int nc,
+                                                               unsigned long long skip) {
+  const long i = (long)blockIdx.x * BND_THREADS + threadIdx.x;           // (f, y, x)
+  if (i >= pixels) return;
+  const long hw = (long)H * W;
+  const long f = i / hw, r = i - f * hw;
+  const int y = (int)(r / W), x = (int)(r - (long)y * W);
+  codes[i] = (unsigned char)bnd_code(gt + f * hw, y, x, H, W, nc, skip);
+  codes[pixels + i] = (unsigned char)bnd_code(pred + f * hw, y, x, H, W, nc, skip);
+}
+
+// bit r of the result: row y0 + r of the column at cm (stride W) holds code c; rows from H on hold nothing.  64 independent loads.
+__device__ __forceinline__ unsigned long long bnd_seg_bits(const unsigned char* __restrict__ cm, int y0, int H, int W, unsigned c) {
+  unsigned long long m = 0;
+#pragma unroll
+  for (int r = 0; r < BND_SEG; ++r)
+    if (y0 + r < H && cm[(long)(y0 + r) * W] == c) m |= 1ull << r;
+  return m;
+}
+
+// grid: (map m, frame f, segment s of BND_SEG rows, band of BND_COLS columns), the band fastest: table[m n + f][s][x] = the classes
+// that have a contour pixel in the segment's rows of column x, one bit per class; present[m n + f] = the classes of the whole map
+__global__ __launch_bounds__(BND_COLS) void bnd_mask_kernel(const unsigned char* __restrict__ codes, unsigned long long* __restrict__ table,
+                                                            unsigned long long* present, int H, int W, int S, int bands) {
+  unsigned b = blockIdx.x;
+  const int band = (int)(b % (unsigned)bands);
+  b /= (unsigned)bands;
+  const int s = (int)(b % (unsigned)S);
+  const long mf = (long)(b / (unsigned)S);
+  const int x = band * BND_COLS + (int)threadIdx.x;
+  const unsigned char* cm = codes + mf * H * W + x;
+  unsigned long long m = 0;
+  if (x < W) {
+#pragma unroll 16
+    for (int r = 0; r < BND_SEG; ++r) {
+      const int y = s * BND_SEG + r;
+      const unsigned code = y < H ? cm[(long)y * W] : BND_NONE;
+      if (code != BND_NONE) m |= 1ull << code;
+    }
+    table[(mf * S + s) * W + x] = m;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m |= __shfl_xor(m, o);                 // the workgroup is one wave: its classes, then the map's
+  if (threadIdx.x == 0 && m) atomicOr(present + mf, m);
+}
+
+// grid: (map m, frame f, class c, segment s, band of BND_COLS columns), the band fastest.  A thread owns BND_SEG rows of one column of
+// one plane: its own rows' contour pixels of the class as a bit mask, the nearest one above and below the segment through the table
+// (the first segment in that direction whose bit c is set, then that segment's rows), and every row's distance from bit counts.
+__global__ __launch_bounds__(BND_COLS) void bnd_column_kernel(const unsigned char* __restrict__ codes, const unsigned long long* __restrict__ table,
+                                                              unsigned short* __restrict__ g, int H, int W, int nc, int S, int bands,
+                                                              unsigned long long skip) {
+  unsigned b = blockIdx.x;
+  const int band = (int)(b % (unsigned)bands);
+  b /= (unsigned)bands;
+  const int s = (int)(b % (unsigned)S);
+  b /= (unsigned)S;
+  const int c = (int)(b % (unsigned)nc);
+  const long mf = (long)(b / (unsigned)nc);                               // m n + f
+  const int x = band * BND_COLS + (int)threadIdx.x;
+  if ((skip >> c & 1ull) || x >= W) return;                               // (a skipped class has no contour pixel: nobody reads its plane)
+  const unsigned char* cm = codes + mf * H * W + x;
+  const unsigned long long* tb = table + mf * S * W + x;
+  unsigned short* gp = g + (mf * nc + c) * (long)H * W + x;
+  const int y0 = s * BND_SEG;
+  const unsigned long long own = (tb[(long)s * W] >> c & 1ull) ? bnd_seg_bits(cm, y0, H, W, (unsigned)c) : 0ull;
+  int above = -1, below = -1;                                             // the nearest contour row outside the segment, -1: none
+  for (int t = s - 1; t >= 0; --t)
+    if (tb[(long)t * W] >> c & 1ull) {
+      above = t * BND_SEG + 63 - __clzll((long long)bnd_seg_bits(cm, t * BND_SEG, H, W, (unsigned)c));
+      break;
+    }
+  for (int t = s + 1; t < S; ++t)
+    if (tb[(long)t * W] >> c & 1ull) {
+      below = t * BND_SEG + __ffsll((long long)bnd_seg_bits(cm, t * BND_SEG, H, W, (unsigned)c)) - 1;
+      break;
+    }
+#pragma unroll 8
+  for (int r = 0; r < BND_SEG; ++r) {
+    const int y = y0 + r;
+    if (y >= H) break;
+    const unsigned long long lo = own & (~0ull >> (63 - r)), hi = own >> r;     // the segment's contour rows <= y, and >= y from bit 0
+    const unsigned up = lo ? (unsigned)(r - (63 - __clzll((long long)lo))) : above >= 0 ? (unsigned)(y - above) : BND_FAR;
+    const unsigned down = hi ? (unsigned)(__ffsll((long long)hi) - 1) : below >= 0 ? (unsigned)(below - y) : BND_FAR;
+    gp[(long)y * W] = (unsigned short)min(up, down);
+  }
+}
+
+// the smallest k with k k >= d2 (d2 < 2^30): the float root seeds, integer comparisons decide
+__device__ __forceinline__ int bnd_ceil_sqrt(int d2) {
+  int k = (int)sqrtf((float)d2);
+  while (k > 0 && (k - 1) * (k - 1) >= d2) --k;
+  while (k * k < d2) ++k;
+  return k;
+}
+
+// grid: (map m, frame f, tile row, tile column), the tile column fastest; m is the direction d of the rows it adds to
+template <bool LDS>
+__global__ __launch_bounds__(BND_THREADS) void bnd_query_kernel(const unsigned char* __restrict__ codes, const unsigned short* __restrict__ g,
+                                                                const unsigned long long* __restrict__ present, int* out, int n, int H,
+                                                                int W, int nc, int bins, int tx, int ty) {
+  __shared__ int tab[LDS ? BND_LDS_WORDS : 1];
+  const int row = 2 + bins;
+  unsigned b = blockIdx.x;
+  const int bx = (int)(b % (unsigned)tx);
+  b /= (unsigned)tx;
+  const int by = (int)(b % (unsigned)ty);
+  b /= (unsigned)ty;
+  const int f = (int)(b % (unsigned)n), m = (int)(b / (unsigned)n);
+  if (LDS) {
+    for (int i = (int)threadIdx.x; i < nc * row; i += BND_THREADS) tab[i] = i % row == 1 ? -1 : 0;
+    __syncthreads();
+  }
+  const long hw = (long)H * W;
+  const unsigned char* cm = codes + ((long)m * n + f) * hw;
+  const unsigned short* other = g + ((long)(1 - m) * n + f) * nc * hw;
+  int* of = out + ((long)f * nc * 2 + m) * row;                           // class c's row of this direction: of + 2 c row
+  const unsigned long long there = present[(long)(1 - m) * n + f];       // the classes the other map has a contour of
+  const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;   // BND_TW is the wave's width: a wave owns rows of the tile
+  const int x = bx * BND_TW + lane;
+  for (int yy = wave; yy < BND_TH; yy += BND_THREADS / 64) {
+    const int y = by * BND_TH + yy;
+    if (y >= H) break;                                                    // (the whole wave)
+    const unsigned code = x < W ? cm[(long)y * W + x] : BND_NONE;
+    // every lane searches for its own pixel up to BND_NEAR columns to both sides; that settles the pixel when best <= (BND_NEAR + 1)^2
+    int mine = BND_INF;
+    bool far = false;
+    if (code != BND_NONE && (there >> code & 1ull)) {
+      const unsigned short* gr = other + (long)code * hw + (long)y * W;
+      const int g0 = gr[x];
+      if (g0 != (int)BND_FAR) mine = g0 * g0;
+      int dx = 1;
+      for (; dx <= BND_NEAR && dx * dx < mine; ++dx) {
+        const int l = x - dx >= 0 ? (int)gr[x - dx] : (int)BND_FAR, r = x + dx < W ? (int)gr[x + dx] : (int)BND_FAR;
+        const int v = min(l, r);
+        if (v != (int)BND_FAR) mine = min(mine, dx * dx + v * v);
+      }
+      far = dx * dx < mine && (x - dx >= 0 || x + dx < W);               // columns from dx on could still be nearer
+    }
+    unsigned long long todo = __ballot(far);
+    while (todo) {                                                        // the others one after the other, the wave searches together
+      const int i = __ffsll((long long)todo) - 1;
+      todo &= todo - 1;
+      const unsigned c = (unsigned)__shfl((int)code, i);
+      const int xp = bx * BND_TW + i;
+      const unsigned short* gr = other + (long)c * hw + (long)y * W;
+      int best = __shfl(mine, i);
+      for (int base = BND_NEAR + 1;; base += 64) {                        // lane l takes the columns xp - dx and xp + dx, dx = base + l
+        const int dx = base + lane;
+        const int l = xp - dx >= 0 ? (int)gr[xp - dx] : (int)BND_FAR, r = xp + dx < W ? (int)gr[xp + dx] : (int)BND_FAR;
+        const int v = min(l, r);
+        int cand = v == (int)BND_FAR ? BND_INF : dx * dx + v * v;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) cand = min(cand, __shfl_xor(cand, o));
+        best = min(best, cand);
+        const int nb = base + 64;                                         // every column further out has dx >= nb
+        if (nb * nb >= best || (xp - nb < 0 && xp + nb >= W)) break;
+      }
+      if (lane == i) mine = best;
+    }
+    if (code != BND_NONE) {
+      int* t = LDS ? tab + (int)code * row : of + 2 * (long)code * row;
+      atomicAdd(t, 1);
+      if (mine != BND_INF) {
+        atomicMax(t + 1, mine);
+        atomicAdd(t + 2 + min(bnd_ceil_sqrt(mine), bins - 1), 1);
+      }
+    }
+  }
+  if (LDS) {
+    __syncthreads();
+    for (int i = (int)threadIdx.x; i < nc * row; i += BND_THREADS) {
+      const int v = tab[i], c = i / row, j = i - c * row;
+      if (j == 1) {
+        if (v >= 0) atomicMax(of + 2 * (long)c * row + 1, v);
+      } else if (v != 0) {
+        atomicAdd(of + 2 * (long)c * row + j, v);
+      }
+    }
+  }
+}
+
+extern "C" int stswin_boundary_geometry(int which) {
+  return which == 0 ? BND_TH : which == 1 ? BND_TW : which == 2 ? BND_COLS : which == 3 ? BND_SEG : -1;
+}
+
+extern "C" long stswin_boundary_scratch(int n, int H, int W, int nc) {
+  if (n <= 0 || H <= 0 || W <= 0 || H > 16384 || W > 16384) return -1870;
+  if (nc < 1 || nc > 64) return -1872;
+  const long S = (H + BND_SEG - 1) / BND_SEG;
+  // the table uint64 [2][n][S][W], the maps' classes uint64 [2][n], the planes uint16 [2][n][nc][H][W], the codes uint8 [2][n][H][W]
+  return 16 * (long)n * (S * W + 1) + 2 * (long)n * H * W * (2 * (long)nc + 1);
+}
+
+extern "C" int stswin_boundary_counts(const long long* gt, const unsigned char* pred, int* out, int n, int H, int W, int nc, int bins,
+                                      long skip_mask, void* workspace, long workspace_bytes, void* stream) {
+  if (n <= 0 || H <= 0 || W <= 0 || H > 16384 || W > 16384) return -1870;
+  if (gt == nullptr || pred == nullptr || out == nullptr || workspace == nullptr) return -1871;
+  if (nc < 1 || nc > 64) return -1872;
+  if (bins < 2 || bins > 256) return -1873;
+  if (workspace_bytes < stswin_boundary_scratch(n, H, W, nc) || ((uintptr_t)workspace & 7)) return -1874;
+  if (((uintptr_t)gt & 7) || ((uintptr_t)out & 3)) return -1875;
+  const long pixels = (long)n * H * W, words = (long)n * nc * 2 * (2 + bins);
+  const int bands = (W + BND_COLS - 1) / BND_COLS, tx = (W + BND_TW - 1) / BND_TW, ty = (H + BND_TH - 1) / BND_TH;
+  const long fill_blocks = (words + BND_THREADS - 1) / BND_THREADS, mark_blocks = (pixels + BND_THREADS - 1) / BND_THREADS;
+  const int S = (H + BND_SEG - 1) / BND_SEG;
+  const long mask_blocks = 2 * (long)n * S * bands, col_blocks = mask_blocks * nc, query_blocks = 2 * (long)n * tx * ty;
+  if (fill_blocks > 0x7fffffffL || mark_blocks > 0x7fffffffL || col_blocks > 0x7fffffffL || query_blocks > 0x7fffffffL) return -1870;
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned long long skip = (unsigned long long)skip_mask;
+  unsigned long long* table = reinterpret_cast<unsigned long long*>(workspace);
+  unsigned long long* present = table + 2 * (long)n * S * W;
+  unsigned short* g = reinterpret_cast<unsigned short*>(present + 2 * n);
+  unsigned char* codes = reinterpret_cast<unsigned char*>(g) + 4 * pixels * nc;
+  hipLaunchKernelGGL(bnd_fill_kernel, dim3((unsigned)fill_blocks), dim3(BND_THREADS), 0, st, out, words, nc, 2 + bins, skip, present, 2 * n);
+  hipLaunchKernelGGL(bnd_mark_kernel, dim3((unsigned)mark_blocks), dim3(BND_THREADS), 0, st, gt, pred, codes, pixels, n, H, W, nc, skip);
+  hipLaunchKernelGGL(bnd_mask_kernel, dim3((unsigned)mask_blocks), dim3(BND_COLS), 0, st, (const unsigned char*)codes, table, present, H, W, S, bands);
+  hipLaunchKernelGGL(bnd_column_kernel, dim3((unsigned)col_blocks), dim3(BND_COLS), 0, st, (const unsigned char*)codes,
+                     (const unsigned long long*)table, g, H, W, nc, S, bands, skip);
+  if (nc * (2 + bins) <= BND_LDS_WORDS)
+    hipLaunchKernelGGL(bnd_query_kernel<true>, dim3((unsigned)query_blocks), dim3(BND_THREADS), 0, st, (const unsigned char*)codes,
+                       (const unsigned short*)g, (const unsigned long long*)present, out, n, H, W, nc, bins, tx, ty);
+  else
+    hipLaunchKernelGGL(bnd_query_kernel<false>, dim3((unsigned)query_blocks), dim3(BND_THREADS), 0, st, (const unsigned char*)codes,
+                       (const unsigned short*)g, (const unsigned long long*)present, out, n, H, W, nc, bins, tx, ty);
+  STSWIN_CHECK_LAUNCH();
+  return 0;
+}
+
 // Frames as a video source delivers them (stswincl_amd/utils/yuv.py states the arithmetic): NV12 or UYVY -> the HWC RGB frame that
 // stswin_frame_ingest and stswin_labels_overlay read, and RGB -> NV12.  matrix int32 [3][4]: out_c = clamp((m[c][0] t0 + m[c][1] t1 +
 // m[c][2] t2 + m[c][3]) >> 14, 0, 255) in int32 (|sum| < 2^25).  A thread owns YUV_PPT = 8 (wide body) or 2 (byte body) consecutive

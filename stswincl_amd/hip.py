@@ -1760,6 +1760,88 @@ def rle_encode(maps: torch.Tensor, cap: int, out=None, workspace: Optional[torch
     return tuple(out)
 
 
+def boundary_geometry():
+    """(rows, columns of the tile a workgroup of the query pass owns, columns of a workgroup and rows of a segment of the column pass)
+    of stswin_boundary_counts."""
+    return tuple(int(load().stswin_boundary_geometry(i)) for i in range(4))
+
+
+def boundary_scratch(n: int, H: int, W: int, nc: int) -> int:
+    """Bytes of workspace hip.boundary_counts needs for maps [n][H][W] of nc classes: 16 n (ceil(H / 64) W + 1) + 2 n H W (2 nc + 1)."""
+    b = int(load().stswin_boundary_scratch(n, H, W, nc))
+    if b == -1872:
+        raise StswinHipError(f"boundary_counts: nc = {nc!r} classes, the kernel takes 1 .. 64")
+    if b < 0:
+        raise StswinHipError(f"boundary_counts: {n} maps of {H} x {W}, the kernel takes up to 16384 x 16384")
+    return b
+
+
+def boundary_counts(gt: torch.Tensor, pred: torch.Tensor, nc: int, bins: int = 32, skip=(), out: Optional[torch.Tensor] = None,
+                    workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """int64 gt [n][H][W] and uint8 pred [n][H][W] -> int32 [n][nc][2][2 + bins]: per frame, class and direction (0: gt's contour
+    measured against pred's, 1: pred's against gt's) the size of the contour, the largest squared distance to the other contour (-1:
+    either one is empty) and the contour pixels per ceil(distance), the last bin open-ended; the rows of the classes in `skip` are zero
+    (utils.boundary.boundary_counts is the numpy definition, matched bit for bit; utils.boundary.BoundaryScores reads NSD and
+    Hausdorff distances from the rows).  out: written in full; workspace: uint8, >= boundary_scratch(n, H, W, nc) bytes.  With both
+    given the call allocates nothing, and it never synchronises (graph-capturable).  Five launches.  Returns out
+    (include/stswin_hip.h, stswin_boundary_counts)."""
+    for what, t, dt in (("gt", gt, torch.int64), ("pred", pred, torch.uint8)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt or t.dim() != 3 or not t.is_contiguous():
+            got = f"{t.dtype} {tuple(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__
+            raise StswinHipError(f"boundary_counts: {what} must be contiguous {dt} [n][H][W], got {got}")
+        if not t.is_cuda:
+            raise StswinHipError(f"boundary_counts: {what} must be on the GPU (no CPU path exists; utils.boundary.boundary_counts is the "
+                                 "numpy definition)")
+    n, H, W = gt.shape
+    if n <= 0 or H <= 0 or W <= 0:
+        raise StswinHipError(f"boundary_counts: empty gt {tuple(gt.shape)}")
+    if tuple(pred.shape) != (n, H, W) or pred.device != gt.device:
+        raise StswinHipError(f"boundary_counts: pred must be [{n}][{H}][{W}] on {gt.device} as gt is, got {tuple(pred.shape)} on {pred.device}")
+    if H > 16384 or W > 16384:
+        raise StswinHipError(f"boundary_counts: a {H} x {W} gt, the kernel takes up to 16384 x 16384")
+    if isinstance(nc, bool) or not isinstance(nc, int) or not 1 <= nc <= 64:
+        raise StswinHipError(f"boundary_counts: nc = {nc!r} classes, the kernel takes 1 .. 64")
+    if isinstance(bins, bool) or not isinstance(bins, int) or not 2 <= bins <= 256:
+        raise StswinHipError(f"boundary_counts: bins must be an int 2 .. 256, got {bins!r}")
+    try:
+        skip = tuple(skip)
+    except TypeError:
+        skip = (skip,)
+    if any(isinstance(c, bool) or not isinstance(c, int) or not 0 <= c <= 63 for c in skip):
+        raise StswinHipError(f"boundary_counts: skip holds classes 0 .. 63, got {skip!r}")
+    dev = gt.device
+    shape = (n, nc, 2, 2 + bins)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.int32, device=dev)
+    elif not isinstance(out, torch.Tensor) or out.dtype != torch.int32 or tuple(out.shape) != shape or not out.is_contiguous() or out.device != dev:
+        got = f"{out.dtype} {tuple(out.shape)} on {out.device}" if isinstance(out, torch.Tensor) else type(out).__name__
+        raise StswinHipError(f"boundary_counts: out must be contiguous torch.int32 [{n}][{nc}][2][{2 + bins}] on {dev}, got {got}")
+    need = boundary_scratch(n, H, W, nc)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.dim() != 1 or not workspace.is_contiguous()
+          or workspace.device != dev):
+        got = f"{workspace.dtype} {tuple(workspace.shape)} on {workspace.device}" if isinstance(workspace, torch.Tensor) else type(workspace).__name__
+        raise StswinHipError(f"boundary_counts: workspace must be contiguous uint8 [bytes] on {dev}, got {got}")
+    elif workspace.numel() < need:
+        raise StswinHipError(f"boundary_counts: a workspace of {workspace.numel()} bytes, {n} maps of {H} x {W} and {nc} classes need {need}")
+    elif workspace.data_ptr() % 8:
+        raise StswinHipError("boundary_counts: workspace must be 8-byte aligned")
+    bufs = (("gt", gt), ("pred", pred), ("out", out), ("workspace", workspace))
+    for i, (wa, a) in enumerate(bufs):
+        for wb, b in bufs[i + 1:]:
+            if _same_memory(a, b):
+                raise StswinHipError(f"boundary_counts: {wb} shares memory with {wa}")
+    mask = 0
+    for c in skip:
+        mask |= 1 << c
+    if mask >= 1 << 63:                      # (the mask travels in a C long: bit 63 is its sign bit)
+        mask -= 1 << 64
+    _check(load().stswin_boundary_counts(_p(gt), _p(pred), _p(out), n, H, W, nc, bins, mask, _p(workspace), workspace.numel(), _stream()),
+           "boundary_counts")
+    return out
+
+
 YUV_NV12, YUV_UYVY = 0, 1                    # stswin_yuv_to_rgb's `format` (plain integers in the header's comment, not #defines)
 YUV_REPLICATE, YUV_LINEAR = 0, 1               # ... and its `chroma`
 _YUV_FORMATS = {"nv12": YUV_NV12, "uyvy": YUV_UYVY}

@@ -195,7 +195,7 @@ class VideoSegmenter:
     """Segment video sequences with an eval-mode TswinPlus, one result per frame, each frame's ResNet features computed once.
 
     seg = VideoSegmenter(model, batch=1, out="logits" | "labels" | "overlay", out_size=None, graph=False, report=None, instances=None,
-                         tracks=False, masks=None)
+                         tracks=False, masks=None, boundary=None)
 
     push(frames, gt=None) takes uint8 RGB frames [n][Hs][Ws][3] (or one [Hs][Ws][3]; torch tensor on the model's GPU or the CPU, or
     a numpy array; NV12 or UYVY frames with pixel_format, below) and returns [(frame_index, result), ...] for the frames whose clip is now complete.  finish() runs what is
@@ -332,6 +332,21 @@ class VideoSegmenter:
     object's COCO RLE, mots_lines(sequence) - joined with instance_report() when instances and report="deferred" are set and with
     track_report() when tracks is.  masks=None: every result, launch and captured graph is what it is without the keyword.
 
+    boundary="deferred" (out="labels" | "overlay", both protocols, every scores mode; boundary_bins=32, boundary_skip=None): the contours
+    scored beside the regions.  For every frame pushed with gt - int64, or as stored with gt_table - the five launches of
+    hip.boundary_counts (utils.boundary.boundary_counts defines the result) follow the launch that makes the frame's labels, on the same
+    stream and in the segmenter's own workspace, about 2 H W (2 classes + 1) bytes, allocated once per frame size: per class and direction the
+    size of the contour, the largest squared distance to the other map's contour and the contour pixels per whole-pixel distance up to
+    boundary_bins - 2, exact integers.  The row goes into a device log beside the score log, with its sequence ordinals: no download
+    and no synchronisation, and the results of push are unchanged.  Under graph=True scored labels are made after the replay, and so
+    are the rows; the captured step is what it is without the keyword.  boundary_scores(names=None) downloads the log once and returns
+    utils.boundary.BoundaryScores: nsd(tau), the normalised surface distance of ROBUST-MIS and "Metrics Reloaded" (MONAI's
+    compute_surface_dice at whole-pixel tolerances), hausdorff(), hausdorff_percentile(q) and their aggregates, over the classes
+    present in the ground truth and not in boundary_skip (default: what `transparent` defaults to, (0,) for endovis18 and (classes - 1,)
+    for cadis; a ground-truth value that is no class of the model, such as an ignore label that was not remapped, belongs to no
+    contour but still bounds its neighbours' contours).  reset() keeps the log, reset_metrics() clears it.  boundary=None: every
+    result, launch and captured graph is what it is without the keyword.
+
     Runs under torch.no_grad().  Refuses (StswinHipError): a model in train mode, a model or frames not on the GPU, a frame size
     that differs from the earlier frames'."""
 
@@ -342,7 +357,8 @@ class VideoSegmenter:
                  chroma: str = "replicate", out_format: str = "rgb", report: Optional[str] = None, min_area: int = 1,
                  instances: Optional[int] = None, connectivity: int = 8, instance_skip: Optional[Sequence[int]] = None,
                  tracks: bool = False, track_iou: int = 100, track_same_class: bool = True, masks: Optional[str] = None,
-                 mask_runs: int = 16384, track_max_gap: int = 0):
+                 mask_runs: int = 16384, track_max_gap: int = 0, boundary: Optional[str] = None, boundary_bins: int = 32,
+                 boundary_skip: Optional[Sequence[int]] = None):
         if out not in ("logits", "labels", "overlay"):
             raise StswinHipError(f"out must be 'logits', 'labels' or 'overlay', got {out!r}")
         if pixel_format not in PIXEL_FORMATS:
@@ -397,6 +413,30 @@ class VideoSegmenter:
         self.tracks, self.track_iou, self.track_same_class = tracks, track_iou, track_same_class
         self.track_max_gap = track_max_gap
         self.masks, self.mask_runs = masks, mask_runs
+        if boundary not in (None, "deferred"):
+            raise StswinHipError(f"boundary must be None or 'deferred', got {boundary!r}")
+        if boundary is None and (boundary_bins != 32 or boundary_skip is not None):
+            raise StswinHipError("boundary_bins and boundary_skip belong to boundary='deferred'")
+        if boundary is not None and out == "logits":
+            raise StswinHipError("boundary='deferred' measures the label map: out must be 'labels' or 'overlay'")
+        if isinstance(boundary_bins, bool) or not isinstance(boundary_bins, int) or not 2 <= boundary_bins <= 256:
+            raise StswinHipError(f"boundary_bins must be an int 2 .. 256, got {boundary_bins!r}")
+        if boundary is not None and not 1 <= classes <= 64:
+            raise StswinHipError(f"boundary: the model has {classes} classes, hip.boundary_counts takes 1 .. 64")
+        if boundary is not None:
+            if boundary_skip is None:         # the background, or the remapped ignore label: what `transparent` defaults to
+                boundary_skip = (classes - 1,) if self.cadis else (0,)
+            try:
+                boundary_skip = tuple(boundary_skip)
+            except TypeError:
+                boundary_skip = (boundary_skip,)
+            if any(isinstance(c, bool) or not isinstance(c, int) or not 0 <= c <= 63 for c in boundary_skip):
+                raise StswinHipError(f"boundary_skip holds classes 0 .. 63, got {boundary_skip!r}")
+        self.boundary, self.boundary_bins, self.boundary_skip = boundary, boundary_bins, boundary_skip
+        self._classes = classes
+        # boundary="deferred": a row per frame pushed with gt, beside _score_log; the call's output row and workspace are the segmenter's
+        self._boundary_log = DeviceLog(self.device, {"counts": ((classes, 2, 2 + boundary_bins), torch.int32)})
+        self._boundary_out = self._boundary_ws = None
         self._gt_table = None
         self._unmatched = None
         if gt_table is not None:
@@ -452,14 +492,16 @@ class VideoSegmenter:
         self._gt = {}
         self._score_log.end_sequence()    # scores="deferred": the sequence that ends here uses up its ordinal if it has rows in the log
         self.chain.reset()                # report="deferred": likewise, with its own ordinal; tracks: ids restart at 0
+        self._boundary_log.end_sequence()  # boundary="deferred": likewise
 
     def reset_metrics(self) -> None:
         """Clear what an evaluation pools and reset() keeps: the confusion matrix (protocol="cadis"), the score log and its sequence
         ordinal (scores="deferred"), the instrument log and its ordinal (report="deferred"), the count of unmatched ground-truth
-        pixels (gt_table); masks="deferred" logs into the instrument log."""
+        pixels (gt_table); masks="deferred" logs into the instrument log; the boundary log and its ordinal (boundary="deferred")."""
         if self._cm is not None:
             self._cm.zero_()
         self._score_log.clear()
+        self._boundary_log.clear()
         self.chain.log.clear()
         if self._unmatched is not None:
             self._unmatched.zero_()
@@ -482,6 +524,29 @@ class VideoSegmenter:
         res = EndoScores.from_counts(cols["counts"], sequences)
         res.frames = frames
         return res
+
+    def boundary_scores(self, names: Optional[Sequence[str]] = None):
+        """boundary="deferred": one download of the boundary log -> utils.boundary.BoundaryScores over every frame pushed with gt since
+        reset_metrics() - nsd(tau), hausdorff(), hausdorff_percentile(q), their aggregates - rows ordered by sequence and frame
+        (.sequences[r], .frames[r]) as endo_scores() orders them.  names: the caller's class names, the default of as_rows()."""
+        if self.boundary != "deferred":
+            raise StswinHipError("boundary_scores() belongs to boundary='deferred'")
+        from .utils.boundary import BoundaryScores
+        cols, sequences, frames = self._boundary_log.download()
+        res = BoundaryScores.from_counts(cols["counts"], sequences, frames)
+        res.names = list(names) if names is not None else None
+        return res
+
+    def _boundary(self, frame: int, gt: torch.Tensor, lab: torch.Tensor) -> None:
+        """boundary="deferred": the five launches of hip.boundary_counts on a scored frame's gt and labels [1][*out_size], behind the
+        launch that made the labels, and the row's copy into the log: no download, no synchronisation."""
+        need = hip.boundary_scratch(1, *lab.shape[1:], self._classes)
+        if self._boundary_ws is None or self._boundary_ws.numel() < need:         # once per frame size
+            self._boundary_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            self._boundary_out = torch.empty(1, self._classes, 2, 2 + self.boundary_bins, dtype=torch.int32, device=self.device)
+        hip.boundary_counts(gt.contiguous(), lab, self._classes, self.boundary_bins, self.boundary_skip, out=self._boundary_out,
+                            workspace=self._boundary_ws)
+        self._boundary_log.append(frame, counts=self._boundary_out)
 
     def instrument_report(self, names: Optional[Sequence[str]] = None):
         """report="deferred": one download of the instrument log -> utils.instruments.InstrumentReport (min_area as given to the
@@ -835,6 +900,8 @@ class VideoSegmenter:
                     from .utils.EndoMetric import predict_and_score
                     lab, dices, ious = predict_and_score(logits[b:b + 1], self.out_size, gt)
                     scored = (dices[0], ious[0])
+                if gt is not None and self.boundary is not None:
+                    self._boundary(g, gt, lab)
                 r, y = logits[b], None
                 if self.out != "logits":
                     out, ys = self._finish_labels(lab, frames and frames[b:b + 1], [g])
