@@ -744,6 +744,35 @@ int stswin_boundary_counts(const long long* gt /*[n][H][W]*/, const unsigned cha
  * column pass (64); anything else: -1.  The query pass
  * gathers in LDS while nc (2 + bins) <= 8192 words and adds to out directly above that. */
 int stswin_boundary_geometry(int which);
+/* ---- confidence of the labels (stswincl_amd/utils/confidence.py, VideoSegmenter(confidence=...)): the softmax probability that
+ * seg18/test.py:153-158 computes between its resize and its argmax, for the label each pixel got.  logits NCHW [F][nc][h][w] (dtype 0
+ * bf16, 1 fp32), labels uint8 [F][H][W] (of stswin_upsample_argmax / stswin_upsample_argmax_cm, or any other), conf uint8 [F][H][W].
+ * v_c is the bilinear value of class c at the output pixel, by the fp32 coordinate and value expressions of those two label launches
+ * (align_corners = 1: src = dst (in - 1) / (out - 1); 0: src = max((in / out) (dst + 0.5) - 0.5, 0)), so for a label they made
+ * v_label is the maximum to the bit.  With m = max_c v_c and l the pixel's label
+ *     p = exp(v_l - m) / sum_c exp(v_c - m)          conf = min(255, floor(255 p + 0.5)),   conf = 0 for l >= nc
+ * in fp32 with expf, the maximum and the sum taken online in one pass over the classes.  One launch, no scratch buffer, no atomics, no
+ * synchronisation (graph-capturable); the result depends on nothing but the inputs.  A thread takes four pixels of one row (they share
+ * the row's weights): labels and conf 4-byte aligned with W % 4 == 0 takes the body with one 4-byte load and store, anything else
+ * the byte body.  1 <= nc <= 64, h w < 2^31.  conf must not overlap labels or logits (the host wrapper checks).
+ * Errors, before anything is launched: -1880 frames, h, w, H or W <= 0, h w >= 2^31 (or more workgroups than a grid holds); -1881 nc
+ * outside 1 .. 64; -1882 logits, labels or conf NULL; -1883 dtype not 0 or 1. */
+int stswin_upsample_confidence(int dtype, const void* logits, const unsigned char* labels, unsigned char* conf, int align_corners,
+                               int frames, int nc, int h, int w, int H, int W, void* stream);
+/* sums of a confidence map over a label map or a component map: map [n][H][W] uint8 (map_bytes 1) or int32 (map_bytes 4: the components
+ * of stswin_label_components, -1 = none), conf uint8 [n][H][W] -> out int64 [n][K][3].  Row out[f][i], over the pixels of frame f whose
+ * map value is i, 0 <= i < K:    0: their number     1: the sum of conf     2: the number of them with conf < low
+ * Other map values are counted nowhere.  out is written in full by the call (cleared by a fill kernel on the stream, no memset node):
+ * a second call into the same out overwrites.  Two launches, no scratch buffer, no synchronisation, no allocation (graph-capturable).
+ * Integer atomics only (exact, independent of the order: bit-reproducible).  A thread takes 16 consecutive pixels of a frame and adds a
+ * run of equal values to its workgroup's LDS bins at once; non-zero bins go out with one 64-bit atomic each.  Any W: map and conf 16-byte
+ * aligned with H W % 16 == 0 takes the body with 16-byte loads, anything else the element body.  1 <= H, W <= 16384, 1 <= K <= 1024,
+ * 0 <= low <= 256.  The buffers must not overlap (the host wrapper checks).
+ * Errors, before anything is launched: -1884 n, H or W <= 0, or H or W > 16384 (or more workgroups than a grid holds); -1885 map, conf
+ * or out NULL; -1886 map_bytes not 1 or 4; -1887 K outside 1 .. 1024; -1888 low outside 0 .. 256; -1889 map not aligned to map_bytes or
+ * out not 8-byte aligned. */
+int stswin_confidence_sums(const void* map /*[n][H][W]*/, int map_bytes /*1: uint8, 4: int32*/, const unsigned char* conf /*[n][H][W]*/,
+                           long long* out /*[n][K][3]*/, int K, int low, int n, int H, int W, void* stream);
 /* ---- frames as a video source delivers them (stswincl_amd/utils/yuv.py, VideoSegmenter(pixel_format=..., out_format="nv12")):
  * stswin_yuv_to_rgb makes the HWC RGB frame uint8 [n][Hs][Ws][3] that stswin_frame_ingest and stswin_labels_overlay read,
  * stswin_rgb_to_nv12 turns such a frame into NV12.  Hs (NV12) and Ws are even.

@@ -1632,6 +1632,228 @@ extern "C" int stswin_label_moments(const unsigned char* labels, long long* out,
   return 0;
 }
 
+// Confidence of the labels (stswincl_amd/utils/confidence.py states the result; VideoSegmenter(confidence=...)): the softmax
+// probability seg18/test.py:153-158 has between its resize and its argmax, for the label a pixel got, as a byte.  The label launches
+// above skip the softmax, so this launch reads the small logits once more: a thread takes CF_PPT = 4 pixels of one output row, which
+// share y0, y1 and wy, with the coordinate and value expressions of upsample_argmax_kernel / upsample_argmax_cm_kernel copied to the
+// letter (this file is built with -ffp-contract=off), so the value at a label those kernels made is the running maximum to the bit.
+// The softmax is online - per class one expf of -|v - m| rescales the sum or joins it - so nothing is indexed by the class: no scratch.
+// WIDE: labels and conf 4-byte aligned and W % 4 == 0, one dword in and out; else the bytes that exist, one by one.
+#define CF_PPT 4
+
+template <typename TL, bool WIDE>
+__global__ __launch_bounds__(256) void upsample_confidence_kernel(const TL* __restrict__ logits, const unsigned char* __restrict__ labels,
+                                                                  unsigned char* __restrict__ conf, int align, int nc, int h, int w, int H,
+                                                                  int W, int cpr, int blocks_per_frame) {
+  const int f = (int)(blockIdx.x / (unsigned)blocks_per_frame);
+  const long q = (long)(blockIdx.x % (unsigned)blocks_per_frame) * 256 + threadIdx.x;
+  const int y = (int)(q / cpr), col = (int)(q - (long)y * cpr);
+  if (y >= H) return;
+  const int xb = CF_PPT * col, len = min(CF_PPT, W - xb);
+  const long at = ((long)f * H + y) * W + xb;
+  unsigned lw = 0u;
+  if (WIDE) {
+    lw = *reinterpret_cast<const unsigned*>(labels + at);
+  } else {
+#pragma unroll
+    for (int i = 0; i < CF_PPT; ++i)
+      if (i < len) lw |= (unsigned)labels[at + i] << (8 * i);
+  }
+  const float sy = align ? (H > 1 ? (float)(h - 1) / (float)(H - 1) : 0.f) : (float)h / (float)H;
+  const float sx = align ? (W > 1 ? (float)(w - 1) / (float)(W - 1) : 0.f) : (float)w / (float)W;
+  float fy;
+  if (align) fy = y * sy;
+  else fy = fmaxf(sy * ((float)y + 0.5f) - 0.5f, 0.f);
+  const int y0 = min((int)fy, h - 1);
+  const int y1 = min(y0 + 1, h - 1);
+  const float wy = fy - y0;
+  int x0[CF_PPT], x1[CF_PPT];
+  float wx[CF_PPT], m[CF_PPT], s[CF_PPT], vl[CF_PPT];
+#pragma unroll
+  for (int i = 0; i < CF_PPT; ++i) {
+    const int x = min(xb + i, W - 1);                          // (a pixel past the row's end repeats the last one and is not stored)
+    float fx;
+    if (align) fx = x * sx;
+    else fx = fmaxf(sx * ((float)x + 0.5f) - 0.5f, 0.f);
+    x0[i] = min((int)fx, w - 1);
+    x1[i] = min(x0[i] + 1, w - 1);
+    wx[i] = fx - x0[i];
+    m[i] = -3.0e38f;
+    s[i] = 0.f;
+    vl[i] = 0.f;
+  }
+  const TL* b = logits + (long)f * nc * h * w;
+  for (int c = 0; c < nc; ++c) {
+    const TL* pl = b + (long)c * h * w;
+    const TL* r0 = pl + y0 * w;
+    const TL* r1 = pl + y1 * w;
+#pragma unroll
+    for (int i = 0; i < CF_PPT; ++i) {
+      const float v = (1.f - wy) * ((1.f - wx[i]) * to_f32<TL>(r0[x0[i]]) + wx[i] * to_f32<TL>(r0[x1[i]])) +
+                      wy * ((1.f - wx[i]) * to_f32<TL>(r1[x0[i]]) + wx[i] * to_f32<TL>(r1[x1[i]]));
+      const float e = expf(-fabsf(v - m[i]));                  // v > m: the old sum's scale; else this class's term
+      if (v > m[i]) {
+        s[i] = s[i] * e + 1.f;
+        m[i] = v;
+      } else {
+        s[i] += e;
+      }
+      if ((unsigned)c == ((lw >> (8 * i)) & 255u)) vl[i] = v;
+    }
+  }
+  unsigned out = 0u;
+#pragma unroll
+  for (int i = 0; i < CF_PPT; ++i) {
+    const unsigned l = (lw >> (8 * i)) & 255u;
+    const float p = expf(vl[i] - m[i]) / s[i];
+    const unsigned qv = l < (unsigned)nc ? (unsigned)fminf(255.f * p + 0.5f, 255.f) : 0u;
+    out |= qv << (8 * i);
+  }
+  if (WIDE) {
+    *reinterpret_cast<unsigned*>(conf + at) = out;
+  } else {
+#pragma unroll
+    for (int i = 0; i < CF_PPT; ++i)
+      if (i < len) conf[at + i] = (unsigned char)(out >> (8 * i));
+  }
+}
+
+extern "C" int stswin_upsample_confidence(int dtype, const void* logits, const unsigned char* labels, unsigned char* conf,
+                                          int align_corners, int frames, int nc, int h, int w, int H, int W, void* stream) {
+  if (frames <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0 || (long)h * w > 0x7fffffffL) return -1880;
+  if (nc < 1 || nc > 64) return -1881;
+  if (logits == nullptr || labels == nullptr || conf == nullptr) return -1882;
+  if (dtype != 0 && dtype != 1) return -1883;
+  const bool wide = (((uintptr_t)labels | (uintptr_t)conf) & 3) == 0 && W % CF_PPT == 0;
+  const int cpr = (W + CF_PPT - 1) / CF_PPT;
+  const long bpf = ((long)H * cpr + 255) / 256;
+  if (bpf * frames > 0x7fffffffL) return -1880;
+  dim3 grid((unsigned)(bpf * frames));
+  hipStream_t st = (hipStream_t)stream;
+  const int al = align_corners ? 1 : 0;
+#define CF_LAUNCH(TL, WIDE_)                                                                                                       \
+  hipLaunchKernelGGL((upsample_confidence_kernel<TL, WIDE_>), grid, dim3(256), 0, st, (const TL*)logits, labels, conf, al, nc, h, w, \
+                     H, W, cpr, (int)bpf)
+  if (dtype == 0) {
+    if (wide) CF_LAUNCH(bf16, true);
+    else CF_LAUNCH(bf16, false);
+  } else {
+    if (wide) CF_LAUNCH(float, true);
+    else CF_LAUNCH(float, false);
+  }
+#undef CF_LAUNCH
+  STSWIN_CHECK_LAUNCH();
+  return 0;
+}
+
+// Sums of the confidence map over a label map or a component map (utils/confidence.py, confidence_sums, states the result): per frame
+// and map value i < K the number of pixels, the sum of their conf and the number with conf < low.  A workgroup takes CS_THREADS * 16
+// consecutive pixels of one frame, a thread 16 of them; a thread adds a run of equal values to the workgroup's LDS bins at once (an
+// instrument is spatially coherent: most threads flush once), and the non-zero bins go out with one 64-bit atomic each.  4096 pixels of
+// conf <= 255 keep every bin below 2^21.  WIDE: 16-byte loads (the frame's pixels start 16-byte aligned); else element by element.
+#define CS_THREADS 256
+#define CS_PPT 16
+
+__device__ __forceinline__ void cs_flush(unsigned* bins, int id, unsigned c, unsigned s, unsigned lo) {
+  atomicAdd(bins + 3 * id, c);
+  atomicAdd(bins + 3 * id + 1, s);
+  if (lo) atomicAdd(bins + 3 * id + 2, lo);
+}
+
+template <int MB, bool WIDE>
+__global__ __launch_bounds__(CS_THREADS) void confidence_sums_kernel(const void* __restrict__ map, const unsigned char* __restrict__ conf,
+                                                                     unsigned long long* out, int K, unsigned low, long HW,
+                                                                     int blocks_per_frame) {
+  __shared__ unsigned bins[3 * 1024];
+  for (int i = threadIdx.x; i < 3 * K; i += CS_THREADS) bins[i] = 0u;
+  __syncthreads();
+  const int f = (int)(blockIdx.x / (unsigned)blocks_per_frame);
+  const long p0 = ((long)(blockIdx.x % (unsigned)blocks_per_frame) * CS_THREADS + threadIdx.x) * CS_PPT;
+  const int len = (int)max(0L, min((long)CS_PPT, HW - p0));
+  if (len > 0) {
+    const long at = (long)f * HW + p0;
+    int id[CS_PPT];
+    unsigned qv[CS_PPT];
+    if (WIDE) {                                                // (len == 16: H W % 16 == 0)
+      const uint4 cw = *reinterpret_cast<const uint4*>(conf + at);
+#pragma unroll
+      for (int i = 0; i < CS_PPT; ++i) qv[i] = lm_byte(cw, i);
+      if (MB == 1) {
+        const uint4 mw = *reinterpret_cast<const uint4*>((const unsigned char*)map + at);
+#pragma unroll
+        for (int i = 0; i < CS_PPT; ++i) id[i] = (int)lm_byte(mw, i);
+      } else {
+        const int4* mp = reinterpret_cast<const int4*>((const int*)map + at);
+#pragma unroll
+        for (int k = 0; k < CS_PPT / 4; ++k) {
+          const int4 mw = mp[k];
+          id[4 * k] = mw.x;
+          id[4 * k + 1] = mw.y;
+          id[4 * k + 2] = mw.z;
+          id[4 * k + 3] = mw.w;
+        }
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < CS_PPT; ++i) {
+        const bool in = i < len;
+        qv[i] = in ? (unsigned)conf[at + i] : 0u;
+        id[i] = !in ? -1 : MB == 1 ? (int)((const unsigned char*)map)[at + i] : ((const int*)map)[at + i];
+      }
+    }
+    int cur = -1;
+    unsigned c = 0u, s = 0u, lo = 0u;
+#pragma unroll
+    for (int i = 0; i < CS_PPT; ++i) {
+      const int v = (unsigned)id[i] < (unsigned)K ? id[i] : -1;        // (-1, a value >= K and a pixel past the end: counted nowhere)
+      if (v != cur) {
+        if (cur >= 0) cs_flush(bins, cur, c, s, lo);
+        cur = v;
+        c = s = lo = 0u;
+      }
+      c += 1u;
+      s += qv[i];
+      lo += qv[i] < low ? 1u : 0u;
+    }
+    if (cur >= 0) cs_flush(bins, cur, c, s, lo);
+  }
+  __syncthreads();
+  unsigned long long* o = out + (long)f * 3 * K;
+  for (int i = threadIdx.x; i < 3 * K; i += CS_THREADS)
+    if (bins[i]) atomicAdd(o + i, (unsigned long long)bins[i]);
+}
+
+extern "C" int stswin_confidence_sums(const void* map, int map_bytes, const unsigned char* conf, long long* out, int K, int low, int n,
+                                      int H, int W, void* stream) {
+  if (n <= 0 || H <= 0 || W <= 0 || H > 16384 || W > 16384) return -1884;
+  if (map == nullptr || conf == nullptr || out == nullptr) return -1885;
+  if (map_bytes != 1 && map_bytes != 4) return -1886;
+  if (K < 1 || K > 1024) return -1887;
+  if (low < 0 || low > 256) return -1888;
+  if (((uintptr_t)map & (uintptr_t)(map_bytes - 1)) || ((uintptr_t)out & 7)) return -1889;
+  const long HW = (long)H * W;
+  const long bpf = (HW + CS_THREADS * CS_PPT - 1) / (CS_THREADS * CS_PPT);
+  if (bpf * n > 0x7fffffffL) return -1884;
+  const bool wide = (((uintptr_t)map | (uintptr_t)conf) & 15) == 0 && HW % CS_PPT == 0;
+  dim3 grid((unsigned)(bpf * n));
+  hipStream_t st = (hipStream_t)stream;
+  unsigned long long* o = reinterpret_cast<unsigned long long*>(out);
+  stswin_zero_bytes(out, (size_t)n * K * 3 * sizeof(long long), st);        // (a kernel, not hipMemsetAsync: see common.h)
+#define CS_LAUNCH(MB_, WIDE_)                                                                                                  \
+  hipLaunchKernelGGL((confidence_sums_kernel<MB_, WIDE_>), grid, dim3(CS_THREADS), 0, st, map, conf, o, K, (unsigned)low, HW, \
+                     (int)bpf)
+  if (map_bytes == 1) {
+    if (wide) CS_LAUNCH(1, true);
+    else CS_LAUNCH(1, false);
+  } else {
+    if (wide) CS_LAUNCH(4, true);
+    else CS_LAUNCH(4, false);
+  }
+#undef CS_LAUNCH
+  STSWIN_CHECK_LAUNCH();
+  return 0;
+}
+
 // Connected components of a label map and their moments rows (stswincl_amd/utils/instruments.py, label_components, states the
 // result; VideoSegmenter(instances=K)): block-based union-find on an int32 parent map of frame-local pixel indices y W + x.  A link
 // only ever points to a smaller index of the same component (LDS or global atomicMin), so a component's root is its first pixel in

@@ -1842,6 +1842,82 @@ def boundary_counts(gt: torch.Tensor, pred: torch.Tensor, nc: int, bins: int = 3
     return out
 
 
+def _got(t) -> str:
+    return f"{t.dtype} {tuple(t.shape)} on {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__
+
+
+def upsample_confidence(logits: torch.Tensor, labels: torch.Tensor, align_corners: bool = True,
+                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """NCHW logits [F][nc][h][w] (bf16 / fp32, nc <= 64) and uint8 labels [F][H][W] -> uint8 [F][H][W]: the softmax probability, over
+    the classes of the bilinear resize of the logits to (H, W) (align_corners as F.interpolate), of each pixel's label, as min(255,
+    floor(255 p + 0.5)); 0 where the label is >= nc.  The resize is the one of upsample_argmax (align_corners=True) and
+    upsample_argmax_cm, so for their labels it is the largest probability (utils.confidence.upsample_confidence is the numpy
+    definition).  out: written in full; with it the call allocates nothing, and it never synchronises (graph-capturable).  One launch.
+    Returns out (include/stswin_hip.h, stswin_upsample_confidence)."""
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 4 or logits.dtype not in (torch.bfloat16, torch.float32) or not logits.is_contiguous():
+        raise StswinHipError(f"upsample_confidence: logits must be contiguous bf16 or fp32 [F][nc][h][w], got {_got(logits)}")
+    if not isinstance(labels, torch.Tensor) or labels.dim() != 3 or labels.dtype != torch.uint8 or not labels.is_contiguous():
+        raise StswinHipError(f"upsample_confidence: labels must be contiguous uint8 [F][H][W], got {_got(labels)}")
+    if not logits.is_cuda or not labels.is_cuda:
+        raise StswinHipError("upsample_confidence: logits and labels must be on the GPU (no CPU path exists; "
+                             "utils.confidence.upsample_confidence is the numpy definition)")
+    F_, nc, h, w = logits.shape
+    if labels.shape[0] != F_ or labels.device != logits.device:
+        raise StswinHipError(f"upsample_confidence: labels must be [{F_}][H][W] on {logits.device} as the logits are, got {_got(labels)}")
+    if logits.numel() == 0 or labels.numel() == 0:
+        raise StswinHipError(f"upsample_confidence: empty logits {tuple(logits.shape)} or labels {tuple(labels.shape)}")
+    if not 1 <= nc <= 64:
+        raise StswinHipError(f"upsample_confidence: {nc} classes, the kernel takes 1 .. 64")
+    if h * w >= 1 << 31:
+        raise StswinHipError(f"upsample_confidence: logits of {h} x {w}, the kernel takes h w < 2^31")
+    H, W = labels.shape[1:]
+    if out is None:
+        out = torch.empty(F_, H, W, dtype=torch.uint8, device=labels.device)
+    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != (F_, H, W) or not out.is_contiguous()
+          or out.device != labels.device):
+        raise StswinHipError(f"upsample_confidence: out must be contiguous uint8 [{F_}][{H}][{W}] on {labels.device}, got {_got(out)}")
+    elif _same_memory(out, labels) or _same_memory(out, logits):
+        raise StswinHipError("upsample_confidence: out shares memory with labels or logits")
+    _check(load().stswin_upsample_confidence(_dt(logits), _p(logits), _p(labels), _p(out), 1 if align_corners else 0, F_, nc, h, w, H, W,
+                                             _stream()), "upsample_confidence")
+    return out
+
+
+def confidence_sums(maps: torch.Tensor, conf: torch.Tensor, K: int, low: int = 128, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint8 (a label map) or int32 (hip.label_components' map, -1 = none) maps [n][H][W] and uint8 conf [n][H][W] -> int64 [n][K][3]:
+    per frame and map value i in [0, K) the number of its pixels, the sum of their conf and the number of them with conf < low (0 ..
+    256); other values are counted nowhere (utils.confidence.confidence_sums is the numpy definition, matched bit for bit).  out:
+    written in full - cleared by a fill kernel, so a second call overwrites; with it the call allocates nothing, and it never
+    synchronises (graph-capturable).  Two launches.  Returns out (include/stswin_hip.h, stswin_confidence_sums)."""
+    if not isinstance(maps, torch.Tensor) or maps.dtype not in (torch.uint8, torch.int32) or maps.dim() != 3 or not maps.is_contiguous():
+        raise StswinHipError(f"confidence_sums: maps must be contiguous uint8 or int32 [n][H][W], got {_got(maps)}")
+    if not isinstance(conf, torch.Tensor) or conf.dtype != torch.uint8 or conf.shape != maps.shape or not conf.is_contiguous():
+        raise StswinHipError(f"confidence_sums: conf must be contiguous uint8 {tuple(maps.shape)} as the maps are, got {_got(conf)}")
+    if not maps.is_cuda or not conf.is_cuda:
+        raise StswinHipError("confidence_sums: maps and conf must be on the GPU (no CPU path exists; utils.confidence.confidence_sums "
+                             "is the numpy definition)")
+    if conf.device != maps.device:
+        raise StswinHipError(f"confidence_sums: conf must be on {maps.device} as the maps are, got {conf.device}")
+    n, H, W = maps.shape
+    if n <= 0 or H <= 0 or W <= 0:
+        raise StswinHipError(f"confidence_sums: empty maps {tuple(maps.shape)}")
+    if H > 16384 or W > 16384:
+        raise StswinHipError(f"confidence_sums: a {H} x {W} map, the kernel takes up to 16384 x 16384")
+    if isinstance(K, bool) or not isinstance(K, int) or not 1 <= K <= 1024:
+        raise StswinHipError(f"confidence_sums: K must be an int 1 .. 1024, got {K!r}")
+    if isinstance(low, bool) or not isinstance(low, int) or not 0 <= low <= 256:
+        raise StswinHipError(f"confidence_sums: low must be an int 0 .. 256, got {low!r}")
+    if out is None:
+        out = torch.empty(n, K, 3, dtype=torch.int64, device=maps.device)
+    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.int64 or tuple(out.shape) != (n, K, 3) or not out.is_contiguous()
+          or out.device != maps.device):
+        raise StswinHipError(f"confidence_sums: out must be contiguous int64 [{n}][{K}][3] on {maps.device}, got {_got(out)}")
+    elif _same_memory(out, maps) or _same_memory(out, conf):
+        raise StswinHipError("confidence_sums: out shares memory with maps or conf")
+    _check(load().stswin_confidence_sums(_p(maps), maps.element_size(), _p(conf), _p(out), K, low, n, H, W, _stream()), "confidence_sums")
+    return out
+
+
 YUV_NV12, YUV_UYVY = 0, 1                    # stswin_yuv_to_rgb's `format` (plain integers in the header's comment, not #defines)
 YUV_REPLICATE, YUV_LINEAR = 0, 1               # ... and its `chroma`
 _YUV_FORMATS = {"nv12": YUV_NV12, "uyvy": YUV_UYVY}

@@ -131,11 +131,13 @@ class MaskReport:
       truncated  bool  [rows]           count > cap: the row's map cannot be rebuilt (dense, objects and mots_lines raise ValueError)
 
     instances / tracks: the utils.instruments.InstanceReport (source "instances": classes, areas, which instances are present) and
-    TrackReport of the same rows; min_area, skip (source "labels": classes left out) and names (per class) shape objects()."""
+    TrackReport of the same rows; min_area, skip (source "labels": classes left out) and names (per class) shape objects().
+    confidence: the utils.confidence.ConfidenceReport of the same rows (None: none); objects() then adds "score", the mean probability
+    of the instance's pixels, or of the class's for source "labels" - what COCO-style result files ask for per object."""
 
     def __init__(self, runs, count, size: Sequence[int], source: str = "labels", frames: Optional[Sequence[int]] = None,
                  sequences: Optional[Sequence[int]] = None, instances=None, tracks=None, min_area: int = 1, skip: Sequence[int] = (),
-                 names: Optional[Sequence[str]] = None):
+                 names: Optional[Sequence[str]] = None, confidence=None):
         rn = np.asarray(runs)
         c = np.asarray(count).reshape(-1)
         if rn.ndim == 2:
@@ -163,9 +165,22 @@ class MaskReport:
         self.instances, self.tracks = instances, tracks
         self.min_area, self.skip = int(min_area), tuple(int(s) for s in skip)
         self.names = list(names) if names is not None else None
+        if confidence is not None:
+            if len(confidence) != n:
+                raise ValueError(f"MaskReport: a confidence report of {len(confidence)} rows for {n} rows")
+            if source == "instances" and confidence.instance_mean is None:
+                raise ValueError("MaskReport: source 'instances' needs a confidence report with instance sums")
+        self.confidence = confidence
 
     def __len__(self) -> int:
         return len(self.frames)
+
+    def _score(self, r: int, d: dict):
+        """The mean probability of the object's pixels: the instance's, or the class's for source "labels" (None: it has no pixels, or
+        its ordinal lies beyond the K of the sums)."""
+        mean = self.confidence.instance_mean if self.source == "instances" else self.confidence.mean
+        i = d["instance"] if self.source == "instances" else d["cls"]
+        return float(mean[r, i]) if i < mean.shape[1] and not np.isnan(mean[r, i]) else None
 
     def dense(self, r: int) -> np.ndarray:
         """Row r's map int32 [H][W]."""
@@ -201,6 +216,8 @@ class MaskReport:
         for d in out:
             d["size"] = [H, W]
             d["counts"] = counts_to_string(mask_counts(self.runs[r], self.count[r], self.size, (d.get("instance", d["cls"]),)))
+            if self.confidence is not None:
+                d["score"] = self._score(r, d)
         return out
 
     def mots_lines(self, sequence: int = 0) -> List[str]:

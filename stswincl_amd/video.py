@@ -195,7 +195,7 @@ class VideoSegmenter:
     """Segment video sequences with an eval-mode TswinPlus, one result per frame, each frame's ResNet features computed once.
 
     seg = VideoSegmenter(model, batch=1, out="logits" | "labels" | "overlay", out_size=None, graph=False, report=None, instances=None,
-                         tracks=False, masks=None, boundary=None)
+                         tracks=False, masks=None, boundary=None, confidence=None)
 
     push(frames, gt=None) takes uint8 RGB frames [n][Hs][Ws][3] (or one [Hs][Ws][3]; torch tensor on the model's GPU or the CPU, or
     a numpy array; NV12 or UYVY frames with pixel_format, below) and returns [(frame_index, result), ...] for the frames whose clip is now complete.  finish() runs what is
@@ -347,6 +347,25 @@ class VideoSegmenter:
     contour but still bounds its neighbours' contours).  reset() keeps the log, reset_metrics() clears it.  boundary=None: every
     result, launch and captured graph is what it is without the keyword.
 
+    confidence="frame" | "deferred" (out="labels" | "overlay", both protocols, every scores mode, batch > 1 and graph=True; needs neither
+    report nor masks; confidence_low=128): how sure the model was of the labels it gave - the softmax probability the reference has
+    between its resize and its argmax and throws away (seg18/test.py:153-158), which the label launches skip.  Wherever a step's label
+    map is made, the scoring paths with ground truth included, one launch (hip.upsample_confidence; utils.confidence states the
+    result) reads the logits the labels came from once more and writes conf uint8 [*out_size] = min(255, floor(255 p + 0.5)), p the
+    probability of the pixel's label; then hip.confidence_sums takes per class the number of pixels, the sum of conf and the number
+    of pixels with conf < confidence_low (0 .. 256), int64 [nc][3], and with instances=K the same per instance ordinal over the chain's
+    component map, int64 [K][3], behind the component launches and before the next clip's components overwrite the map (where the
+    masks are encoded: nothing depends on the tracker, a parked frame is summed when its labels exist, and ordinals join with track ids
+    by row on the host).  confidence="frame": a result r becomes r + (conf, class_sums[, instance_sums]) behind whatever report and
+    masks append, all on the device - no download and no synchronisation.  Under graph=True the launches are part of the captured
+    steady step and the three tensors of the last replayed step of a push are views of the graph's buffers, as the labels are; with
+    ground truth they are made after the replay.  confidence="deferred": results are unchanged and the sums, not the map, go into the
+    device log; confidence_report(names=None) downloads once and returns utils.confidence.ConfidenceReport - mean = sum / (255 count)
+    and low_fraction per class, and per instance, NaN where absent - over every frame released since reset_metrics(), in
+    instrument_report()'s order and with its sequence ordinals; mask_report() passes it to the MaskReport when masks is deferred too,
+    and objects(r) then carry "score", the mean probability of the instance (of the class without instances).  confidence=None: every
+    result, launch and captured graph is what it is without the keyword.
+
     Runs under torch.no_grad().  Refuses (StswinHipError): a model in train mode, a model or frames not on the GPU, a frame size
     that differs from the earlier frames'."""
 
@@ -358,7 +377,7 @@ class VideoSegmenter:
                  instances: Optional[int] = None, connectivity: int = 8, instance_skip: Optional[Sequence[int]] = None,
                  tracks: bool = False, track_iou: int = 100, track_same_class: bool = True, masks: Optional[str] = None,
                  mask_runs: int = 16384, track_max_gap: int = 0, boundary: Optional[str] = None, boundary_bins: int = 32,
-                 boundary_skip: Optional[Sequence[int]] = None):
+                 boundary_skip: Optional[Sequence[int]] = None, confidence: Optional[str] = None, confidence_low: int = 128):
         if out not in ("logits", "labels", "overlay"):
             raise StswinHipError(f"out must be 'logits', 'labels' or 'overlay', got {out!r}")
         if pixel_format not in PIXEL_FORMATS:
@@ -408,7 +427,9 @@ class VideoSegmenter:
         classes = model.classifier[-1].out_channels
         self._score_log = DeviceLog(self.device, {"counts": ((3, classes), torch.int32)})     # scores="deferred": a row per scored frame
         self.chain = ReportChain(self.device, classes, protocol, out, report, min_area, instances, connectivity, instance_skip, tracks,
-                                 track_iou, track_same_class, masks, mask_runs, track_max_gap)
+                                 track_iou, track_same_class, masks, mask_runs, track_max_gap, confidence, confidence_low,
+                                 self.align_corners)
+        self.confidence, self.confidence_low = confidence, confidence_low
         self.report, self.min_area, self.instances, self.connectivity, self.instance_skip = report, min_area, instances, connectivity, self.chain.instance_skip
         self.tracks, self.track_iou, self.track_same_class = tracks, track_iou, track_same_class
         self.track_max_gap = track_max_gap
@@ -587,20 +608,42 @@ class VideoSegmenter:
         from .utils.instruments import InstanceReport, TrackReport
         from .utils.rle import MaskReport
         joined = self.instances is not None and self.report == "deferred"
+        scored = self.confidence == "deferred"   # objects(r) then carry a score: the instance's (the class's) mean probability
         wanted = ("runs", "count") + (("rows", "total") if joined else ()) + (("ids", "started") if joined and self.tracks else ())
+        wanted += self._confidence_columns() if scored else ()
         cols, sequences, frames = self.chain.log.download(*wanted)          # the one download: every column the report is made of
         size = self.out_size or (0, 0)         # (out="overlay" before its first frame: no size yet, and no row that would need one)
         skip = self.instance_skip if self.instance_skip is not None else (self.chain.classes - 1,) if self.cadis else (0,)
-        inst = trk = None
+        inst = trk = conf = None
         try:
             if joined:
                 inst = InstanceReport.from_rows(cols["rows"], cols["total"], size, self.min_area, names, frames, sequences)
                 if self.tracks:
                     trk = TrackReport.from_ids(inst, cols["ids"], cols["started"])
+            if scored:
+                from .utils.confidence import ConfidenceReport
+                conf = ConfidenceReport.from_sums(cols["class_sums"], cols.get("instance_sums"), self.confidence_low, names, frames, sequences)
             return MaskReport(cols["runs"], cols["count"], size, "labels" if self.instances is None else "instances", frames, sequences,
-                              inst, trk, self.min_area, skip, names)
+                              inst, trk, self.min_area, skip, names, confidence=conf)
         except ValueError as e:
             raise StswinHipError(f"mask_report: {e}") from e
+
+    def _confidence_columns(self) -> Tuple[str, ...]:
+        return ("class_sums",) + (("instance_sums",) if self.instances is not None else ())
+
+    def confidence_report(self, names: Optional[Sequence[str]] = None):
+        """confidence="deferred": one download of the confidence log -> utils.confidence.ConfidenceReport over every frame released since
+        reset_metrics() - per class, and per instance with instances=K, the mean probability of its pixels and the share of them below
+        confidence_low - rows ordered by sequence and frame as instrument_report()'s, with its sequence ordinals.  names: the caller's
+        class names, for as_rows()."""
+        if self.confidence != "deferred":
+            raise StswinHipError("confidence_report() belongs to confidence='deferred'")
+        from .utils.confidence import ConfidenceReport
+        cols, sequences, frames = self.chain.log.download(*self._confidence_columns())
+        try:
+            return ConfidenceReport.from_sums(cols["class_sums"], cols.get("instance_sums"), self.confidence_low, names, frames, sequences)
+        except ValueError as e:
+            raise StswinHipError(f"confidence_report: {e}") from e
 
     def instance_report(self, names: Optional[Sequence[str]] = None):
         """report="deferred" with instances=K: one download of the instance log -> utils.instruments.InstanceReport (min_area as given
@@ -787,13 +830,15 @@ class VideoSegmenter:
         hip.clip_assemble(self._ring, tok, clips, table, B, n_new)
         logits = m.forward_frame_tokens(clips, h, w, self.size[0], self.size[1])
         if labels:
-            return (logits,) + self._finish_labels(self._labels(logits), frames, steady=tracked)
+            return (logits,) + self._finish_labels(self._labels(logits), frames, steady=tracked, logits=logits)
         return logits, None, None
 
-    def _finish_labels(self, lab: torch.Tensor, frames, clips: Optional[List[int]] = None, steady: bool = False):
+    def _finish_labels(self, lab: torch.Tensor, frames, clips: Optional[List[int]] = None, steady: bool = False,
+                       logits: Optional[torch.Tensor] = None):
         """Labels (B, *out_size) of a step, or of the one clip `clips` names (made by a scoring launch) -> (the result form of out="labels"
-        | "overlay", what the report chain makes of them per clip).  The one statement of the order: moments, components, (tracks), masks, overlay."""
-        ys = self.chain.labelled(lab, clips, steady)
+        | "overlay", what the report chain makes of them per clip).  The one statement of the order: moments, components, (tracks), masks,
+        confidence (on `logits`, the ones the labels were made from), overlay."""
+        ys = self.chain.labelled(lab, clips, steady, logits=logits)
         return lab if self._table is None else self._overlay(lab, frames), ys
 
     def _overlay(self, labels: torch.Tensor, frames) -> torch.Tensor:
@@ -904,7 +949,7 @@ class VideoSegmenter:
                     self._boundary(g, gt, lab)
                 r, y = logits[b], None
                 if self.out != "logits":
-                    out, ys = self._finish_labels(lab, frames and frames[b:b + 1], [g])
+                    out, ys = self._finish_labels(lab, frames and frames[b:b + 1], [g], logits=logits[b:b + 1])
                     r, y = out[0], ys and ys[0]
                 results.append((r,) + scored if scored else r)
                 extras.append(y)

@@ -67,31 +67,38 @@ class DeviceLog:
         return cols, [self.keys[r][0] for r in order], [self.keys[r][1] for r in order]
 
 
-class Yield(namedtuple("Yield", "moments rows total ids started runs count", defaults=(None,) * 7)):
+class Yield(namedtuple("Yield", "moments rows total ids started runs count conf class_sums instance_sums", defaults=(None,) * 10)):
     """What the labels [B][*out_size] of a step (or of one clip, B = 1) yield on the device: moments int64 [B][nc][10]; with instances
     rows int64 [B][K][12] and total int32 [B]; once tracked ids int32 [B][K] and started int32 [B][1]; with masks runs int32
-    [B][cap][2] and count int32 [B].  Absent fields are None."""
+    [B][cap][2] and count int32 [B]; with confidence conf uint8 [B][*out_size], class_sums int64 [B][nc][3] and, with instances,
+    instance_sums int64 [B][K][3].  Absent fields are None."""
     __slots__ = ()
 
     def clip(self, b: int) -> "Yield":
         """Clip b's part [1][...]."""
         return Yield(*(None if t is None else t[b:b + 1] for t in self))
 
-    def appended(self, result, report: bool = True, masks: bool = False):
+    def appended(self, result, report: bool = True, masks: bool = False, confidence: bool = False):
         """report="frame": a clip's result r -> r + (moments, rows, total, ids), what there is of them; masks="frame": then
-        + (runs, count); all on the device."""
+        + (runs, count); confidence="frame": then + (conf, class_sums[, instance_sums]); all on the device."""
         extra = tuple(t[0] for t in self[:4] if t is not None) if report else ()
         if masks:
             extra += (self.runs[0], self.count[0])
+        if confidence:
+            extra += tuple(t[0] for t in (self.conf, self.class_sums, self.instance_sums) if t is not None)
         return result + extra if isinstance(result, tuple) else (result,) + extra
 
-    def logged(self, log: DeviceLog, frame: int, tracked: bool = True, report: bool = True, masks: bool = False) -> int:
-        """report="deferred" and / or masks="deferred": a clip's row in the log -> its index (tracked = False: ids and started are
-        written when it is tracked); the columns of the one that is not deferred are left alone."""
+    def logged(self, log: DeviceLog, frame: int, tracked: bool = True, report: bool = True, masks: bool = False,
+               confidence: bool = False) -> int:
+        """report="deferred", masks="deferred" and / or confidence="deferred": a clip's row in the log -> its index (tracked = False:
+        ids and started are written when it is tracked); the columns of what is not deferred are left alone.  Of the confidence the
+        sums are logged, not the map."""
         values = dict(moments=self.moments, rows=self.rows, total=self.total, ids=self.ids if tracked else None,
                       started=self.started if tracked else None) if report else {}
         if masks:
             values.update(runs=self.runs, count=self.count)
+        if confidence:
+            values.update(class_sums=self.class_sums, instance_sums=self.instance_sums)
         return log.append(frame, **values)
 
 
@@ -123,15 +130,17 @@ class TrackSequencer:
 
 
 class ReportChain:
-    """report / instances / tracks / masks of a VideoSegmenter: hip.label_moments, then the launches of hip.label_components, then those
-    of hip.track_instances, then those of hip.rle_encode (on the component map with instances, else on the labels) on every label map
-    the segmenter makes.  The segmenter calls labelled() where a step's labels exist and
+    """report / instances / tracks / masks / confidence of a VideoSegmenter: hip.label_moments, then the launches of
+    hip.label_components, then those of hip.track_instances, then those of hip.rle_encode (on the component map with instances, else on
+    the labels), then hip.upsample_confidence on the logits the labels came from and hip.confidence_sums over the labels (and over
+    the component map with instances), on every label map the segmenter makes.  The segmenter calls labelled() where a step's labels exist and
     released() where its frames are handed out (step_is_steady() is the check in front of the graph's steady step, which tracks inside
     itself).  Owns what persists across steps: the component map and the workspaces (they only grow; the ones they replaced are kept, a
     captured step may still use them), the tracker's state, the parked frames, the pool of their map copies, and the deferred log."""
 
     def __init__(self, device, classes: int, protocol: str, out: str, report, min_area, instances, connectivity, instance_skip, tracks,
-                 track_iou, track_same_class, masks=None, mask_runs=16384, track_max_gap=0):
+                 track_iou, track_same_class, masks=None, mask_runs=16384, track_max_gap=0, confidence=None, confidence_low=128,
+                 align_corners=True):
         if report not in (None, "frame", "deferred"):
             raise StswinHipError(f"report must be None, 'frame' or 'deferred', got {report!r}")
         if report is not None and out == "logits":
@@ -178,7 +187,18 @@ class ReportChain:
             raise StswinHipError(f"mask_runs must be an int 1 .. {hip.RLE_MAX_RUNS}, got {mask_runs!r}")
         if masks is None and mask_runs != 16384:
             raise StswinHipError("mask_runs belongs to masks='frame' or 'deferred'")
+        if confidence not in (None, "frame", "deferred"):
+            raise StswinHipError(f"confidence must be None, 'frame' or 'deferred', got {confidence!r}")
+        if isinstance(confidence_low, bool) or not isinstance(confidence_low, int) or not 0 <= confidence_low <= 256:
+            raise StswinHipError(f"confidence_low must be an int 0 .. 256, got {confidence_low!r}")
+        if confidence is None and confidence_low != 128:
+            raise StswinHipError("confidence_low belongs to confidence='frame' or 'deferred'")
+        if confidence is not None and out == "logits":
+            raise StswinHipError("confidence belongs to out='labels' and out='overlay' (it is the probability of the label map's labels)")
+        if confidence is not None and not 1 <= classes <= 64:
+            raise StswinHipError(f"confidence: the model has {classes} classes, hip.upsample_confidence takes 1 .. 64")
         self.device, self.classes, self.report, self.min_area = device, classes, report, min_area
+        self.confidence, self.confidence_low, self.align_corners = confidence, confidence_low, bool(align_corners)
         self.masks, self.mask_runs = masks, mask_runs
         self.rle_ws = None                    # masks: the encoder's workspace (retired ones go where the component map's do)
         self.instances, self.connectivity, self.instance_skip = instances, connectivity, instance_skip
@@ -195,7 +215,9 @@ class ReportChain:
                              dict(rows=((instances, 12), torch.int64), total=((), torch.int32)) if logged and instances is not None else {},
                              dict(ids=((instances,), torch.int32), started=((), torch.int32)) if logged and tracks else {},
                              dict(moments=((classes, 10), torch.int64)) if logged else {},
-                             dict(runs=((mask_runs, 2), torch.int32), count=((), torch.int32)) if masks == "deferred" else {})
+                             dict(runs=((mask_runs, 2), torch.int32), count=((), torch.int32)) if masks == "deferred" else {},
+                             dict(class_sums=((classes, 3), torch.int64)) if confidence == "deferred" else {},
+                             dict(instance_sums=((instances, 3), torch.int64)) if confidence == "deferred" and instances is not None else {})
 
     def reset(self) -> None:
         """The sequence ends: its ordinal in the log, ids restart at 0 (a fill kernel on the stream), what is parked is dropped."""
@@ -206,14 +228,16 @@ class ReportChain:
         self.parked = {}
         self.order.reset()
 
-    def labelled(self, labels: torch.Tensor, frames: Optional[Sequence[int]] = None, steady: bool = False) -> Optional[List[Yield]]:
-        """A step's labels [B][*out_size] exist -> what they yield, per clip (None without report and masks): the moments, one launch behind the
-        clearing of their buffer (a fill kernel, also when captured: no memset node), the component launches behind it, and the
+    def labelled(self, labels: torch.Tensor, frames: Optional[Sequence[int]] = None, steady: bool = False,
+                 logits: Optional[torch.Tensor] = None) -> Optional[List[Yield]]:
+        """A step's labels [B][*out_size] exist -> what they yield, per clip (None without report, masks and confidence): the moments,
+        one launch behind the clearing of their buffer (a fill kernel, also when captured: no memset node), the component launches behind it, and the
         tracker's behind those for clips whose frame indices `frames` names (labels made per clip: the component map is that clip's
         until the next clip's labels) or in the graph's steady step (`steady`: one frame, in frame order); released() tracks the rest.
         The encoder's launches come last: they need nothing from the tracker, so a frame that is parked is encoded here, before the
-        next clip's components overwrite the map."""
-        if self.report is None and self.masks is None:
+        next clip's components overwrite the map.  So do the confidence launches, on the `logits` [B][nc][h][w] the labels were made
+        from: the map, its sums over the labels and, with instances, over the component map."""
+        if self.report is None and self.masks is None and self.confidence is None:
             return None
         moments = rows = total = ids = started = None
         if self.report is not None:
@@ -230,21 +254,33 @@ class ReportChain:
             B, H, W = labels.shape
             runs, count = self._runs(self.cc_map[:B * H * W].view(B, H, W) if self.instances is not None else labels)
             ys = [c._replace(runs=runs[b:b + 1], count=count[b:b + 1]) for b, c in enumerate(ys)]
+        if self.confidence is not None:
+            if logits is None:
+                raise StswinHipError("internal error: confidence needs the logits the labels were made from")
+            B, H, W = labels.shape
+            conf = hip.upsample_confidence(logits.contiguous(), labels, self.align_corners)
+            sums = hip.confidence_sums(labels, conf, self.classes, self.confidence_low)
+            inst = None
+            if self.instances is not None:
+                inst = hip.confidence_sums(self.cc_map[:B * H * W].view(B, H, W), conf, self.instances, self.confidence_low)
+            ys = [c._replace(conf=conf[b:b + 1], class_sums=sums[b:b + 1], instance_sums=None if inst is None else inst[b:b + 1])
+                  for b, c in enumerate(ys)]
         return ys
 
     def released(self, frames: Sequence[int], results: list, ys: Optional[List[Yield]]) -> list:
         """The clips of `frames` are released with `results` and what their labels yielded: clips not tracked yet are, in the step's
-        order; then report="frame" and masks="frame" append to each result (on the device), and a row is logged when either is
-        "deferred".  -> the results."""
-        if self.report is None and self.masks is None:
+        order; then report="frame", masks="frame" and confidence="frame" append to each result (on the device), and a row is logged
+        when any of them is "deferred".  -> the results."""
+        if self.report is None and self.masks is None and self.confidence is None:
             return results
         if self.tracks:
             ys = [y if y.ids is not None else self._track(g, b, y) for b, (g, y) in enumerate(zip(frames, ys))]
-        if "frame" in (self.report, self.masks):
-            results = [y.appended(r, self.report == "frame", self.masks == "frame") for r, y in zip(results, ys)]
-        if "deferred" in (self.report, self.masks):
+        if "frame" in (self.report, self.masks, self.confidence):
+            results = [y.appended(r, self.report == "frame", self.masks == "frame", self.confidence == "frame") for r, y in zip(results, ys)]
+        if "deferred" in (self.report, self.masks, self.confidence):
             for g, y in zip(frames, ys):
-                row = y.logged(self.log, g, g not in self.parked, self.report == "deferred", self.masks == "deferred")
+                row = y.logged(self.log, g, g not in self.parked, self.report == "deferred", self.masks == "deferred",
+                               self.confidence == "deferred")
                 if g in self.parked and self.report == "deferred":
                     self.parked[g].log_row = row
         return results
