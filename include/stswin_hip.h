@@ -224,7 +224,9 @@ int stswin_tn_combine(const float* workspace, float* C, long ldc, int Ni, int Nj
 /* Which kernel the launcher chose for the calling thread's most recent stswin_gemm_nt (family 0) / stswin_gemm_tn
  * (family 1) call: one of the codes below (family 1: | slab bits | split count << 16).  Test instrumentation only - the
  * parity suite asserts that the production shapes of the training step run the production kernels
- * (swin_512.py:109-141 qkv/proj, :7-23 Mlp, resnet.py:31-34 3x3 convolutions and their weight gradients). */
+ * (swin_512.py:109-141 qkv/proj, :7-23 Mlp, resnet.py:31-34 3x3 convolutions and their weight gradients), and the float64
+ * contracts assert the word per kernel and per combine form: tests/test_hip_gemm_nt_contract.py for family 0,
+ * tests/test_hip_gemm_tn_contract.py for family 1 (the whole word: kernel code, slab type, fused, tap-minor, split count). */
 #define STSWIN_VAR_F32 100                 /* added to a 128x128-family code when the exact-fp32 instantiation ran */
 #define STSWIN_VAR_NT_RING256_REGEPI 1     /* 256x256 ping-pong ring, operand-swapped MFMA + register epilogue (production) */
 #define STSWIN_VAR_NT_RING256_LDSEPI 2     /* 256x256 ping-pong ring, fp32 LDS epilogue (fp32 outputs, unaligned operands) */
