@@ -96,9 +96,15 @@ int stswin_stem_im2col(int dtype, const float* img, void* patches, long ld, int 
  * the last record (the last segment reads on). */
 int stswin_stem_s2d(int dtype, const float* img, void* out, int frames, int H, int W, void* stream);
 /* The stem convolution over the space-to-depth image `rec` of stswin_stem_s2d (bf16): y bf16 [F*Ho*Wo][64] = conv(7, 2, 3) with
- * wmat bf16 [64][4][4][16] (= [cout][tap row][record][position], zeros where the 7 x 7 window has no tap); stats (or NULL): the
- * STSWIN_GF_CS_SQ table of y.  Record rows pass through an LDS ring once, the weights live in registers: replaces stswin_gemm_nt
- * over the row map for this M = F*Ho*Wo, N = 64, K = 256 shape.  Wo % 128 != 0: -1732, nothing launched.  resnet.py:98-102. */
+ * wmat bf16 [64][4][4][16] (= [cout][tap row][record][position], zeros where the 7 x 7 window has no tap); stats (or NULL): a
+ * STSWIN_GF_CS_SQ table ([2][2*ceil(M/256)][64]) of the fp32 values BEFORE the bf16 store, written per RUN: a workgroup takes `per`
+ * consecutive units (unit = one output row of a 128-pixel-wide strip = one 128-row block), a run ends with the workgroup's units or
+ * with the strip; the row of a run's FIRST block holds the sums | sums of squares of the whole run, the rows of its other blocks hold
+ * 0.0.  Every row up to M/128 is written; consumers must add the rows of whole frames (stswin_cs_group_reduce and
+ * stswin_bn_table_finalize over groups of whole frames), a single row is not the sum of its own block.  Record rows pass through an LDS ring once, the weights live in registers:
+ * replaces stswin_gemm_nt over the row map for this M = F*Ho*Wo, N = 64, K = 256 shape.  Wo % 128 != 0: -1732, nothing launched.
+ * resnet.py:98-102.  Per-element contract (this kernel, stswin_stem_wgrad, stswin_conv3x3_c64 and stswin_conv3x3_c64_wgrad):
+ * tests/conv_halo_ref.py, tests/test_conv_halo_ref.py, tests/test_hip_conv_halo_contract.py. */
 int stswin_stem_conv(const void* rec, const void* wmat, void* y, float* stats, int frames, int H, int W, void* stream);
 /* Weight gradient of the stem convolution from dy (bf16 [F*Ho*Wo][64]) and the space-to-depth image `rec` of stswin_stem_s2d (bf16):
  * dw fp32 [64][4][4][16] = [cout][tap row][record][position], the order stswin_gemm_tn produces over the row map (accumulate != 0 adds).
@@ -130,9 +136,11 @@ int stswin_maxpool3x3s2(int dtype, const void* in, long ldi, void* out, long ldo
  * used by resnet.py:104-105, basic blocks resnet.py:31-51) from an LDS-resident halo with the weights in registers: replaces the
  * gather form of stswin_gemm_nt for these shapes.  wmat = the [64][9][64] matrices stswin_conv_pack makes; sign = +1 with the fwd
  * matrix: the convolution; sign = -1 with the dgrad matrix: its input gradient (x = dy).  resid (or NULL): [frames*H*W][64] added
- * before the store (a gradient another consumer of the input produced); stats (or NULL): the STSWIN_GF_CS_SQ table of the stored
- * values ([2][2*ceil(M/256)][64]: per-128-row-block column sums | sums of squares).  W in {16, 32, 64, 128}, H*W % 256 == 0; other
- * geometries return -1702 / -1701 and launch nothing (the caller keeps the gather GEMM). */
+ * before the store (a gradient another consumer of the input produced); stats (or NULL): the STSWIN_GF_CS_SQ table
+ * ([2][2*ceil(M/256)][64]: per-128-row-block column sums | sums of squares) of the fp32 values BEFORE the bf16 store (residual
+ * included), not of the stored bf16 values; every row is written, also when workgroups are left without a tile.  W in {16, 32, 64,
+ * 128}, H*W % 256 == 0; other geometries return -1702 / -1701 and launch nothing (the caller keeps the gather GEMM).  Per-element
+ * contract: tests/conv_halo_ref.py, tests/test_conv_halo_ref.py, tests/test_hip_conv_halo_contract.py. */
 int stswin_conv3x3_c64(const void* x, const void* wmat, void* y, const void* resid, float* stats, int frames, int H, int W, int sign,
                        void* stream);
 /* Weight gradient of the same convolution from dy and x (both bf16 [frames*H*W][64]): dw fp32 [64][9][64] (the order of

@@ -16,8 +16,9 @@
 //   y[p][co] = sum_{tap, ci} x[p + off(tap)][ci] * w[co][tap * 64 + ci]      off(tap) = sign * (tap / 3 - 1, tap % 3 - 1)
 // sign = +1: forward (w = the tap-major forward matrix of stswin_conv_pack); sign = -1: input gradient (w = its dgrad matrix,
 // taps in forward order: the inverse row map negates the offsets, stswin_conv_rowmap).  Optional: + R (the gradient another
-// consumer of the input produced: headops.GradLink), per-128-row-block column sums and sums of squares of the stored values
-// (the BatchNorm statistics table of STSWIN_GF_CS_SQ: [2][2 * ceil(M / 256)][64]).
+// consumer of the input produced: headops.GradLink), per-128-row-block column sums and sums of squares of the fp32 values before
+// the bf16 store (the BatchNorm statistics table of STSWIN_GF_CS_SQ: [2][2 * ceil(M / 256)][64]).  Per-element contract of the four
+// kernels of this file: tests/conv_halo_ref.py, tests/test_hip_conv_halo_contract.py.
 #include "common.h"
 
 struct ConvHaloArgs {

@@ -137,7 +137,7 @@ def bound(P, Ab, ranges, *, c_prev=None, slab_bf16=False, rows_kernel=False):
         Mk = ranges[-1][1] - ranges[0][0]
         return (2 * Mk + 2) * U * (Ab.sum(0) + cp)
     splits = len(ranges)
-    rows = torch.tensor([m1 - m0 for m0, m1 in ranges], dtype=F64)[:, None, None]
+    rows = torch.tensor([m1 - m0 for m0, m1 in ranges], dtype=F64, device=P.device)[:, None, None]
     E = (rows + 2) * U * Ab
     H = half_ulp_bf16(P.abs() + E) if slab_bf16 else torch.zeros_like(E)
     T = cp + (P.abs() + E + H).sum(0)
