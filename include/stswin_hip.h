@@ -783,6 +783,35 @@ int stswin_upsample_confidence(int dtype, const void* logits, const unsigned cha
  * out not 8-byte aligned. */
 int stswin_confidence_sums(const void* map /*[n][H][W]*/, int map_bytes /*1: uint8, 4: int32*/, const unsigned char* conf /*[n][H][W]*/,
                            long long* out /*[n][K][3]*/, int K, int low, int n, int H, int W, void* stream);
+/* ---- parts and contacts of the instances (stswincl_amd/utils/instruments.py instance_parts, VideoSegmenter(parts=...)): what an
+ * instance is made of and what it touches.  labels uint8 [n][H][W], the model's labels (ungrouped, where VideoSegmenter(instance_groups=
+ * ...) took the components of grouped ones); components int32 [n][H][W], the map of stswin_label_components, -1 = none.
+ *   parts[f][i][c], 0 <= i < K, 0 <= c < nc: the ten integers of stswin_label_moments - count, sum x, sum y, sum x^2, sum xy, sum y^2,
+ *       max(W - x), max(H - y), max(x + 1), max(y + 1) - over the pixels (y, x) of frame f with components == i and labels == c; all
+ *       zero where there are none.
+ *   contacts[f][i][c]: the number of ordered pairs (p, q), p a pixel of frame f with components[p] == i, q one of p's four neighbours
+ *       inside the frame with components[q] != i and labels[q] == c: the length in pixel edges of the border between instance i and
+ *       class c outside it, whatever the connectivity the components were taken with.  Borders between the parts of one instance are
+ *       not counted; a neighbour of another instance, of a skipped class or of an ordinal >= K is counted under its label.
+ * Pixels with ordinal -1 or >= K are nobody's p; labels >= nc count nowhere, neither in parts nor as q's class.  Both outputs are
+ * written in full by the call (cleared by a fill kernel each on the stream, no memset node): a second call into the same outputs
+ * overwrites.  Three launches, no scratch buffer, no allocation, no synchronisation (graph-capturable); integer atomics only (adds and
+ * maxima: exact, independent of the order, bit-reproducible); no kernel waits on another workgroup.  A workgroup takes a tile of
+ * stswin_instance_parts_geometry(0) x (1) pixels and reads each map once plus the one-pixel frame around the tile; a thread folds the
+ * runs of equal (ordinal, class) along 16 pixels of a row and adds them to a keyed table of stswin_instance_parts_geometry(2) slots
+ * on chip, whose slots in use go out with one 64-bit atomic per non-zero integer; a key that finds no slot among its probes - always
+ * so once the table is full - adds to the outputs directly, with the same result.  Any W and any pointer: labels and components
+ * 16-byte aligned with W % 16 == 0 takes the body with 16-byte loads, anything else the element body.  1 <= H, W <= 16384, 1 <= nc <=
+ * 64, 1 <= K <= 1024; every sum fits an int64 and contacts <= 4 H W.  The buffers must not overlap (the host wrapper checks).
+ * Errors, before anything is launched: -1890 n, H or W <= 0, or H or W > 16384 (or more workgroups than a grid holds); -1891 labels,
+ * components, parts or contacts NULL; -1892 nc outside 1 .. 64; -1893 K outside 1 .. 1024; -1894 components not 4-byte aligned, or parts
+ * or contacts not 8-byte aligned. */
+int stswin_instance_parts(const unsigned char* labels /*[n][H][W]*/, const int* components /*[n][H][W]*/,
+                          long long* parts /*[n][K][nc][10]*/, long long* contacts /*[n][K][nc]*/, int n, int H, int W, int nc, int K,
+                          void* stream);
+/* the geometry of stswin_instance_parts (the tests place their shapes around it): which = 0: the tile's height (32), 1: its width
+ * (128), 2: the slots of the on-chip table (64); anything else: -1. */
+int stswin_instance_parts_geometry(int which);
 /* ---- frames as a video source delivers them (stswincl_amd/utils/yuv.py, VideoSegmenter(pixel_format=..., out_format="nv12")):
  * stswin_yuv_to_rgb makes the HWC RGB frame uint8 [n][Hs][Ws][3] that stswin_frame_ingest and stswin_labels_overlay read,
  * stswin_rgb_to_nv12 turns such a frame into NV12.  Hs (NV12) and Ws are even.

@@ -1854,6 +1854,267 @@ extern "C" int stswin_confidence_sums(const void* map, int map_bytes, const unsi
   return 0;
 }
 
+// Parts and contacts of the instances (utils/instruments.py, instance_parts, states the result; VideoSegmenter(parts=...)): per frame,
+// instance ordinal i < K and class c < nc the ten integers of the moments row over the pixels with components == i and labels == c, and
+// the number of pixel edges between instance i and pixels of class c outside it.  A workgroup takes a tile of IP_TH x IP_TW pixels of
+// one frame, a thread IP_PPT = 16 consecutive pixels of one row.  A pixel becomes one word, (ordinal + 1) << 8 | label with ordinal + 1
+// = 0 for -1 and ordinals >= K; the tile's words and those of the one-pixel frame around it (IP_NONE outside the map) go through LDS,
+// so each map is read once plus that halo.  K nc 11 bins do not fit on chip, but a tile of a real map holds a handful of distinct
+// (ordinal, class) keys: a thread folds the runs of equal keys along its 16 pixels in registers (the moments of a run in closed form
+// by lm_run; the edges towards the row above, the row below, the left and the right each as runs of equal (ordinal, neighbour's
+// class)) and adds every run to a keyed table of IP_SLOTS slots in LDS, found by a multiplicative hash and up to IP_PROBES linear
+// probes.  The slots in use go out with one 64-bit atomic per non-zero integer.  A key that finds none of its probe slots free or its
+// own - always so once the table is full - adds to the outputs directly: integer adds and maxima only, so the result is the same
+// either way and whatever the order.  WIDE: both maps 16-byte aligned and W % 16 == 0, one 16-byte load of labels and four of
+// components per thread; else element by element.  The halo is always read by element.
+#define IP_TH 32
+#define IP_TW 128
+#define IP_PPT 16
+#define IP_CPR (IP_TW / IP_PPT)               // threads per row of the tile
+#define IP_THREADS (IP_TH * IP_CPR)
+#define IP_RS (IP_TW + 4)                     // words per LDS row: 16-byte aligned rows that start on different banks
+#define IP_SLOTS 64
+#define IP_PROBES 8
+#define IP_NONE 255u                          // no ordinal and a label no class has (nc <= 64): nobody's p, nobody's q
+static_assert(IP_SLOTS == 64, "ip_slot takes the hash's top 6 bits");
+
+struct IpTable {
+  unsigned key[IP_SLOTS];                     // the slot's word (ordinal + 1) << 8 | class, 0: free
+  unsigned long long sums[IP_SLOTS * 6];      // (a tile's sum x^2 passes 2^32)
+  unsigned ext[IP_SLOTS * 4];
+  unsigned touch[IP_SLOTS];                   // <= 4 IP_TH IP_TW
+};
+
+__device__ __forceinline__ unsigned ip_word(int comp, unsigned label, int K) {
+  return ((unsigned)comp < (unsigned)K ? (unsigned)comp + 1u : 0u) << 8 | label;
+}
+
+__device__ __forceinline__ int ip_slot(IpTable& tb, unsigned word) {
+  const unsigned h = (word * 2654435761u) >> 26;
+  for (int t = 0; t < IP_PROBES; ++t) {
+    const int s = (int)((h + t) & (IP_SLOTS - 1));
+    const unsigned old = atomicCAS(&tb.key[s], 0u, word);
+    if (old == 0u || old == word) return s;
+  }
+  return -1;
+}
+
+__device__ __forceinline__ long ip_at(unsigned word, int nc) { return (long)((word >> 8) - 1u) * nc + (long)(word & 255u); }
+
+__device__ __forceinline__ void ip_moments(IpTable& tb, unsigned long long* parts_f, int nc, unsigned word, const LmTerms& t) {
+  const int s = ip_slot(tb, word);
+  if (s >= 0) {
+    lm_flush(tb.sums, tb.ext, (unsigned)s, t);
+  } else {
+    unsigned long long* o = parts_f + ip_at(word, nc) * 10;
+    atomicAdd(o + 0, (unsigned long long)t.n);
+    atomicAdd(o + 1, (unsigned long long)t.sx);
+    atomicAdd(o + 2, (unsigned long long)t.sy);
+    atomicAdd(o + 3, t.sxx);
+    atomicAdd(o + 4, t.sxy);
+    atomicAdd(o + 5, t.syy);
+    atomicMax(o + 6, (unsigned long long)t.e0);
+    atomicMax(o + 7, (unsigned long long)t.e1);
+    atomicMax(o + 8, (unsigned long long)t.e2);
+    atomicMax(o + 9, (unsigned long long)t.e3);
+  }
+}
+
+__device__ __forceinline__ void ip_touch(IpTable& tb, unsigned long long* contacts_f, int nc, unsigned word, unsigned edges) {
+  const int s = ip_slot(tb, word);
+  if (s >= 0) atomicAdd(&tb.touch[s], edges);
+  else atomicAdd(contacts_f + ip_at(word, nc), (unsigned long long)edges);
+}
+
+// v[a] by masks: every element is read at a constant index (a chain of selects between the elements comes back from the compiler as
+// one indexed load, and the array with it in scratch memory)
+__device__ __forceinline__ unsigned ip_pick(const unsigned (&v)[IP_PPT], int a) {
+  unsigned r = 0u;
+#pragma unroll
+  for (int k = 0; k < IP_PPT; ++k) r |= v[k] & (0u - (unsigned)(a == k));
+  return r;
+}
+
+// f(word, first, length) for every run of equal non-zero words among a thread's 16
+template <typename F>
+__device__ __forceinline__ void ip_runs(const unsigned (&v)[IP_PPT], F f) {
+  unsigned change = 1u, some = v[0] ? 1u : 0u;
+#pragma unroll
+  for (int k = 1; k < IP_PPT; ++k) {
+    if (v[k] != v[k - 1]) change |= 1u << k;
+    if (v[k]) some |= 1u << k;
+  }
+  unsigned starts = change & some;
+  while (starts) {
+    const int a = __builtin_ctz(starts);
+    starts &= starts - 1u;
+    const unsigned rest = change >> (a + 1);
+    const int e = rest ? a + 1 + __builtin_ctz(rest) : IP_PPT;
+    f(ip_pick(v, a), a, e - a);
+  }
+}
+
+// the edge of pixel `me` towards neighbour `nb`: (me's ordinal, nb's class) where me has an ordinal, nb another one or none and a class
+__device__ __forceinline__ unsigned ip_edge(unsigned me, unsigned nb, unsigned nc) {
+  return (me >> 8) != 0u && (nb >> 8) != (me >> 8) && (nb & 255u) < nc ? (me & ~255u) | (nb & 255u) : 0u;
+}
+
+template <bool WIDE>
+__global__ __launch_bounds__(IP_THREADS) void instance_parts_kernel(const unsigned char* __restrict__ labels, const int* __restrict__ comps,
+                                                                    unsigned long long* parts, unsigned long long* contacts, int H, int W,
+                                                                    int nc, int K, int tiles_x, int tiles_per_frame) {
+  __shared__ IpTable tb;
+  __shared__ __attribute__((aligned(16))) unsigned tile[(IP_TH + 2) * IP_RS];      // rows 0 and IP_TH + 1: the halo above and below
+  __shared__ unsigned side[2 * IP_TH];                                              // the halo left and right of the tile's rows
+  const int tid = (int)threadIdx.x;
+  for (int i = tid; i < IP_SLOTS; i += IP_THREADS) {
+    tb.key[i] = 0u;
+    tb.touch[i] = 0u;
+  }
+  for (int i = tid; i < 6 * IP_SLOTS; i += IP_THREADS) tb.sums[i] = 0ull;
+  for (int i = tid; i < 4 * IP_SLOTS; i += IP_THREADS) tb.ext[i] = 0u;
+  const int f = (int)(blockIdx.x / (unsigned)tiles_per_frame);
+  const int t = (int)(blockIdx.x % (unsigned)tiles_per_frame);
+  const int ty = t / tiles_x, tx = t - ty * tiles_x;
+  const int y0 = ty * IP_TH, xt = tx * IP_TW;
+  const unsigned char* lf = labels + (long)f * H * W;
+  const int* cf = comps + (long)f * H * W;
+  const int r = tid / IP_CPR, ch = tid - r * IP_CPR;
+  const int y = y0 + r, x0 = xt + ch * IP_PPT;
+  unsigned w[IP_PPT];
+#pragma unroll
+  for (int k = 0; k < IP_PPT; ++k) w[k] = IP_NONE;
+  if (y < H && x0 < W) {
+    const long at = (long)y * W + x0;
+    if (WIDE) {                                                // (W % 16 == 0: the 16 pixels exist)
+      const uint4 lw = *reinterpret_cast<const uint4*>(lf + at);
+      const int4* cp = reinterpret_cast<const int4*>(cf + at);
+#pragma unroll
+      for (int q = 0; q < IP_PPT / 4; ++q) {
+        const int4 c = cp[q];
+        w[4 * q] = ip_word(c.x, lm_byte(lw, 4 * q), K);
+        w[4 * q + 1] = ip_word(c.y, lm_byte(lw, 4 * q + 1), K);
+        w[4 * q + 2] = ip_word(c.z, lm_byte(lw, 4 * q + 2), K);
+        w[4 * q + 3] = ip_word(c.w, lm_byte(lw, 4 * q + 3), K);
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < IP_PPT; ++k)
+        if (x0 + k < W) w[k] = ip_word(cf[at + k], (unsigned)lf[at + k], K);
+    }
+  }
+  uint4* own = reinterpret_cast<uint4*>(tile + (r + 1) * IP_RS + ch * IP_PPT);
+#pragma unroll
+  for (int q = 0; q < IP_PPT / 4; ++q) own[q] = make_uint4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
+  for (int i = tid; i < 2 * IP_TW + 2 * IP_TH; i += IP_THREADS) {
+    int hy, hx;
+    unsigned* d;
+    if (i < IP_TW) {
+      hy = y0 - 1, hx = xt + i, d = tile + i;
+    } else if (i < 2 * IP_TW) {
+      hy = y0 + IP_TH, hx = xt + i - IP_TW, d = tile + (IP_TH + 1) * IP_RS + (i - IP_TW);
+    } else if (i < 2 * IP_TW + IP_TH) {
+      hy = y0 + i - 2 * IP_TW, hx = xt - 1, d = side + (i - 2 * IP_TW);
+    } else {
+      hy = y0 + i - 2 * IP_TW - IP_TH, hx = xt + IP_TW, d = side + IP_TH + (i - 2 * IP_TW - IP_TH);
+    }
+    unsigned v = IP_NONE;
+    if (hy >= 0 && hy < H && hx >= 0 && hx < W) {
+      const long at = (long)hy * W + hx;
+      v = ip_word(cf[at], (unsigned)lf[at], K);
+    }
+    *d = v;
+  }
+  __syncthreads();
+  unsigned long long* pf = parts + (long)f * K * nc * 10;
+  unsigned long long* qf = contacts + (long)f * K * nc;
+  bool any = false;
+#pragma unroll
+  for (int k = 0; k < IP_PPT; ++k) any |= (w[k] >> 8) != 0u;
+  if (any) {                                                   // (a thread of the background, or past the map, has nothing to add)
+    const unsigned ncu = (unsigned)nc;
+    unsigned v[IP_PPT];
+#pragma unroll
+    for (int k = 0; k < IP_PPT; ++k) v[k] = (w[k] >> 8) != 0u && (w[k] & 255u) < ncu ? w[k] : 0u;
+    IpTable* tp = &tb;                                         // (the closures hold values only: nothing of theirs lives in memory)
+    ip_runs(v, [=](unsigned word, int a, int n) {
+      ip_moments(*tp, pf, nc, word, lm_run((unsigned)(x0 + a), (unsigned)n, (unsigned)y, (unsigned)H, (unsigned)W));
+    });
+    const auto touch = [=](unsigned word, int, int n) { ip_touch(*tp, qf, nc, word, (unsigned)n); };
+    const uint4* above = reinterpret_cast<const uint4*>(tile + r * IP_RS + ch * IP_PPT);
+    const uint4* below = reinterpret_cast<const uint4*>(tile + (r + 2) * IP_RS + ch * IP_PPT);
+#pragma unroll
+    for (int q = 0; q < IP_PPT / 4; ++q) {
+      const uint4 u = above[q];
+      v[4 * q] = ip_edge(w[4 * q], u.x, ncu);
+      v[4 * q + 1] = ip_edge(w[4 * q + 1], u.y, ncu);
+      v[4 * q + 2] = ip_edge(w[4 * q + 2], u.z, ncu);
+      v[4 * q + 3] = ip_edge(w[4 * q + 3], u.w, ncu);
+    }
+    ip_runs(v, touch);
+#pragma unroll
+    for (int q = 0; q < IP_PPT / 4; ++q) {
+      const uint4 u = below[q];
+      v[4 * q] = ip_edge(w[4 * q], u.x, ncu);
+      v[4 * q + 1] = ip_edge(w[4 * q + 1], u.y, ncu);
+      v[4 * q + 2] = ip_edge(w[4 * q + 2], u.z, ncu);
+      v[4 * q + 3] = ip_edge(w[4 * q + 3], u.w, ncu);
+    }
+    ip_runs(v, touch);
+    const unsigned lft = ch ? tile[(r + 1) * IP_RS + ch * IP_PPT - 1] : side[r];
+    const unsigned rgt = ch < IP_CPR - 1 ? tile[(r + 1) * IP_RS + (ch + 1) * IP_PPT] : side[IP_TH + r];
+#pragma unroll
+    for (int k = 0; k < IP_PPT; ++k) v[k] = ip_edge(w[k], k ? w[k - 1] : lft, ncu);
+    ip_runs(v, touch);
+#pragma unroll
+    for (int k = 0; k < IP_PPT; ++k) v[k] = ip_edge(w[k], k < IP_PPT - 1 ? w[k + 1] : rgt, ncu);
+    ip_runs(v, touch);
+  }
+  __syncthreads();
+  for (int i = tid; i < IP_SLOTS * 11; i += IP_THREADS) {
+    const int s = i / 11, k = i - 11 * s;
+    const unsigned word = tb.key[s];
+    if (!word) continue;
+    const long at = ip_at(word, nc);
+    if (k < 6) {
+      const unsigned long long sum = tb.sums[6 * s + k];
+      if (sum) atomicAdd(pf + at * 10 + k, sum);
+    } else if (k < 10) {
+      const unsigned e = tb.ext[4 * s + k - 6];
+      if (e) atomicMax(pf + at * 10 + k, (unsigned long long)e);
+    } else if (tb.touch[s]) {
+      atomicAdd(qf + at, (unsigned long long)tb.touch[s]);
+    }
+  }
+}
+
+extern "C" int stswin_instance_parts(const unsigned char* labels, const int* components, long long* parts, long long* contacts, int n,
+                                     int H, int W, int nc, int K, void* stream) {
+  if (n <= 0 || H <= 0 || W <= 0 || H > 16384 || W > 16384) return -1890;
+  if (labels == nullptr || components == nullptr || parts == nullptr || contacts == nullptr) return -1891;
+  if (nc < 1 || nc > 64) return -1892;
+  if (K < 1 || K > 1024) return -1893;
+  if (((uintptr_t)components & 3) || (((uintptr_t)parts | (uintptr_t)contacts) & 7)) return -1894;
+  const int tiles_x = (W + IP_TW - 1) / IP_TW;
+  const long tpf = (long)tiles_x * ((H + IP_TH - 1) / IP_TH);
+  if (tpf * n > 0x7fffffffL) return -1890;
+  const bool wide = (((uintptr_t)labels | (uintptr_t)components) & 15) == 0 && W % IP_PPT == 0;
+  dim3 grid((unsigned)(tpf * n));
+  hipStream_t st = (hipStream_t)stream;
+  unsigned long long* p = reinterpret_cast<unsigned long long*>(parts);
+  unsigned long long* q = reinterpret_cast<unsigned long long*>(contacts);
+  stswin_zero_bytes(parts, (size_t)n * K * nc * 10 * sizeof(long long), st);        // (a kernel, not hipMemsetAsync: see common.h)
+  stswin_zero_bytes(contacts, (size_t)n * K * nc * sizeof(long long), st);
+  if (wide) hipLaunchKernelGGL(instance_parts_kernel<true>, grid, dim3(IP_THREADS), 0, st, labels, components, p, q, H, W, nc, K, tiles_x, (int)tpf);
+  else hipLaunchKernelGGL(instance_parts_kernel<false>, grid, dim3(IP_THREADS), 0, st, labels, components, p, q, H, W, nc, K, tiles_x, (int)tpf);
+  STSWIN_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int stswin_instance_parts_geometry(int which) {
+  return which == 0 ? IP_TH : which == 1 ? IP_TW : which == 2 ? IP_SLOTS : -1;
+}
+
 // Connected components of a label map and their moments rows (stswincl_amd/utils/instruments.py, label_components, states the
 // result; VideoSegmenter(instances=K)): block-based union-find on an int32 parent map of frame-local pixel indices y W + x.  A link
 // only ever points to a smaller index of the same component (LDS or global atomicMin), so a component's root is its first pixel in

@@ -1918,6 +1918,60 @@ def confidence_sums(maps: torch.Tensor, conf: torch.Tensor, K: int, low: int = 1
     return out
 
 
+def instance_parts_geometry():
+    """(tile height, tile width, on-chip key slots) of hip.instance_parts (stswin_instance_parts_geometry)."""
+    geo = load().stswin_instance_parts_geometry
+    return geo(0), geo(1), geo(2)
+
+
+def instance_parts(labels: torch.Tensor, components: torch.Tensor, K: int, nc: int, out=None):
+    """uint8 labels [n][H][W] and int32 components [n][H][W] (hip.label_components' map, -1 = none) -> (parts int64 [n][K][nc][10],
+    contacts int64 [n][K][nc]): per frame, instance ordinal i < K and class c < nc the ten integers of label_moments over the pixels
+    with components == i and labels == c, and the number of pixel edges between instance i and pixels of class c outside it (p in i, q
+    one of p's four neighbours with components[q] != i and labels[q] == c).  Ordinals -1 and >= K are nobody's, labels >= nc count
+    nowhere (utils.instruments.instance_parts is the numpy definition, matched bit for bit).  out: the pair of such buffers, written
+    in full - cleared by a fill kernel, so a second call overwrites; with it the call allocates nothing, and it never synchronises
+    (graph-capturable).  Three launches.  Returns the pair (include/stswin_hip.h, stswin_instance_parts)."""
+    if not isinstance(labels, torch.Tensor) or labels.dtype != torch.uint8 or labels.dim() != 3 or not labels.is_contiguous():
+        raise StswinHipError(f"instance_parts: labels must be contiguous uint8 [n][H][W], got {_got(labels)}")
+    if (not isinstance(components, torch.Tensor) or components.dtype != torch.int32 or components.shape != labels.shape
+            or not components.is_contiguous()):
+        raise StswinHipError(f"instance_parts: components must be contiguous int32 {tuple(labels.shape)} as the labels are, got "
+                             f"{_got(components)}")
+    if not labels.is_cuda or not components.is_cuda:
+        raise StswinHipError("instance_parts: labels and components must be on the GPU (no CPU path exists; "
+                             "utils.instruments.instance_parts is the numpy definition)")
+    if components.device != labels.device:
+        raise StswinHipError(f"instance_parts: components must be on {labels.device} as the labels are, got {components.device}")
+    n, H, W = labels.shape
+    if n <= 0 or H <= 0 or W <= 0:
+        raise StswinHipError(f"instance_parts: empty labels {tuple(labels.shape)}")
+    if H > 16384 or W > 16384:
+        raise StswinHipError(f"instance_parts: a {H} x {W} map, the kernel takes up to 16384 x 16384")
+    if isinstance(K, bool) or not isinstance(K, int) or not 1 <= K <= 1024:
+        raise StswinHipError(f"instance_parts: K must be an int 1 .. 1024, got {K!r}")
+    if isinstance(nc, bool) or not isinstance(nc, int) or not 1 <= nc <= 64:
+        raise StswinHipError(f"instance_parts: {nc!r} classes, the kernel takes 1 .. 64")
+    dev = labels.device
+    want = (("parts", (n, K, nc, 10)), ("contacts", (n, K, nc)))
+    if out is None:
+        out = tuple(torch.empty(shape, dtype=torch.int64, device=dev) for _, shape in want)
+    else:
+        if not isinstance(out, (tuple, list)) or len(out) != 2:
+            raise StswinHipError("instance_parts: out must be the pair (parts, contacts)")
+        for t, (what, shape) in zip(out, want):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
+                form = "".join(f"[{d}]" for d in shape)
+                raise StswinHipError(f"instance_parts: {what} must be contiguous int64 {form} on {dev}, got {_got(t)}")
+        bufs = (("labels", labels), ("components", components), ("parts", out[0]), ("contacts", out[1]))
+        for i, (wa, a) in enumerate(bufs[:3]):
+            for wb, b in bufs[max(i + 1, 2):]:
+                if _same_memory(a, b):
+                    raise StswinHipError(f"instance_parts: {wb} shares memory with {wa}")
+    _check(load().stswin_instance_parts(_p(labels), _p(components), _p(out[0]), _p(out[1]), n, H, W, nc, K, _stream()), "instance_parts")
+    return tuple(out)
+
+
 YUV_NV12, YUV_UYVY = 0, 1                    # stswin_yuv_to_rgb's `format` (plain integers in the header's comment, not #defines)
 YUV_REPLICATE, YUV_LINEAR = 0, 1               # ... and its `chroma`
 _YUV_FORMATS = {"nv12": YUV_NV12, "uyvy": YUV_UYVY}

@@ -17,7 +17,12 @@ InstanceReport reads those rows as InstrumentReport reads the class rows, by the
 InstanceTracker gives the instances of consecutive frames a common id (hip.track_instances, VideoSegmenter(tracks=True)) by greedy
 matching on intersection over union in integers, and TrackReport reads the ids beside an InstanceReport: one entry per track.
 
-This module ships no dataset's class names: pass `names` if the rows of a log should carry them."""
+group_table maps the classes that are parts of one instrument (shaft, wrist, clasper) to one representative, so that the components of
+the grouped labels are whole instruments (VideoSegmenter(instance_groups=...)); instance_parts says per instance and class what it
+is made of (the ten integers again) and how many pixel edges it shares with each class outside itself (hip.instance_parts,
+VideoSegmenter(parts=...)), and PartsReport reads both beside the instance and track reports.
+
+This module ships no dataset's class names or ids: pass `names` if the rows of a log should carry them."""
 from __future__ import annotations
 
 import math
@@ -589,4 +594,175 @@ class TrackReport:
             for i in np.nonzero(self.report.present[r])[0]:
                 out[k]["track"] = int(self.ids[r, i])
                 k += 1
+        return out
+
+
+def check_groups(groups, nc: int, skip: Sequence[int] = ()) -> tuple:
+    """Instance groups (VideoSegmenter(instance_groups=...)) as a tuple of tuples of ints, or ValueError: a sequence of groups, each a
+    sequence of at least two distinct classes 0 .. nc - 1, the groups disjoint, no class of a group in `skip`."""
+    try:
+        out = tuple(tuple(g) for g in groups)
+    except TypeError:
+        raise ValueError(f"instance_groups is a sequence of groups of classes, got {groups!r}") from None
+    seen = set()
+    for g in out:
+        if any(isinstance(c, bool) or not isinstance(c, (int, np.integer)) or not 0 <= c < nc for c in g):
+            raise ValueError(f"instance_groups: a group holds classes 0 .. {nc - 1}, got {g!r}")
+        if len(g) < 2 or len(set(g)) != len(g):
+            raise ValueError(f"instance_groups: a group holds at least two distinct classes, got {g!r}")
+        if seen & set(g):
+            raise ValueError(f"instance_groups: the groups are disjoint, {sorted(seen & set(g))} are in two")
+        if set(g) & set(skip):
+            raise ValueError(f"instance_groups: {sorted(set(g) & set(skip))} are skipped classes (instance_skip) and cannot be parts")
+        seen |= set(g)
+    return tuple(tuple(int(c) for c in g) for g in out)
+
+
+def group_table(groups, nc: int) -> np.ndarray:
+    """Instance groups -> uint8 [256]: every grouped class maps to its group's representative, the smallest class of the group, and
+    every other byte value to itself (values >= nc stay >= nc and so outside every component).  The id-coded table of hip.gt_decode;
+    with it the components of a frame are label_components(group_table[labels], ...): one instrument instead of its parts."""
+    table = np.arange(256, dtype=np.uint8)
+    for g in check_groups(groups, nc):
+        table[list(g)] = min(g)
+    return table
+
+
+def instance_parts(labels, components, K: int, nc: int):
+    """Integer labels [n][H][W] and components [n][H][W] (label_components' map, -1 = none; or one [H][W] each) -> (parts int64
+    [n][K][nc][10], contacts int64 [n][K][nc]): what hip.instance_parts gives bit for bit.
+
+    parts[f][i][c], 0 <= i < K, 0 <= c < nc: the ten integers of the moments row over the pixels of frame f with components == i and
+    labels == c (all zero where there are none).  contacts[f][i][c]: the number of ordered pairs (p, q), p a pixel of frame f with
+    components[p] == i, q one of p's four neighbours inside the frame with components[q] != i and labels[q] == c - the length in
+    pixel edges of the border between instance i and class c outside it.  Borders between the parts of one instance are not counted;
+    a neighbour of another instance, of a skipped class or of an ordinal >= K is counted under its label.  Pixels with ordinal -1 or
+    >= K are nobody's p; labels >= nc count nowhere."""
+    lab, comp = np.asarray(labels), np.asarray(components)
+    if lab.ndim == 2 and comp.ndim == 2:
+        lab, comp = lab[None], comp[None]
+    if lab.ndim != 3 or lab.dtype.kind not in "iu" or min(lab.shape) < 1:
+        raise ValueError(f"instance_parts: labels are integers [n][H][W], got {lab.dtype} {lab.shape}")
+    if comp.shape != lab.shape or comp.dtype.kind not in "iu":
+        raise ValueError(f"instance_parts: components are integers {lab.shape} as the labels are, got {comp.dtype} {comp.shape}")
+    if isinstance(K, bool) or int(K) != K or not 1 <= K <= 1024:
+        raise ValueError(f"instance_parts: K is 1 .. 1024, got {K!r}")
+    if isinstance(nc, bool) or int(nc) != nc or not 1 <= nc <= 64:
+        raise ValueError(f"instance_parts: 1 .. 64 classes, got {nc!r}")
+    n, H, W = lab.shape
+    lab, comp = lab.astype(np.int64), comp.astype(np.int64)
+    ys, xs = np.meshgrid(np.arange(H, dtype=np.int64), np.arange(W, dtype=np.int64), indexing="ij")
+    parts = np.zeros((n, K * nc, ROW), dtype=np.int64)
+    contacts = np.zeros((n, K * nc), dtype=np.int64)
+    owned = (comp >= 0) & (comp < K)
+    classed = (lab >= 0) & (lab < nc)
+    for f in range(n):
+        m = owned[f] & classed[f]
+        if m.any():
+            key, x, y = comp[f][m] * nc + lab[f][m], xs[m], ys[m]
+            order = np.argsort(key, kind="stable")
+            key, x, y = key[order], x[order], y[order]
+            first = np.flatnonzero(np.r_[True, key[1:] != key[:-1]])
+            at = key[first]
+            for k, v in enumerate((np.ones_like(x), x, y, x * x, x * y, y * y)):
+                parts[f, at, k] = np.add.reduceat(v, first)
+            for k, v in enumerate((W - x, H - y, x + 1, y + 1)):
+                parts[f, at, 6 + k] = np.maximum.reduceat(v, first)
+        # p and q = p + (dy, dx) for the four neighbours, as slices of the frame
+        for p, q in (((slice(1, None), slice(None)), (slice(None, -1), slice(None))), ((slice(None, -1), slice(None)), (slice(1, None), slice(None))),
+                     ((slice(None), slice(1, None)), (slice(None), slice(None, -1))), ((slice(None), slice(None, -1)), (slice(None), slice(1, None)))):
+            e = owned[f][p] & (comp[f][q] != comp[f][p]) & classed[f][q]
+            contacts[f] += np.bincount(comp[f][p][e] * nc + lab[f][q][e], minlength=K * nc)
+    return parts.reshape(n, K, nc, ROW), contacts.reshape(n, K, nc)
+
+
+class PartsReport:
+    """What the instances are made of and what they touch (hip.instance_parts, VideoSegmenter(parts="deferred").parts_report()), per
+    row-frame r, instance ordinal i < K and class c, from parts [rows][K][nc][10] and contacts [rows][K][nc]:
+
+      has      bool    [rows][K][nc]     instance i holds pixels of class c
+      area     int64   [rows][K][nc]     their number
+      box, centroid, angle, axes         of that part, as InstrumentReport's, by the same arithmetic (NaN where the part is absent)
+      contacts int64   [rows][K][nc]     the pixel edges between instance i and pixels of class c outside it
+
+    With instance_groups the classes of an instance are its parts (shaft, wrist, clasper); without, an instance has the one class of
+    its component.  parts(r, i) and touches(r, i) give the two as dicts, direction(r, i, a, b) the unit vector from part a to part b.
+    instances / tracks: the InstanceReport and TrackReport of the same rows (None: none); as_rows() then lists the present instances
+    with their class (the group's representative) and track.  frames / sequences / names as InstrumentReport's."""
+
+    def __init__(self, parts, contacts, size: Sequence[int], names: Optional[Sequence[str]] = None, frames: Optional[Sequence[int]] = None,
+                 sequences: Optional[Sequence[int]] = None, instances=None, tracks=None):
+        pt, ct = np.asarray(parts), np.asarray(contacts)
+        if pt.ndim == 3:
+            pt = pt[None]
+        if ct.ndim == 2:
+            ct = ct[None]
+        if pt.ndim != 4 or pt.shape[3] != ROW or pt.dtype.kind not in "iu":
+            raise ValueError(f"PartsReport: parts are integers [rows][K][nc][{ROW}], got {pt.dtype} {pt.shape}")
+        if ct.shape != pt.shape[:3] or ct.dtype.kind not in "iu":
+            raise ValueError(f"PartsReport: contacts are integers {pt.shape[:3]} as the parts are, got {ct.dtype} {ct.shape}")
+        n, K, nc = ct.shape
+        if names is not None and len(names) != nc:
+            raise ValueError(f"PartsReport: {len(names)} names for {nc} classes")
+        for what, v in (("frames", frames), ("sequences", sequences)):
+            if v is not None and len(v) != n:
+                raise ValueError(f"PartsReport: {len(v)} {what} for {n} rows")
+        if tracks is not None and instances is None:
+            instances = tracks.report
+        if instances is not None and (len(instances) != n or instances.present.shape[1] != K):
+            raise ValueError(f"PartsReport: an instance report of {len(instances)} rows and {instances.present.shape[1]} instances for "
+                             f"{n} rows and {K} instances")
+        H, W = (int(v) for v in size)
+        self.size = (H, W)
+        self.names = list(names) if names is not None else None
+        self.frames = [int(f) for f in frames] if frames is not None else list(range(n))
+        self.sequences = [int(s) for s in sequences] if sequences is not None else [0] * n
+        self.instances, self.tracks = instances, tracks
+        self.moments, self.contacts = pt.astype(np.int64), ct.astype(np.int64)
+        self.has = self.moments[..., 0] > 0
+        self.area = self.moments[..., 0].copy()
+        self.box = np.full((n, K, nc, 4), np.nan)
+        self.centroid = np.full((n, K, nc, 2), np.nan)
+        self.angle = np.full((n, K, nc), np.nan)
+        self.axes = np.full((n, K, nc, 2), np.nan)
+        for r, i, c in zip(*np.nonzero(self.has)):
+            self.box[r, i, c], self.centroid[r, i, c], self.angle[r, i, c], self.axes[r, i, c] = _shape_of(self.moments[r, i, c], H, W)
+
+    def __len__(self) -> int:
+        return len(self.frames)
+
+    def parts(self, r: int, i: int) -> dict:
+        """class -> {area, box, centroid, angle, axes} for the classes instance i of row r holds, as plain Python values."""
+        return {int(c): {"area": int(self.area[r, i, c]), "box": tuple(int(v) for v in self.box[r, i, c]),
+                         "centroid": tuple(float(v) for v in self.centroid[r, i, c]), "angle": float(self.angle[r, i, c]),
+                         "axes": tuple(float(v) for v in self.axes[r, i, c])} for c in np.nonzero(self.has[r, i])[0]}
+
+    def touches(self, r: int, i: int) -> dict:
+        """class -> the pixel edges instance i of row r shares with pixels of that class outside itself (the classes it touches)."""
+        return {int(c): int(self.contacts[r, i, c]) for c in np.nonzero(self.contacts[r, i])[0]}
+
+    def direction(self, r: int, i: int, a: int, b: int) -> np.ndarray:
+        """float64 [2]: the unit vector (dx, dy) from the centroid of part a of instance i of row r to that of its part b - shaft ->
+        clasper is where the instrument points; NaN where either part is absent or the centroids coincide."""
+        d = self.centroid[r, i, b] - self.centroid[r, i, a]
+        length = float(np.hypot(d[0], d[1]))
+        return d / length if length > 0 else np.full(2, np.nan)
+
+    def as_rows(self) -> List[dict]:
+        """One dict per instance, in row order then instance order, for a log: sequence, frame, instance, class (and name) and track
+        where the instance and track reports were given, parts and touches as above.  With an instance report its present instances
+        are listed, else the instances that hold a pixel."""
+        out = []
+        some = self.instances.present if self.instances is not None else self.has.any(axis=2)
+        for r in range(len(self)):
+            for i in np.nonzero(some[r])[0]:
+                row = {"sequence": self.sequences[r], "frame": self.frames[r], "instance": int(i)}
+                if self.instances is not None:
+                    row["class"] = int(self.instances.cls[r, i])
+                    if self.names is not None:
+                        row["name"] = self.names[row["class"]]
+                if self.tracks is not None:
+                    row["track"] = int(self.tracks.ids[r, i])
+                row["parts"], row["touches"] = self.parts(r, int(i)), self.touches(r, int(i))
+                out.append(row)
         return out

@@ -195,7 +195,7 @@ class VideoSegmenter:
     """Segment video sequences with an eval-mode TswinPlus, one result per frame, each frame's ResNet features computed once.
 
     seg = VideoSegmenter(model, batch=1, out="logits" | "labels" | "overlay", out_size=None, graph=False, report=None, instances=None,
-                         tracks=False, masks=None, boundary=None, confidence=None)
+                         tracks=False, masks=None, boundary=None, confidence=None, instance_groups=None, parts=None)
 
     push(frames, gt=None) takes uint8 RGB frames [n][Hs][Ws][3] (or one [Hs][Ws][3]; torch tensor on the model's GPU or the CPU, or
     a numpy array; NV12 or UYVY frames with pixel_format, below) and returns [(frame_index, result), ...] for the frames whose clip is now complete.  finish() runs what is
@@ -366,6 +366,34 @@ class VideoSegmenter:
     and objects(r) then carry "score", the mean probability of the instance (of the class without instances).  confidence=None: every
     result, launch and captured graph is what it is without the keyword.
 
+    instance_groups=((1, 2, 3), ...) (needs instances=K): the classes that are parts of one instrument - EndoVis18's shaft, wrist and
+    clasper, CaDIS's finer label sets; the ids are the caller's own - so that instances=K reports whole instruments.  A sequence of
+    groups, each at least two distinct classes 0 .. classes - 1, the groups disjoint, none of their classes in instance_skip.  A
+    group's representative is its smallest class.  One launch in front of the component launches (hip.gt_decode, id-coded, with the
+    persistent table utils.instruments.group_table(groups, classes)) writes the grouped labels into a buffer of the chain's own, and
+    the components, rows and total of a frame are exactly utils.instruments.label_components(group_table[labels], ...): the class
+    column of a row holds the representative, which the caller's names call "instrument".  The tracker (track_same_class compares
+    representatives), the masks and the per-instance confidence sums read the component map and follow by construction; the
+    per-class moments of report= stay on the ungrouped labels.  instance_groups=None: every result, launch and captured graph is
+    what it is without the keyword.
+
+    parts="frame" | "deferred" (needs instances=K; with or without instance_groups; both protocols, every scores mode, batch > 1 and
+    graph=True): what each instance is made of and what it touches.  Wherever the component launches run, the scoring paths with
+    ground truth included, hip.instance_parts (utils.instruments.instance_parts states the result) takes over the labels (ungrouped)
+    and the chain's component map, per instance ordinal i < K and class c, parts int64 [K][nc][10], the ten integers of the moments
+    over the pixels of instance i with label c, and contacts int64 [K][nc], the pixel edges between instance i and pixels of class c
+    outside it (needle in clasper, instrument on kidney; borders between an instance's own parts are not counted) - behind the
+    component launches and before the next clip's components overwrite the map, where the masks are encoded: nothing depends on the
+    tracker, a parked frame is summed when its labels exist.  parts="frame": a result r becomes r + (parts, contacts) behind whatever
+    report, masks and confidence append, on the device.  Under graph=True the launch is part of the captured steady step and the two
+    tensors of the last replayed step of a push are views of the graph's buffers; with ground truth they are made after the replay.
+    parts="deferred": results are unchanged and both tensors go into the device log; parts_report(names=None) downloads once and
+    returns utils.instruments.PartsReport - per instance the area, box, centroid and principal axis of every class it holds,
+    touches(r, i) class -> edges, direction(r, i, a, b) the unit vector from part a's centroid to part b's (shaft -> clasper: the
+    heading) - over every frame released since reset_metrics(), in instrument_report()'s order and with its sequence ordinals,
+    joined by row with instance_report() under report="deferred" and with track_report() under tracks=True.  parts=None: every
+    result, launch and captured graph is what it is without the keyword.
+
     Runs under torch.no_grad().  Refuses (StswinHipError): a model in train mode, a model or frames not on the GPU, a frame size
     that differs from the earlier frames'."""
 
@@ -377,7 +405,8 @@ class VideoSegmenter:
                  instances: Optional[int] = None, connectivity: int = 8, instance_skip: Optional[Sequence[int]] = None,
                  tracks: bool = False, track_iou: int = 100, track_same_class: bool = True, masks: Optional[str] = None,
                  mask_runs: int = 16384, track_max_gap: int = 0, boundary: Optional[str] = None, boundary_bins: int = 32,
-                 boundary_skip: Optional[Sequence[int]] = None, confidence: Optional[str] = None, confidence_low: int = 128):
+                 boundary_skip: Optional[Sequence[int]] = None, confidence: Optional[str] = None, confidence_low: int = 128,
+                 instance_groups=None, parts: Optional[str] = None):
         if out not in ("logits", "labels", "overlay"):
             raise StswinHipError(f"out must be 'logits', 'labels' or 'overlay', got {out!r}")
         if pixel_format not in PIXEL_FORMATS:
@@ -428,8 +457,9 @@ class VideoSegmenter:
         self._score_log = DeviceLog(self.device, {"counts": ((3, classes), torch.int32)})     # scores="deferred": a row per scored frame
         self.chain = ReportChain(self.device, classes, protocol, out, report, min_area, instances, connectivity, instance_skip, tracks,
                                  track_iou, track_same_class, masks, mask_runs, track_max_gap, confidence, confidence_low,
-                                 self.align_corners)
+                                 self.align_corners, parts, instance_groups)
         self.confidence, self.confidence_low = confidence, confidence_low
+        self.parts, self.instance_groups = parts, self.chain.instance_groups
         self.report, self.min_area, self.instances, self.connectivity, self.instance_skip = report, min_area, instances, connectivity, self.chain.instance_skip
         self.tracks, self.track_iou, self.track_same_class = tracks, track_iou, track_same_class
         self.track_max_gap = track_max_gap
@@ -518,7 +548,8 @@ class VideoSegmenter:
     def reset_metrics(self) -> None:
         """Clear what an evaluation pools and reset() keeps: the confusion matrix (protocol="cadis"), the score log and its sequence
         ordinal (scores="deferred"), the instrument log and its ordinal (report="deferred"), the count of unmatched ground-truth
-        pixels (gt_table); masks="deferred" logs into the instrument log; the boundary log and its ordinal (boundary="deferred")."""
+        pixels (gt_table); masks="deferred", confidence="deferred" and parts="deferred" log into the instrument log; the boundary log
+        and its ordinal (boundary="deferred")."""
         if self._cm is not None:
             self._cm.zero_()
         self._score_log.clear()
@@ -644,6 +675,30 @@ class VideoSegmenter:
             return ConfidenceReport.from_sums(cols["class_sums"], cols.get("instance_sums"), self.confidence_low, names, frames, sequences)
         except ValueError as e:
             raise StswinHipError(f"confidence_report: {e}") from e
+
+    def parts_report(self, names: Optional[Sequence[str]] = None):
+        """parts="deferred": one download of the parts log -> utils.instruments.PartsReport over every frame released since
+        reset_metrics() - per instance the area, box, centroid and axis of every class it holds, the classes it touches and
+        direction() from one part to another - rows ordered by sequence and frame as instrument_report()'s, with its sequence
+        ordinals; with report="deferred" joined by row with instance_report(names), with tracks=True with track_report(names) too."""
+        if self.parts != "deferred":
+            raise StswinHipError("parts_report() belongs to parts='deferred'")
+        if self.tracks and self.chain.parked:
+            raise StswinHipError("parts_report(): released frames still wait for their predecessors (finish() the sequence first)")
+        from .utils.instruments import InstanceReport, PartsReport, TrackReport
+        joined = self.report == "deferred"
+        wanted = ("parts", "contacts") + (("rows", "total") if joined else ()) + (("ids", "started") if joined and self.tracks else ())
+        cols, sequences, frames = self.chain.log.download(*wanted)          # the one download: every column the report is made of
+        size = self.out_size or (0, 0)
+        inst = trk = None
+        try:
+            if joined:
+                inst = InstanceReport.from_rows(cols["rows"], cols["total"], size, self.min_area, names, frames, sequences)
+                if self.tracks:
+                    trk = TrackReport.from_ids(inst, cols["ids"], cols["started"])
+            return PartsReport(cols["parts"], cols["contacts"], size, names, frames, sequences, inst, trk)
+        except ValueError as e:
+            raise StswinHipError(f"parts_report: {e}") from e
 
     def instance_report(self, names: Optional[Sequence[str]] = None):
         """report="deferred" with instances=K: one download of the instance log -> utils.instruments.InstanceReport (min_area as given
@@ -836,8 +891,8 @@ class VideoSegmenter:
     def _finish_labels(self, lab: torch.Tensor, frames, clips: Optional[List[int]] = None, steady: bool = False,
                        logits: Optional[torch.Tensor] = None):
         """Labels (B, *out_size) of a step, or of the one clip `clips` names (made by a scoring launch) -> (the result form of out="labels"
-        | "overlay", what the report chain makes of them per clip).  The one statement of the order: moments, components, (tracks), masks,
-        confidence (on `logits`, the ones the labels were made from), overlay."""
+        | "overlay", what the report chain makes of them per clip).  The one statement of the order: moments, (grouping,) components,
+        (tracks), masks, confidence (on `logits`, the ones the labels were made from), parts, overlay."""
         ys = self.chain.labelled(lab, clips, steady, logits=logits)
         return lab if self._table is None else self._overlay(lab, frames), ys
 

@@ -1,5 +1,5 @@
 """What a VideoSegmenter makes of its label maps beside the result (its docstring states the keywords): the chain moments -> instances
--> tracks -> masks with its buffers (ReportChain), its record (Yield), the tracker's frame order (TrackSequencer) and the device log."""
+-> tracks -> masks -> confidence -> parts with its buffers (ReportChain), its record (Yield), the tracker's frame order (TrackSequencer) and the device log."""
 from __future__ import annotations
 
 from collections import namedtuple
@@ -67,38 +67,44 @@ class DeviceLog:
         return cols, [self.keys[r][0] for r in order], [self.keys[r][1] for r in order]
 
 
-class Yield(namedtuple("Yield", "moments rows total ids started runs count conf class_sums instance_sums", defaults=(None,) * 10)):
+class Yield(namedtuple("Yield", "moments rows total ids started runs count conf class_sums instance_sums parts contacts",
+                       defaults=(None,) * 12)):
     """What the labels [B][*out_size] of a step (or of one clip, B = 1) yield on the device: moments int64 [B][nc][10]; with instances
     rows int64 [B][K][12] and total int32 [B]; once tracked ids int32 [B][K] and started int32 [B][1]; with masks runs int32
     [B][cap][2] and count int32 [B]; with confidence conf uint8 [B][*out_size], class_sums int64 [B][nc][3] and, with instances,
-    instance_sums int64 [B][K][3].  Absent fields are None."""
+    instance_sums int64 [B][K][3]; with parts parts int64 [B][K][nc][10] and contacts int64 [B][K][nc].  Absent fields are None."""
     __slots__ = ()
 
     def clip(self, b: int) -> "Yield":
         """Clip b's part [1][...]."""
         return Yield(*(None if t is None else t[b:b + 1] for t in self))
 
-    def appended(self, result, report: bool = True, masks: bool = False, confidence: bool = False):
+    def appended(self, result, report: bool = True, masks: bool = False, confidence: bool = False, parts: bool = False):
         """report="frame": a clip's result r -> r + (moments, rows, total, ids), what there is of them; masks="frame": then
-        + (runs, count); confidence="frame": then + (conf, class_sums[, instance_sums]); all on the device."""
+        + (runs, count); confidence="frame": then + (conf, class_sums[, instance_sums]); parts="frame": then + (parts, contacts); all
+        on the device."""
         extra = tuple(t[0] for t in self[:4] if t is not None) if report else ()
         if masks:
             extra += (self.runs[0], self.count[0])
         if confidence:
             extra += tuple(t[0] for t in (self.conf, self.class_sums, self.instance_sums) if t is not None)
+        if parts:
+            extra += (self.parts[0], self.contacts[0])
         return result + extra if isinstance(result, tuple) else (result,) + extra
 
     def logged(self, log: DeviceLog, frame: int, tracked: bool = True, report: bool = True, masks: bool = False,
-               confidence: bool = False) -> int:
-        """report="deferred", masks="deferred" and / or confidence="deferred": a clip's row in the log -> its index (tracked = False:
-        ids and started are written when it is tracked); the columns of what is not deferred are left alone.  Of the confidence the
-        sums are logged, not the map."""
+               confidence: bool = False, parts: bool = False) -> int:
+        """report="deferred", masks="deferred", confidence="deferred" and / or parts="deferred": a clip's row in the log -> its index
+        (tracked = False: ids and started are written when it is tracked); the columns of what is not deferred are left alone.  Of the
+        confidence the sums are logged, not the map."""
         values = dict(moments=self.moments, rows=self.rows, total=self.total, ids=self.ids if tracked else None,
                       started=self.started if tracked else None) if report else {}
         if masks:
             values.update(runs=self.runs, count=self.count)
         if confidence:
             values.update(class_sums=self.class_sums, instance_sums=self.instance_sums)
+        if parts:
+            values.update(parts=self.parts, contacts=self.contacts)
         return log.append(frame, **values)
 
 
@@ -133,14 +139,24 @@ class ReportChain:
     """report / instances / tracks / masks / confidence of a VideoSegmenter: hip.label_moments, then the launches of
     hip.label_components, then those of hip.track_instances, then those of hip.rle_encode (on the component map with instances, else on
     the labels), then hip.upsample_confidence on the logits the labels came from and hip.confidence_sums over the labels (and over
-    the component map with instances), on every label map the segmenter makes.  The segmenter calls labelled() where a step's labels exist and
+    the component map with instances), then hip.instance_parts over the labels and the component map, on every label map the segmenter
+    makes.  With instance_groups the component launches read the grouped labels, which hip.gt_decode makes of the labels with the
+    persistent table of utils.instruments.group_table; everything else reads the labels themselves.  The segmenter calls labelled() where a step's labels exist and
     released() where its frames are handed out (step_is_steady() is the check in front of the graph's steady step, which tracks inside
-    itself).  Owns what persists across steps: the component map and the workspaces (they only grow; the ones they replaced are kept, a
+    itself).  Owns what persists across steps: the component map, the grouped labels and the workspaces (they only grow; the ones they replaced are kept, a
     captured step may still use them), the tracker's state, the parked frames, the pool of their map copies, and the deferred log."""
 
     def __init__(self, device, classes: int, protocol: str, out: str, report, min_area, instances, connectivity, instance_skip, tracks,
                  track_iou, track_same_class, masks=None, mask_runs=16384, track_max_gap=0, confidence=None, confidence_low=128,
-                 align_corners=True):
+                 align_corners=True, parts=None, instance_groups=None):
+        if parts not in (None, "frame", "deferred"):
+            raise StswinHipError(f"parts must be None, 'frame' or 'deferred', got {parts!r}")
+        if parts is not None and out == "logits":
+            raise StswinHipError("parts belongs to out='labels' and out='overlay' (the parts are taken over the label map)")
+        if parts is not None and instances is None:
+            raise StswinHipError("parts says what the instances are made of and what they touch: it needs instances=K")
+        if instance_groups is not None and instances is None:
+            raise StswinHipError("instance_groups belongs to instances=K")
         if report not in (None, "frame", "deferred"):
             raise StswinHipError(f"report must be None, 'frame' or 'deferred', got {report!r}")
         if report is not None and out == "logits":
@@ -164,6 +180,12 @@ class ReportChain:
             instance_skip = tuple(instance_skip)
             if any(isinstance(c, bool) or not isinstance(c, int) or not 0 <= c <= 63 for c in instance_skip):
                 raise StswinHipError(f"instance_skip holds classes 0 .. 63, got {instance_skip!r}")
+            if instance_groups is not None:
+                from .utils.instruments import check_groups
+                try:
+                    instance_groups = check_groups(instance_groups, classes, instance_skip)
+                except ValueError as e:
+                    raise StswinHipError(str(e)) from e
         if not isinstance(tracks, bool):
             raise StswinHipError(f"tracks must be a bool, got {tracks!r}")
         if not tracks and (track_iou != 100 or track_same_class is not True):
@@ -199,6 +221,11 @@ class ReportChain:
             raise StswinHipError(f"confidence: the model has {classes} classes, hip.upsample_confidence takes 1 .. 64")
         self.device, self.classes, self.report, self.min_area = device, classes, report, min_area
         self.confidence, self.confidence_low, self.align_corners = confidence, confidence_low, bool(align_corners)
+        self.parts, self.instance_groups = parts, instance_groups
+        self.group_table = self.grouped = None        # instance_groups: the class -> representative table (persistent: a captured graph
+        if instance_groups is not None:               # reads it) and the grouped labels, a buffer that only grows, as cc_map does
+            from .utils.instruments import group_table
+            self.group_table = torch.from_numpy(group_table(instance_groups, classes)).to(device)
         self.masks, self.mask_runs = masks, mask_runs
         self.rle_ws = None                    # masks: the encoder's workspace (retired ones go where the component map's do)
         self.instances, self.connectivity, self.instance_skip = instances, connectivity, instance_skip
@@ -217,7 +244,9 @@ class ReportChain:
                              dict(moments=((classes, 10), torch.int64)) if logged else {},
                              dict(runs=((mask_runs, 2), torch.int32), count=((), torch.int32)) if masks == "deferred" else {},
                              dict(class_sums=((classes, 3), torch.int64)) if confidence == "deferred" else {},
-                             dict(instance_sums=((instances, 3), torch.int64)) if confidence == "deferred" and instances is not None else {})
+                             dict(instance_sums=((instances, 3), torch.int64)) if confidence == "deferred" and instances is not None else {},
+                             dict(parts=((instances, classes, 10), torch.int64), contacts=((instances, classes), torch.int64))
+                             if parts == "deferred" else {})
 
     def reset(self) -> None:
         """The sequence ends: its ordinal in the log, ids restart at 0 (a fill kernel on the stream), what is parked is dropped."""
@@ -236,7 +265,8 @@ class ReportChain:
         until the next clip's labels) or in the graph's steady step (`steady`: one frame, in frame order); released() tracks the rest.
         The encoder's launches come last: they need nothing from the tracker, so a frame that is parked is encoded here, before the
         next clip's components overwrite the map.  So do the confidence launches, on the `logits` [B][nc][h][w] the labels were made
-        from: the map, its sums over the labels and, with instances, over the component map."""
+        from: the map, its sums over the labels and, with instances, over the component map.  And so does the parts launch, on the
+        labels (ungrouped) and the component map."""
         if self.report is None and self.masks is None and self.confidence is None:
             return None
         moments = rows = total = ids = started = None
@@ -265,22 +295,27 @@ class ReportChain:
                 inst = hip.confidence_sums(self.cc_map[:B * H * W].view(B, H, W), conf, self.instances, self.confidence_low)
             ys = [c._replace(conf=conf[b:b + 1], class_sums=sums[b:b + 1], instance_sums=None if inst is None else inst[b:b + 1])
                   for b, c in enumerate(ys)]
+        if self.parts is not None:
+            B, H, W = labels.shape
+            pt, ct = hip.instance_parts(labels, self.cc_map[:B * H * W].view(B, H, W), self.instances, self.classes)
+            ys = [c._replace(parts=pt[b:b + 1], contacts=ct[b:b + 1]) for b, c in enumerate(ys)]
         return ys
 
     def released(self, frames: Sequence[int], results: list, ys: Optional[List[Yield]]) -> list:
         """The clips of `frames` are released with `results` and what their labels yielded: clips not tracked yet are, in the step's
-        order; then report="frame", masks="frame" and confidence="frame" append to each result (on the device), and a row is logged
-        when any of them is "deferred".  -> the results."""
+        order; then report="frame", masks="frame", confidence="frame" and parts="frame" append to each result (on the device), and a
+        row is logged when any of them is "deferred".  -> the results."""
         if self.report is None and self.masks is None and self.confidence is None:
             return results
         if self.tracks:
             ys = [y if y.ids is not None else self._track(g, b, y) for b, (g, y) in enumerate(zip(frames, ys))]
-        if "frame" in (self.report, self.masks, self.confidence):
-            results = [y.appended(r, self.report == "frame", self.masks == "frame", self.confidence == "frame") for r, y in zip(results, ys)]
-        if "deferred" in (self.report, self.masks, self.confidence):
+        if "frame" in (self.report, self.masks, self.confidence, self.parts):
+            results = [y.appended(r, self.report == "frame", self.masks == "frame", self.confidence == "frame", self.parts == "frame")
+                       for r, y in zip(results, ys)]
+        if "deferred" in (self.report, self.masks, self.confidence, self.parts):
             for g, y in zip(frames, ys):
                 row = y.logged(self.log, g, g not in self.parked, self.report == "deferred", self.masks == "deferred",
-                               self.confidence == "deferred")
+                               self.confidence == "deferred", self.parts == "deferred")
                 if g in self.parked and self.report == "deferred":
                     self.parked[g].log_row = row
         return results
@@ -296,9 +331,16 @@ class ReportChain:
         return self.cc_map[b * hw:(b + 1) * hw].view(self.hw)
 
     def _components(self, labels: torch.Tensor):
-        """(rows int64 [B][K][12], total int32 [B]) of labels [B][H][W].  The component map and the workspace only ever grow, so the
-        warm-up frames allocate what the captured step then uses; rows and total are fresh per step (under capture: the graph's)."""
+        """(rows int64 [B][K][12], total int32 [B]) of labels [B][H][W]; with instance_groups of the grouped labels, group_table[labels],
+        made by one launch in front (hip.gt_decode, id-coded).  The component map, the grouped labels and the workspace only ever grow,
+        so the warm-up frames allocate what the captured step then uses; rows and total are fresh per step (under capture: the graph's)."""
         B, H, W = labels.shape
+        if self.group_table is not None:
+            if self.grouped is None or self.grouped.numel() < B * H * W:
+                if self.grouped is not None:
+                    self.cc_retired.append(self.grouped)
+                self.grouped = torch.empty(B * H * W, dtype=torch.uint8, device=self.device)
+            labels = hip.gt_decode(labels, self.group_table, torch.uint8, out=self.grouped[:B * H * W].view(B, H, W))
         need = hip.label_components_scratch(B, H, W)
         if self.cc_ws is None or self.cc_ws.numel() < need or self.cc_map.numel() < B * H * W:
             self.cc_retired += [t for t in (self.cc_ws, self.cc_map) if t is not None]
