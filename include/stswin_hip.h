@@ -812,6 +812,48 @@ int stswin_instance_parts(const unsigned char* labels /*[n][H][W]*/, const int* 
 /* the geometry of stswin_instance_parts (the tests place their shapes around it): which = 0: the tile's height (32), 1: its width
  * (128), 2: the slots of the on-chip table (64); anything else: -1. */
 int stswin_instance_parts_geometry(int which);
+/* ---- the label map cleaned: specks out, small holes filled (stswincl_amd/utils/instruments.py clean_labels states the result bit
+ * for bit; VideoSegmenter(clean_area=A)).  labels uint8 [n][H][W] -> out uint8 [n][H][W], stats int32 [n][2].
+ *   The components of every class c < nc, nothing skipped, under `connectivity` 4 or 8, are those of stswin_label_components; pixels
+ *   with a label >= nc belong to none, are never changed and never vote.  A component is small if its area is < min_area and its class
+ *   is not in `keep` (bit c of the mask: class c is kept); every other pixel of a class < nc is stable.  A frame's small components are
+ *   numbered s = 0, 1, ... by their first pixel in raster order; only those with s < max_small can be relabelled, the rest stay as they
+ *   are whatever the order of execution, but still count as small.  votes[s][c] = the number of ordered pairs (p, q), p a pixel of
+ *   small component s, q one of p's four neighbours inside the frame, stable, with labels[q] == c (always the input labels: one pass).
+ *   The new label of s is the smallest c with the largest votes[s][c] if that is > 0, else its own.
+ *   stats[f] = (the frame's number of small components, not bounded by max_small; the number of pixels whose label changed).
+ * out and stats are written in full; nothing in the workspace needs clearing by the caller (what is accumulated is cleared by fill
+ * kernels on the stream, no memset node).  No allocation, no synchronisation (graph-capturable); no kernel waits on another workgroup;
+ * integer atomics only (exact, independent of the order: bit-reproducible).  workspace: caller-owned, 4-byte aligned, >=
+ * stswin_labels_clean_scratch(n, H, W, nc, max_small) bytes (two int32 maps, the chunk counts, and per frame max_small (2 + nc) words).
+ * Twelve launches: two fills (the areas, the votes); the tile, border (more than one tile only) and root pass of
+ * stswin_label_components with an empty skip mask, after which the parent map holds every pixel's root; areas by root, a thread
+ * folding the runs along 16 pixels of a row and a workgroup gathering its tile's runs on chip before the atomics; the count of small roots per raster chunk, its scan and the numbering
+ * (which also writes stats); the vote pass, in which only pixels of small components with s < max_small do any work, a workgroup
+ * gathering the votes of its tile of stswin_labels_clean_geometry(0) x (1) pixels in a keyed on-chip table of (3) slots and adding
+ * directly where a key finds no slot; the resolve pass, a thread per small component; the relabel pass.  Any pointer alignment, any W:
+ * labels, out and workspace 16-byte aligned with W % 16 == 0 takes the bodies with 16-byte loads and stores, anything else the element
+ * bodies.  1 <= H, W <= 16384.  out must not overlap labels (the host wrapper checks).
+ * Errors, before anything is launched: -1900 n, H or W <= 0, or H or W > 16384, or more workgroups than a grid holds
+ * (stswin_labels_clean_scratch returns the same for such a shape); -1901 labels, out, stats or workspace NULL; -1902 nc outside 1 ..
+ * 64; -1903 connectivity not 4 or 8; -1904 min_area outside 2 .. 2^30; -1905 max_small outside 1 .. 65536; -1906 workspace too small
+ * or not 4-byte aligned (or stats not 4-byte aligned). */
+long stswin_labels_clean_scratch(int n, int H, int W, int nc, int max_small);
+int stswin_labels_clean(const unsigned char* labels /*[n][H][W]*/, unsigned char* out /*[n][H][W]*/, int* stats /*[n][2]*/, int n, int H,
+                        int W, int nc, int connectivity, long keep, int min_area, int max_small, void* workspace, long workspace_bytes,
+                        void* stream);
+/* the geometry of stswin_labels_clean (the tests place their shapes around it): which = 0: the vote tile's height (32), 1: its width
+ * (128), 2: the pixels of a raster chunk of the numbering pass (2048), 3: the slots of the on-chip vote table (256); anything else: -1. */
+int stswin_labels_clean_geometry(int which);
+/* what the fused label launches count, from a label map that already exists (a cleaned one): labels uint8 [n][H][W], gt int64
+ * [n][H][W].  With counts (int32 [n][3][nc], zeroed by the caller): counts[f][0 | 1 | 2][c] += |gt == c|, |labels == c|, |gt == c and
+ * labels == c|, the integers of stswin_upsample_argmax.  With cm (int64 [ncm][ncm]): every pixel with 0 <= gt < ncm and labels < ncm
+ * adds 1 to cm[gt][labels]; accumulated, never cleared, as stswin_upsample_argmax_cm does.  Either or both.  One launch: LDS bins per
+ * workgroup, one atomic per non-zero bin; integer adds only.  gt 8-byte aligned, labels at any address.
+ * Errors: -1910 n, H or W <= 0, or H or W > 16384; -1911 labels or gt NULL, or counts and cm both NULL; -1912 nc outside 1 .. 64, or
+ * (with cm) ncm outside 1 .. 64; -1913 gt or cm not 8-byte aligned, or counts not 4-byte aligned. */
+int stswin_labels_score(const unsigned char* labels /*[n][H][W]*/, const long long* gt /*[n][H][W]*/, int* counts /*[n][3][nc] or NULL*/,
+                        unsigned long long* cm /*[ncm][ncm] or NULL*/, int ncm, int n, int H, int W, int nc, void* stream);
 /* ---- frames as a video source delivers them (stswincl_amd/utils/yuv.py, VideoSegmenter(pixel_format=..., out_format="nv12")):
  * stswin_yuv_to_rgb makes the HWC RGB frame uint8 [n][Hs][Ws][3] that stswin_frame_ingest and stswin_labels_overlay read,
  * stswin_rgb_to_nv12 turns such a frame into NV12.  Hs (NV12) and Ws are even.

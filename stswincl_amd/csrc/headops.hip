@@ -2527,6 +2527,457 @@ extern "C" int stswin_label_components(const unsigned char* labels, int* compone
   return 0;
 }
 
+// The label map cleaned: specks out, holes filled (stswincl_amd/utils/instruments.py, clean_labels, states the result;
+// VideoSegmenter(clean_area=A)).  The components are those of the union-find above with nothing skipped; a component of fewer than
+// min_area pixels whose class is not kept is small, and takes the class most of its pixel edges towards stable pixels lead to.  The
+// workspace, in int32 words: the parent map [n][H W], aux [n][H W] (at a root: first the component's area, then -1 for a stable
+// component and the ordinal s among the frame's small ones otherwise), the chunk counts, the frames' totals [n], info [n][max_small][2]
+// (root, then area, then the new label) and votes [n][max_small][nc].  Launches:
+//   1, 2 fill kernels          aux and votes to zero
+//   3, 4 cc_tile_kernel, cc_border_kernel (the latter only with more than one tile), 5 cc_count_kernel: every pixel's parent is its root
+//   6 cl_area_kernel           a thread folds the runs of equal roots along its CL_PPT pixels of a row and adds each run to the keyed LDS
+//                              table of its tile (as launch 10 does), which ends as one global atomic per root the tile meets
+//   7 cl_count_kernel          a workgroup counts the small roots of its raster chunk of CC_CHUNK pixels;  8 cc_scan_kernel as above
+//   9 cl_number_kernel         a small root's s = its chunk's offset + its rank in the chunk (raster order: truncation keeps the first
+//                              max_small); aux = s and info = (root, area) for s < max_small, aux = -1 at a stable root; stats
+//  10 cl_vote_kernel           a workgroup takes a tile of CL_TH x CL_TW pixels; only the pixels of small components with s < max_small
+//                              do any work: each looks at its four neighbours' roots and adds a vote for a stable one's class to the
+//                              workgroup's keyed LDS table (CL_SLOTS slots, multiplicative hash, CL_PROBES probes), whose slots in use
+//                              end as one global atomic each; a key that finds no slot adds to votes directly, with the same result
+//  11 cl_resolve_kernel        a thread per small component: the first maximum; the area into stats where the label changes
+//  12 cl_relabel_kernel        out = the new label for the pixels of small components with s < max_small, the label elsewhere
+// Integer atomics only: exact and independent of the order.  No kernel waits on another workgroup or uses scratch memory.  WIDE:
+// labels, out and the workspace 16-byte aligned and W % 16 == 0, 16-byte loads and stores; else element by element.
+#define CL_TH 32
+#define CL_TW 128
+#define CL_PPT 16
+#define CL_CPR (CL_TW / CL_PPT)
+#define CL_THREADS (CL_TH * CL_CPR)
+#define CL_SLOTS 256
+#define CL_PROBES 8
+static_assert(CL_SLOTS == 256, "cl_vote takes the hash's top 8 bits");
+
+// the thread's pixels: row y, columns x0 .. x0 + len - 1 of frame f (len 0: none)
+struct ClSpan {
+  int f, y, x0, len;
+};
+
+__device__ __forceinline__ ClSpan cl_span(int H, int W, int tiles_x, int tiles_per_frame) {
+  ClSpan s;
+  s.f = (int)(blockIdx.x / (unsigned)tiles_per_frame);
+  const int t = (int)(blockIdx.x % (unsigned)tiles_per_frame);
+  const int ty = t / tiles_x, tx = t - ty * tiles_x;
+  const int r = (int)threadIdx.x / CL_CPR, ch = (int)threadIdx.x - r * CL_CPR;
+  s.y = ty * CL_TH + r;
+  s.x0 = tx * CL_TW + ch * CL_PPT;
+  s.len = s.y < H ? max(0, min(CL_PPT, W - s.x0)) : 0;
+  return s;
+}
+
+template <bool WIDE>
+__device__ __forceinline__ void cl_roots(const int* __restrict__ par, int len, int (&r)[CL_PPT]) {      // -1 past the end
+  if (WIDE) {
+    const int4* p = reinterpret_cast<const int4*>(par);
+#pragma unroll
+    for (int q = 0; q < CL_PPT / 4; ++q) {
+      const int4 v = p[q];
+      r[4 * q] = v.x;
+      r[4 * q + 1] = v.y;
+      r[4 * q + 2] = v.z;
+      r[4 * q + 3] = v.w;
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < CL_PPT; ++k) r[k] = k < len ? par[k] : -1;
+  }
+}
+
+// The workgroup's keyed table of CL_SLOTS counters in LDS: `word` (non-zero) finds its slot by a multiplicative hash and up to CL_PROBES
+// linear probes, claiming a free one by compare-and-swap, and adds v there -> true; false when none of its probe slots is free or its
+// own (always so once the table is full): the caller then adds to global memory directly, the same integers either way.
+__device__ __forceinline__ bool cl_table_add(unsigned* key, unsigned* cnt, unsigned word, unsigned v) {
+  const unsigned h = (word * 2654435761u) >> 24;
+  for (int t = 0; t < CL_PROBES; ++t) {
+    const unsigned i = (h + t) & (CL_SLOTS - 1);
+    const unsigned old = atomicCAS(&key[i], 0u, word);
+    if (old == 0u || old == word) {
+      atomicAdd(&cnt[i], v);
+      return true;
+    }
+  }
+  return false;
+}
+
+// (a large component - the background - covers whole tiles: its runs meet in one LDS counter and leave as one global atomic per tile;
+// added run by run to the one word at its root they would queue up behind each other across the whole device)
+template <bool WIDE>
+__global__ __launch_bounds__(CL_THREADS) void cl_area_kernel(const int* __restrict__ parent, int* aux, int H, int W, int tiles_x,
+                                                             int tiles_per_frame) {
+  __shared__ unsigned key[CL_SLOTS], cnt[CL_SLOTS];
+  for (int i = threadIdx.x; i < CL_SLOTS; i += CL_THREADS) {
+    key[i] = 0u;
+    cnt[i] = 0u;
+  }
+  __syncthreads();
+  const ClSpan s = cl_span(H, W, tiles_x, tiles_per_frame);
+  int* ax = aux + (long)s.f * H * W;
+  if (s.len > 0) {
+    int r[CL_PPT];
+    cl_roots<WIDE>(parent + (long)s.f * H * W + (long)s.y * W + s.x0, s.len, r);
+    int cur = -1;
+    unsigned c = 0;
+#pragma unroll
+    for (int k = 0; k <= CL_PPT; ++k) {
+      const int rk = k < CL_PPT ? r[k < CL_PPT ? k : 0] : -1;
+      if (rk != cur) {
+        if (cur >= 0 && !cl_table_add(key, cnt, (unsigned)cur + 1u, c)) atomicAdd(ax + cur, (int)c);
+        cur = rk;
+        c = 0;
+      }
+      c += 1;
+    }
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < CL_SLOTS; i += CL_THREADS)
+    if (key[i]) atomicAdd(ax + (key[i] - 1u), (int)cnt[i]);
+}
+
+// bit i: pixel base + i is the root of a small component (aux still holds the areas)
+__device__ __forceinline__ unsigned cl_small_roots(const unsigned char* __restrict__ lab, const int* __restrict__ par,
+                                                   const int* __restrict__ aux, int base, int HW, int min_area, unsigned long long keep,
+                                                   unsigned* roots) {
+  unsigned small = 0, all = 0;
+#pragma unroll
+  for (int i = 0; i < CC_PPT; ++i) {
+    const int p = base + i;
+    if (p < HW && par[p] == p) {
+      all |= 1u << i;
+      if (aux[p] < min_area && !((keep >> (lab[p] & 63u)) & 1ull)) small |= 1u << i;
+    }
+  }
+  *roots = all;
+  return small;
+}
+
+__global__ __launch_bounds__(CC_THREADS) void cl_count_kernel(const unsigned char* __restrict__ labels, const int* __restrict__ parent,
+                                                              const int* __restrict__ aux, int* __restrict__ counts, int HW, int chunks,
+                                                              int min_area, unsigned long long keep) {
+  __shared__ unsigned red[4];
+  const int ch = (int)(blockIdx.x % (unsigned)chunks), f = (int)(blockIdx.x / (unsigned)chunks);
+  const long fo = (long)f * HW;
+  unsigned roots;
+  const unsigned small = cl_small_roots(labels + fo, parent + fo, aux + fo, ch * CC_CHUNK + (int)threadIdx.x * CC_PPT, HW, min_area, keep, &roots);
+  const unsigned c = cc_block_sum((unsigned)__builtin_popcount(small), red);
+  if (threadIdx.x == 0) counts[(long)f * chunks + ch] = (int)c;
+}
+
+__global__ __launch_bounds__(CC_THREADS) void cl_number_kernel(const unsigned char* __restrict__ labels, const int* __restrict__ parent,
+                                                               int* aux, const int* __restrict__ offsets, const int* __restrict__ total,
+                                                               int* __restrict__ info, int* __restrict__ stats, int HW, int chunks,
+                                                               int min_area, unsigned long long keep, int max_small) {
+  __shared__ unsigned red[4];
+  const int ch = (int)(blockIdx.x % (unsigned)chunks), f = (int)(blockIdx.x / (unsigned)chunks);
+  const long fo = (long)f * HW;
+  const int base = ch * CC_CHUNK + (int)threadIdx.x * CC_PPT;
+  unsigned roots;
+  const unsigned small = cl_small_roots(labels + fo, parent + fo, aux + fo, base, HW, min_area, keep, &roots);
+  const unsigned mine = (unsigned)__builtin_popcount(small);
+  unsigned o = (unsigned)offsets[(long)f * chunks + ch] + cc_block_scan(mine, red) - mine;
+#pragma unroll
+  for (int i = 0; i < CC_PPT; ++i) {
+    if (!(roots & (1u << i))) continue;
+    int* a = aux + fo + base + i;
+    if (small & (1u << i)) {
+      if (o < (unsigned)max_small) {
+        int* e = info + ((long)f * max_small + o) * 2;
+        e[0] = base + i;
+        e[1] = *a;
+      }
+      *a = (int)o;
+      ++o;
+    } else {
+      *a = -1;
+    }
+  }
+  if (ch == 0 && threadIdx.x == 0) {
+    stats[2 * f] = total[f];
+    stats[2 * f + 1] = 0;
+  }
+}
+
+__device__ __forceinline__ void cl_vote(unsigned* key, unsigned* cnt, int* votes_f, int nc, int s, unsigned c) {
+  const unsigned word = ((unsigned)s << 6 | c) + 1u;                  // s < 65536, c < 64; 0: a free slot
+  if (!cl_table_add(key, cnt, word, 1u)) atomicAdd(votes_f + (long)s * nc + c, 1);
+}
+
+template <bool WIDE>
+__global__ __launch_bounds__(CL_THREADS) void cl_vote_kernel(const unsigned char* __restrict__ labels, const int* __restrict__ parent,
+                                                             const int* __restrict__ aux, int* votes, int H, int W, int nc, int max_small,
+                                                             int tiles_x, int tiles_per_frame) {
+  __shared__ unsigned key[CL_SLOTS], cnt[CL_SLOTS];
+  for (int i = threadIdx.x; i < CL_SLOTS; i += CL_THREADS) {
+    key[i] = 0u;
+    cnt[i] = 0u;
+  }
+  __syncthreads();
+  const ClSpan s = cl_span(H, W, tiles_x, tiles_per_frame);
+  const long fo = (long)s.f * H * W;
+  const unsigned char* lab = labels + fo;
+  const int* par = parent + fo;
+  const int* ax = aux + fo;
+  int* votes_f = votes + (long)s.f * max_small * nc;
+  if (s.len > 0) {
+    const int p0 = s.y * W + s.x0;
+    int r[CL_PPT];
+    cl_roots<WIDE>(par + p0, s.len, r);
+    unsigned todo = 0;                                   // the thread's pixels of small components with s < max_small
+    int cur = -1;
+    bool live = false;
+#pragma unroll
+    for (int k = 0; k < CL_PPT; ++k) {
+      if (r[k] != cur) {
+        cur = r[k];
+        live = cur >= 0 && (unsigned)ax[cur] < (unsigned)max_small;
+      }
+      if (live) todo |= 1u << k;
+    }
+    while (todo) {                                       // (rare: the roots are read again rather than indexed out of registers)
+      const int k = __builtin_ctz(todo);
+      todo &= todo - 1u;
+      const int x = s.x0 + k, p = p0 + k;
+      const int sm = ax[par[p]];
+#pragma unroll
+      for (int d = 0; d < 4; ++d) {
+        const int qy = s.y + (d == 0 ? -1 : d == 1 ? 1 : 0), qx = x + (d == 2 ? -1 : d == 3 ? 1 : 0);
+        if (qy < 0 || qy >= H || qx < 0 || qx >= W) continue;
+        const int q = qy * W + qx, rq = par[q];
+        if (rq >= 0 && ax[rq] == -1) cl_vote(key, cnt, votes_f, nc, sm, (unsigned)lab[q]);
+      }
+    }
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < CL_SLOTS; i += CL_THREADS) {
+    const unsigned word = key[i];
+    if (word) atomicAdd(votes_f + (long)((word - 1u) >> 6) * nc + ((word - 1u) & 63u), (int)cnt[i]);
+  }
+}
+
+__global__ __launch_bounds__(CC_THREADS) void cl_resolve_kernel(const unsigned char* __restrict__ labels, const int* __restrict__ votes,
+                                                                int* info, int* stats, int HW, int nc, int max_small,
+                                                                int blocks_per_frame) {
+  const int f = (int)(blockIdx.x / (unsigned)blocks_per_frame);
+  const int s = (int)(blockIdx.x % (unsigned)blocks_per_frame) * CC_THREADS + (int)threadIdx.x;
+  if (s >= max_small || s >= stats[2 * f]) return;       // (stats[2 f]: written by cl_number_kernel, only read here)
+  int* e = info + ((long)f * max_small + s) * 2;
+  const int old = (int)labels[(long)f * HW + e[0]], area = e[1];
+  const int* v = votes + ((long)f * max_small + s) * nc;
+  int best = 0, arg = old;
+  for (int c = 0; c < nc; ++c) {
+    const int t = v[c];
+    if (t > best) best = t, arg = c;
+  }
+  e[1] = arg;
+  if (arg != old) atomicAdd(stats + 2 * f + 1, area);
+}
+
+template <bool WIDE>
+__global__ __launch_bounds__(CL_THREADS) void cl_relabel_kernel(const unsigned char* __restrict__ labels, const int* __restrict__ parent,
+                                                                const int* __restrict__ aux, const int* __restrict__ info,
+                                                                unsigned char* __restrict__ out, int H, int W, int max_small, int tiles_x,
+                                                                int tiles_per_frame) {
+  const ClSpan s = cl_span(H, W, tiles_x, tiles_per_frame);
+  if (s.len == 0) return;
+  const long fo = (long)s.f * H * W, at = fo + (long)s.y * W + s.x0;
+  const int* ax = aux + fo;
+  const int* inf = info + (long)s.f * max_small * 2;
+  int r[CL_PPT];
+  cl_roots<WIDE>(parent + at, s.len, r);
+  uint4 lw = make_uint4(0u, 0u, 0u, 0u);
+  if (WIDE) lw = *reinterpret_cast<const uint4*>(labels + at);
+  unsigned o[CL_PPT / 4] = {0u, 0u, 0u, 0u};
+  int cur = -1, repl = -1;                               // repl: the new label of the run's component, -1: the pixel keeps its own
+#pragma unroll
+  for (int k = 0; k < CL_PPT; ++k) {
+    if (r[k] != cur) {
+      cur = r[k];
+      repl = -1;
+      if (cur >= 0) {
+        const int sm = ax[cur];
+        if ((unsigned)sm < (unsigned)max_small) repl = inf[2 * sm + 1];
+      }
+    }
+    if (WIDE) {
+      const unsigned v = repl >= 0 ? (unsigned)repl : lm_byte(lw, k);
+      o[k >> 2] |= v << (8 * (k & 3));
+    } else if (k < s.len) {
+      out[at + k] = repl >= 0 ? (unsigned char)repl : labels[at + k];
+    }
+  }
+  if (WIDE) *reinterpret_cast<uint4*>(out + at) = make_uint4(o[0], o[1], o[2], o[3]);
+}
+
+extern "C" int stswin_labels_clean_geometry(int which) {
+  return which == 0 ? CL_TH : which == 1 ? CL_TW : which == 2 ? CC_CHUNK : which == 3 ? CL_SLOTS : -1;
+}
+
+struct ClLayout {
+  long parent, aux, counts, total, info, votes, words;   // offsets in int32 words
+  int chunks, tiles_x;
+  long tpf, cc_tiles, border_items, resolve_bpf;
+};
+
+static bool cl_layout(int n, int H, int W, int nc, int max_small, ClLayout* L) {
+  if (n <= 0 || H <= 0 || W <= 0 || H > 16384 || W > 16384) return false;
+  const long HW = (long)H * W;
+  L->chunks = (int)((HW + CC_CHUNK - 1) / CC_CHUNK);
+  L->tiles_x = (W + CL_TW - 1) / CL_TW;
+  L->tpf = (long)L->tiles_x * ((H + CL_TH - 1) / CL_TH);
+  L->cc_tiles = (long)((W + CC_TW - 1) / CC_TW) * ((H + CC_TH - 1) / CC_TH);
+  L->border_items = (long)((H + CC_TH - 1) / CC_TH - 1) * W + (long)((W + CC_TW - 1) / CC_TW - 1) * H;
+  L->resolve_bpf = ((long)max_small + CC_THREADS - 1) / CC_THREADS;
+  if (L->tpf * n > 0x7fffffffL || L->cc_tiles * n > 0x7fffffffL || (long)L->chunks * n > 0x7fffffffL ||
+      (L->border_items * n + CC_THREADS - 1) / CC_THREADS > 0x7fffffffL || L->resolve_bpf * n > 0x7fffffffL)
+    return false;
+  L->parent = 0;
+  L->aux = (long)n * HW;
+  L->counts = 2 * (long)n * HW;
+  L->total = L->counts + (long)n * L->chunks;
+  L->info = L->total + n;
+  L->votes = L->info + 2 * (long)n * max_small;
+  L->words = L->votes + (long)n * max_small * nc;
+  return true;
+}
+
+extern "C" long stswin_labels_clean_scratch(int n, int H, int W, int nc, int max_small) {
+  ClLayout L;
+  if (nc < 1 || nc > 64) return -1902;
+  if (max_small < 1 || max_small > 65536) return -1905;
+  if (!cl_layout(n, H, W, nc, max_small, &L)) return -1900;
+  return 4 * L.words;
+}
+
+extern "C" int stswin_labels_clean(const unsigned char* labels, unsigned char* out, int* stats, int n, int H, int W, int nc, int connectivity,
+                                   long keep, int min_area, int max_small, void* workspace, long workspace_bytes, void* stream) {
+  ClLayout L;
+  if (!cl_layout(n, H, W, nc < 1 || nc > 64 ? 1 : nc, max_small < 1 || max_small > 65536 ? 1 : max_small, &L)) return -1900;
+  if (labels == nullptr || out == nullptr || stats == nullptr || workspace == nullptr) return -1901;
+  if (nc < 1 || nc > 64) return -1902;
+  if (connectivity != 4 && connectivity != 8) return -1903;
+  if (min_area < 2 || min_area > (1 << 30)) return -1904;
+  if (max_small < 1 || max_small > 65536) return -1905;
+  if (workspace_bytes < 4 * L.words || ((uintptr_t)workspace & 3) || ((uintptr_t)stats & 3)) return -1906;
+  const int HW = H * W, chunks = L.chunks;
+  int* ws = reinterpret_cast<int*>(workspace);
+  int* parent = ws + L.parent;
+  int* aux = ws + L.aux;
+  int* counts = ws + L.counts;
+  int* total = ws + L.total;
+  int* info = ws + L.info;
+  int* votes = ws + L.votes;
+  hipStream_t st = (hipStream_t)stream;
+  const int conn8 = connectivity == 8;
+  const unsigned long long kp = (unsigned long long)keep;
+  const int cc_tx = (W + CC_TW - 1) / CC_TW, cc_ty = (H + CC_TH - 1) / CC_TH;
+  const long rows_items = (long)(cc_ty - 1) * W, per_frame = L.border_items;
+  const bool wide = (((uintptr_t)labels | (uintptr_t)out | (uintptr_t)workspace) & 15) == 0 && W % CL_PPT == 0;
+  const dim3 tiles((unsigned)(L.tpf * n)), per_chunk((unsigned)(chunks * n));
+  stswin_zero_bytes(aux, sizeof(int) * (size_t)n * (size_t)HW, st);                     // (kernels, not hipMemsetAsync: see common.h)
+  stswin_zero_bytes(votes, sizeof(int) * (size_t)n * (size_t)max_small * (size_t)nc, st);
+  hipLaunchKernelGGL(cc_tile_kernel, dim3((unsigned)(L.cc_tiles * n)), dim3(CC_THREADS), 0, st, labels, parent, H, W, nc, 0ull, conn8, cc_tx, cc_ty);
+  if (per_frame > 0)
+    hipLaunchKernelGGL(cc_border_kernel, dim3((unsigned)((per_frame * n + CC_THREADS - 1) / CC_THREADS)), dim3(CC_THREADS), 0, st, labels, parent, H,
+                       W, nc, 0ull, conn8, rows_items, per_frame, per_frame * n);
+  hipLaunchKernelGGL(cc_count_kernel, per_chunk, dim3(CC_THREADS), 0, st, parent, counts, HW, chunks);
+  if (wide) hipLaunchKernelGGL(cl_area_kernel<true>, tiles, dim3(CL_THREADS), 0, st, (const int*)parent, aux, H, W, L.tiles_x, (int)L.tpf);
+  else hipLaunchKernelGGL(cl_area_kernel<false>, tiles, dim3(CL_THREADS), 0, st, (const int*)parent, aux, H, W, L.tiles_x, (int)L.tpf);
+  hipLaunchKernelGGL(cl_count_kernel, per_chunk, dim3(CC_THREADS), 0, st, labels, (const int*)parent, (const int*)aux, counts, HW, chunks, min_area,
+                     kp);
+  hipLaunchKernelGGL(cc_scan_kernel, dim3((unsigned)n), dim3(CC_THREADS), 0, st, counts, total, chunks);
+  hipLaunchKernelGGL(cl_number_kernel, per_chunk, dim3(CC_THREADS), 0, st, labels, (const int*)parent, aux, (const int*)counts, (const int*)total,
+                     info, stats, HW, chunks, min_area, kp, max_small);
+  if (wide)
+    hipLaunchKernelGGL(cl_vote_kernel<true>, tiles, dim3(CL_THREADS), 0, st, labels, (const int*)parent, (const int*)aux, votes, H, W, nc, max_small,
+                       L.tiles_x, (int)L.tpf);
+  else
+    hipLaunchKernelGGL(cl_vote_kernel<false>, tiles, dim3(CL_THREADS), 0, st, labels, (const int*)parent, (const int*)aux, votes, H, W, nc, max_small,
+                       L.tiles_x, (int)L.tpf);
+  hipLaunchKernelGGL(cl_resolve_kernel, dim3((unsigned)(L.resolve_bpf * n)), dim3(CC_THREADS), 0, st, labels, (const int*)votes, info, stats, HW, nc,
+                     max_small, (int)L.resolve_bpf);
+  if (wide)
+    hipLaunchKernelGGL(cl_relabel_kernel<true>, tiles, dim3(CL_THREADS), 0, st, labels, (const int*)parent, (const int*)aux, (const int*)info, out, H,
+                       W, max_small, L.tiles_x, (int)L.tpf);
+  else
+    hipLaunchKernelGGL(cl_relabel_kernel<false>, tiles, dim3(CL_THREADS), 0, st, labels, (const int*)parent, (const int*)aux, (const int*)info, out, H,
+                       W, max_small, L.tiles_x, (int)L.tpf);
+  STSWIN_CHECK_LAUNCH();
+  return 0;
+}
+
+// The counts of the label launches, from a label map that already exists (VideoSegmenter(clean_area=A) scores the cleaned labels):
+// counts[f][0 | 1 | 2][c] += |gt == c|, |labels == c|, |gt == c and labels == c| as upsample_argmax_kernel counts them, and / or
+// cm[gt][labels] += 1 where both lie in [0, ncm) as upsample_argmax_cm_kernel does.  A workgroup takes LS_PIX consecutive pixels of one
+// frame, counts them into LDS bins and adds every non-zero bin with one atomic.
+#define LS_PIX 4096
+
+template <bool CNT, bool CM>
+__global__ __launch_bounds__(256) void labels_score_kernel(const unsigned char* __restrict__ labels, const long long* __restrict__ gt,
+                                                           int* counts, unsigned long long* cm, int ncm, int nc, long HW,
+                                                           int blocks_per_frame) {
+  __shared__ int hist[CNT ? 3 * 64 : 1];
+  __shared__ int hcm[CM ? 64 * 64 : 1];
+  const int bins = ncm * ncm;
+  if (CNT)
+    for (int i = threadIdx.x; i < 3 * 64; i += 256) hist[i] = 0;
+  if (CM)
+    for (int i = threadIdx.x; i < bins; i += 256) hcm[i] = 0;
+  __syncthreads();
+  const int f = (int)(blockIdx.x / (unsigned)blocks_per_frame);
+  const long p0 = (long)(blockIdx.x % (unsigned)blocks_per_frame) * LS_PIX;
+  for (int k = 0; k < LS_PIX / 256; ++k) {
+    const long px = p0 + k * 256 + threadIdx.x;
+    if (px >= HW) break;
+    const long long g = gt[(long)f * HW + px];
+    const int l = (int)labels[(long)f * HW + px];
+    if (CNT) {
+      if (g >= 0 && g < 64) atomicAdd(&hist[(int)g], 1);
+      if (l < nc) {
+        atomicAdd(&hist[64 + l], 1);
+        if (g == (long long)l) atomicAdd(&hist[128 + l], 1);
+      }
+    }
+    if (CM && g >= 0 && g < ncm && l < ncm) atomicAdd(&hcm[(int)g * ncm + l], 1);
+  }
+  __syncthreads();
+  if (CNT)
+    for (int i = threadIdx.x; i < 3 * 64; i += 256) {
+      const int k = i / 64, c = i % 64;
+      if (c < nc && hist[i]) atomicAdd(counts + ((long)f * 3 + k) * nc + c, hist[i]);
+    }
+  if (CM)
+    for (int i = threadIdx.x; i < bins; i += 256)
+      if (hcm[i]) atomicAdd(cm + i, (unsigned long long)hcm[i]);
+}
+
+extern "C" int stswin_labels_score(const unsigned char* labels, const long long* gt, int* counts, unsigned long long* cm, int ncm, int n, int H,
+                                   int W, int nc, void* stream) {
+  if (n <= 0 || H <= 0 || W <= 0 || H > 16384 || W > 16384) return -1910;
+  if (labels == nullptr || gt == nullptr || (counts == nullptr && cm == nullptr)) return -1911;
+  if (nc < 1 || nc > 64 || (cm != nullptr && (ncm < 1 || ncm > 64))) return -1912;
+  if (((uintptr_t)gt & 7) || ((uintptr_t)counts & 3) || ((uintptr_t)cm & 7)) return -1913;
+  const long HW = (long)H * W, bpf = (HW + LS_PIX - 1) / LS_PIX;
+  if (bpf * n > 0x7fffffffL) return -1910;
+  dim3 grid((unsigned)(bpf * n));
+  hipStream_t st = (hipStream_t)stream;
+#define LS_LAUNCH(CNT_, CM_) \
+  hipLaunchKernelGGL((labels_score_kernel<CNT_, CM_>), grid, dim3(256), 0, st, labels, gt, counts, cm, cm ? ncm : 1, nc, HW, (int)bpf)
+  if (counts != nullptr && cm != nullptr) LS_LAUNCH(true, true);
+  else if (counts != nullptr) LS_LAUNCH(true, false);
+  else LS_LAUNCH(false, true);
+#undef LS_LAUNCH
+  STSWIN_CHECK_LAUNCH();
+  return 0;
+}
+
 // Instances followed from frame to frame (stswincl_amd/utils/instruments.py, InstanceTracker, states the result;
 // VideoSegmenter(tracks=True)).  The state buffer, in int32 words (include/stswin_hip.h states it too):
 //   [0] next id  [1] number of listed pairs  [2], [3] unused      cls[K], area[K], id[K] of the previous frame's instances (cls -1: takes

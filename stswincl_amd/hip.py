@@ -1972,6 +1972,132 @@ def instance_parts(labels: torch.Tensor, components: torch.Tensor, K: int, nc: i
     return tuple(out)
 
 
+def labels_clean_geometry():
+    """(vote tile height, vote tile width, raster chunk of the numbering pass, slots of the on-chip vote table) of hip.labels_clean
+    (stswin_labels_clean_geometry)."""
+    geo = load().stswin_labels_clean_geometry
+    return int(geo(0)), int(geo(1)), int(geo(2)), int(geo(3))
+
+
+def _clean_ints(fn: str, nc, max_small) -> None:
+    if isinstance(nc, bool) or not isinstance(nc, int) or not 1 <= nc <= 64:
+        raise StswinHipError(f"{fn}: {nc!r} classes, the kernel takes 1 .. 64")
+    if isinstance(max_small, bool) or not isinstance(max_small, int) or not 1 <= max_small <= 65536:
+        raise StswinHipError(f"{fn}: max_small must be an int 1 .. 65536, got {max_small!r}")
+
+
+def labels_clean_scratch(n: int, H: int, W: int, nc: int, max_small: int = 4096) -> int:
+    """Bytes of workspace hip.labels_clean needs for labels [n][H][W] of nc classes."""
+    _clean_ints("labels_clean", nc, max_small)
+    b = int(load().stswin_labels_clean_scratch(n, H, W, nc, max_small))
+    if b < 0:
+        raise StswinHipError(f"labels_clean: {n} maps of {H} x {W}, the kernel takes up to 16384 x 16384")
+    return b
+
+
+def labels_clean(labels: torch.Tensor, nc: int, min_area: int, connectivity: int = 8, keep=(), max_small: int = 4096,
+                 out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None):
+    """uint8 labels [n][H][W] -> (out uint8 [n][H][W], stats int32 [n][2]): the label map with its specks removed and its small holes
+    filled.  A component (4- or 8-connectivity, every class c < nc) of fewer than min_area pixels whose class is not in `keep` is small
+    and takes the class that most of its pixel edges towards stable pixels - those of components that are not small - lead to, the
+    smallest class on a tie, its own without such an edge; of a frame's small components, numbered by their first pixel in raster
+    order, the first max_small can change.  stats[f] = (small components of frame f, not bounded by max_small; pixels whose label
+    changed).  utils.instruments.clean_labels is the numpy definition, matched bit for bit, truncation included.  out: such a buffer,
+    written in full; workspace: uint8, >= labels_clean_scratch(n, H, W, nc, max_small) bytes.  With both given the call allocates only
+    stats and synchronises nothing (graph-capturable).  Returns (out, stats) (include/stswin_hip.h, stswin_labels_clean)."""
+    if not isinstance(labels, torch.Tensor) or labels.dtype != torch.uint8 or labels.dim() != 3 or not labels.is_contiguous():
+        raise StswinHipError(f"labels_clean: labels must be contiguous uint8 [n][H][W], got {_got(labels)}")
+    if not labels.is_cuda:
+        raise StswinHipError("labels_clean: labels must be on the GPU (no CPU path exists; utils.instruments.clean_labels is the numpy "
+                             "definition)")
+    n, H, W = labels.shape
+    if n <= 0 or H <= 0 or W <= 0:
+        raise StswinHipError(f"labels_clean: empty labels {tuple(labels.shape)}")
+    if H > 16384 or W > 16384:
+        raise StswinHipError(f"labels_clean: a {H} x {W} map, the kernel takes up to 16384 x 16384")
+    _clean_ints("labels_clean", nc, max_small)
+    if isinstance(min_area, bool) or not isinstance(min_area, int) or not 2 <= min_area <= 1 << 30:
+        raise StswinHipError(f"labels_clean: min_area must be an int 2 .. 2^30, got {min_area!r}")
+    if isinstance(connectivity, bool) or not isinstance(connectivity, int) or connectivity not in (4, 8):
+        raise StswinHipError(f"labels_clean: connectivity must be 4 or 8, got {connectivity!r}")
+    try:
+        keep = tuple(keep)
+    except TypeError:
+        keep = (keep,)
+    if any(isinstance(c, bool) or not isinstance(c, int) or not 0 <= c <= 63 for c in keep):
+        raise StswinHipError(f"labels_clean: keep holds classes 0 .. 63, got {keep!r}")
+    dev = labels.device
+    if out is None:
+        out = torch.empty_like(labels)
+    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != (n, H, W) or not out.is_contiguous()
+          or out.device != dev):
+        raise StswinHipError(f"labels_clean: out must be contiguous uint8 [{n}][{H}][{W}] on {dev}, got {_got(out)}")
+    need = labels_clean_scratch(n, H, W, nc, max_small)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.dim() != 1 or not workspace.is_contiguous()
+          or workspace.device != dev):
+        raise StswinHipError(f"labels_clean: workspace must be contiguous uint8 [bytes] on {dev}, got {_got(workspace)}")
+    elif workspace.numel() < need:
+        raise StswinHipError(f"labels_clean: a workspace of {workspace.numel()} bytes, {n} maps of {H} x {W} need {need}")
+    elif workspace.data_ptr() % 4:
+        raise StswinHipError("labels_clean: workspace must be 4-byte aligned")
+    bufs = (("labels", labels), ("out", out), ("workspace", workspace))
+    for i, (wa, a) in enumerate(bufs):
+        for wb, b in bufs[i + 1:]:
+            if _same_memory(a, b):
+                raise StswinHipError(f"labels_clean: {wb} shares memory with {wa}")
+    stats = torch.empty(n, 2, dtype=torch.int32, device=dev)
+    mask = 0
+    for c in keep:
+        mask |= 1 << c
+    if mask >= 1 << 63:                      # (the mask travels in a C long: bit 63 is its sign bit)
+        mask -= 1 << 64
+    _check(load().stswin_labels_clean(_p(labels), _p(out), _p(stats), n, H, W, nc, connectivity, mask, min_area, max_small,
+                                      _p(workspace), workspace.numel(), _stream()), "labels_clean")
+    return out, stats
+
+
+def labels_score(labels: torch.Tensor, gt: torch.Tensor, nc: int, counts: Optional[torch.Tensor] = None,
+                 cm: Optional[torch.Tensor] = None):
+    """uint8 labels [n][H][W] and int64 gt [n][H][W] -> (counts, cm): what the fused label launches count, from a label map that
+    already exists.  counts int32 [n][3][nc] (made of zeros when neither is given; a given one is added to): per frame and class
+    |gt == c|, |labels == c|, |gt == c and labels == c|, the integers of hip.upsample_argmax.  cm int64 [ncm][ncm]: every pixel with
+    gt and label in [0, ncm) adds 1 to cm[gt][label]; accumulated, not cleared, as hip.upsample_argmax_cm does.  One launch, no
+    synchronisation (include/stswin_hip.h, stswin_labels_score)."""
+    if not isinstance(labels, torch.Tensor) or labels.dtype != torch.uint8 or labels.dim() != 3 or not labels.is_contiguous():
+        raise StswinHipError(f"labels_score: labels must be contiguous uint8 [n][H][W], got {_got(labels)}")
+    if not labels.is_cuda:
+        raise StswinHipError("labels_score: labels must be on the GPU (no CPU path exists)")
+    n, H, W = labels.shape
+    dev = labels.device
+    if n <= 0 or H <= 0 or W <= 0 or H > 16384 or W > 16384:
+        raise StswinHipError(f"labels_score: labels {tuple(labels.shape)}, the kernel takes 1 .. 16384 x 1 .. 16384")
+    if (not isinstance(gt, torch.Tensor) or gt.dtype != torch.int64 or tuple(gt.shape) != (n, H, W) or not gt.is_contiguous()
+            or gt.device != dev):
+        raise StswinHipError(f"labels_score: gt must be contiguous int64 [{n}][{H}][{W}] on {dev}, got {_got(gt)}")
+    if isinstance(nc, bool) or not isinstance(nc, int) or not 1 <= nc <= 64:
+        raise StswinHipError(f"labels_score: {nc!r} classes, the kernel takes 1 .. 64")
+    if counts is None and cm is None:
+        counts = torch.zeros(n, 3, nc, dtype=torch.int32, device=dev)
+    if counts is not None and (not isinstance(counts, torch.Tensor) or counts.dtype != torch.int32 or tuple(counts.shape) != (n, 3, nc)
+                               or not counts.is_contiguous() or counts.device != dev):
+        raise StswinHipError(f"labels_score: counts must be contiguous int32 [{n}][3][{nc}] on {dev}, got {_got(counts)}")
+    ncm = 0
+    if cm is not None:
+        if (not isinstance(cm, torch.Tensor) or cm.dtype != torch.int64 or cm.dim() != 2 or cm.shape[0] != cm.shape[1]
+                or not cm.is_contiguous() or cm.device != dev):
+            raise StswinHipError(f"labels_score: cm must be contiguous int64 [ncm][ncm] on {dev}, got {_got(cm)}")
+        ncm = cm.shape[0]
+        if not 1 <= ncm <= 64:
+            raise StswinHipError(f"labels_score: a {ncm} x {ncm} matrix, the kernel takes 1 .. 64 classes")
+    for what, t in (("counts", counts), ("cm", cm)):
+        if t is not None and (_same_memory(t, labels) or _same_memory(t, gt)):
+            raise StswinHipError(f"labels_score: {what} shares memory with labels or gt")
+    _check(load().stswin_labels_score(_p(labels), _p(gt), _p(counts), _p(cm), ncm, n, H, W, nc, _stream()), "labels_score")
+    return counts, cm
+
+
 YUV_NV12, YUV_UYVY = 0, 1                    # stswin_yuv_to_rgb's `format` (plain integers in the header's comment, not #defines)
 YUV_REPLICATE, YUV_LINEAR = 0, 1               # ... and its `chroma`
 _YUV_FORMATS = {"nv12": YUV_NV12, "uyvy": YUV_UYVY}

@@ -22,6 +22,9 @@ the grouped labels are whole instruments (VideoSegmenter(instance_groups=...)); 
 is made of (the ten integers again) and how many pixel edges it shares with each class outside itself (hip.instance_parts,
 VideoSegmenter(parts=...)), and PartsReport reads both beside the instance and track reports.
 
+clean_labels states what hip.labels_clean writes (VideoSegmenter(clean_area=A)): the label map with its small components relabelled by
+the vote of their stable neighbours - specks out, small holes filled - before anything above reads it.
+
 This module ships no dataset's class names or ids: pass `names` if the rows of a log should carry them."""
 from __future__ import annotations
 
@@ -674,6 +677,75 @@ def instance_parts(labels, components, K: int, nc: int):
             e = owned[f][p] & (comp[f][q] != comp[f][p]) & classed[f][q]
             contacts[f] += np.bincount(comp[f][p][e] * nc + lab[f][q][e], minlength=K * nc)
     return parts.reshape(n, K, nc, ROW), contacts.reshape(n, K, nc)
+
+
+def clean_labels(labels, nc: int, min_area: int, connectivity: int = 8, keep: Sequence[int] = (), max_small: int = 4096):
+    """Integer labels [n][H][W] -> (out uint8 [n][H][W], stats int32 [n][2]): the label map with its specks removed and its small holes
+    filled, what hip.labels_clean gives bit for bit (VideoSegmenter(clean_area=...)).
+
+    The components are those of label_components(labels, nc, connectivity, skip=()): of every class c < nc, nothing skipped; pixels
+    with a label >= nc belong to no component, are never changed and never vote.  A component is small if its area is < min_area and
+    its class is not in `keep` (the classes that are thin by nature: thread, needle); every other pixel of a class < nc is stable.
+    The small components of a frame are numbered s = 0, 1, ... by their first pixel in raster order and only those with s < max_small
+    can be relabelled; the rest stay as they are but still count as small: they do not vote.  votes[s][c] is the number of ordered
+    pairs (p, q), p a pixel of small component s, q one of p's four neighbours inside the frame, stable and with labels[q] == c -
+    always of the input labels: one pass.  Only stable pixels vote, so two adjacent specks cannot swap labels and a speck among specks
+    stays.  The component's new label is the smallest c with the largest votes[s][c] if that is > 0, else its own.
+    stats[f] = (the frame's number of small components, not bounded by max_small: a truncated frame shows as stats[f][0] > max_small;
+    the number of pixels whose label changed)."""
+    lab = np.asarray(labels)
+    if lab.ndim != 3 or lab.dtype.kind not in "iu" or min(lab.shape) < 1:
+        raise ValueError(f"clean_labels: labels are integers [n][H][W], got {lab.dtype} {lab.shape}")
+    if isinstance(nc, bool) or int(nc) != nc or not 1 <= nc <= 64:
+        raise ValueError(f"clean_labels: 1 .. 64 classes, got {nc!r}")
+    if isinstance(min_area, bool) or not isinstance(min_area, (int, np.integer)) or not 2 <= min_area <= 1 << 30:
+        raise ValueError(f"clean_labels: min_area is an int 2 .. 2^30, got {min_area!r}")
+    if connectivity not in (4, 8):
+        raise ValueError(f"clean_labels: connectivity is 4 or 8, got {connectivity!r}")
+    try:
+        keep = tuple(keep)
+    except TypeError:
+        raise ValueError(f"clean_labels: keep holds classes 0 .. 63, got {keep!r}") from None
+    if any(isinstance(c, bool) or not isinstance(c, (int, np.integer)) or not 0 <= c <= 63 for c in keep):
+        raise ValueError(f"clean_labels: keep holds classes 0 .. 63, got {keep!r}")
+    if isinstance(max_small, bool) or not isinstance(max_small, (int, np.integer)) or not 1 <= max_small <= 65536:
+        raise ValueError(f"clean_labels: max_small is an int 1 .. 65536, got {max_small!r}")
+    n, H, W = lab.shape
+    comp = label_components(lab, nc, connectivity, (), 1)[0].astype(np.int64)          # ordinals in raster order of the first pixel
+    lab64 = lab.astype(np.int64)
+    out = lab.astype(np.uint8)
+    stats = np.zeros((n, 2), dtype=np.int32)
+    for f in range(n):
+        c, l = comp[f], lab64[f]
+        inside = c >= 0
+        if not inside.any():
+            continue
+        area = np.bincount(c[inside])
+        cls = np.zeros(area.size, dtype=np.int64)
+        cls[c[inside][::-1]] = l[inside][::-1]                                        # (every pixel of a component has its class)
+        small = (area < min_area) & ~np.isin(cls, keep)
+        number = np.cumsum(small) - 1                                                 # s of a small component
+        stats[f, 0] = int(small.sum())
+        live = small & (number < max_small)                                           # the ones that can be relabelled
+        S = min(int(small.sum()), max_small)
+        if S == 0:
+            continue
+        stable = inside & ~small[np.where(inside, c, 0)]
+        voter = inside & live[np.where(inside, c, 0)]
+        votes = np.zeros(S * nc, dtype=np.int64)
+        for p, q in (((slice(1, None), slice(None)), (slice(None, -1), slice(None))), ((slice(None, -1), slice(None)), (slice(1, None), slice(None))),
+                     ((slice(None), slice(1, None)), (slice(None), slice(None, -1))), ((slice(None), slice(None, -1)), (slice(None), slice(1, None)))):
+            e = voter[p] & stable[q]
+            votes += np.bincount(number[c[p][e]] * nc + l[q][e], minlength=S * nc)
+        votes = votes.reshape(S, nc)
+        best = votes.argmax(axis=1)                                                   # the first, so the smallest, class of the maximum
+        old = cls[live]
+        new = np.where(votes.max(axis=1) > 0, best, old)
+        table = cls.copy()
+        table[live] = new
+        stats[f, 1] = int(area[live][new != old].sum())
+        out[f][inside] = table[c[inside]].astype(np.uint8)
+    return out, stats
 
 
 class PartsReport:

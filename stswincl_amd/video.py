@@ -42,7 +42,7 @@ from . import hip
 from .frames import (CADIS_MEAN, CADIS_SIZE, CADIS_STD, RULES, T, VALUE_TABLE, bilinear_coeffs, cadis_value_table,  # noqa: F401
                      PRECISION_BITS as _PRECISION_BITS, Pinned as _Pinned, check_rule as _check_rule, tables as _tables, value_lut as _lut)
 from .hip import StswinHipError
-from .video_report import DeviceLog, ReportChain, Yield
+from .video_report import DeviceLog, LabelCleaner, ReportChain, Yield
 
 PIXEL_FORMATS = ("rgb", "nv12", "uyvy")
 _FRAME_FORMS = {"rgb": "uint8 RGB [n][Hs][Ws][3]", "nv12": "uint8 NV12 [n][3 Hs / 2][Ws]", "uyvy": "uint8 UYVY [n][Hs][Ws][2]"}
@@ -195,7 +195,7 @@ class VideoSegmenter:
     """Segment video sequences with an eval-mode TswinPlus, one result per frame, each frame's ResNet features computed once.
 
     seg = VideoSegmenter(model, batch=1, out="logits" | "labels" | "overlay", out_size=None, graph=False, report=None, instances=None,
-                         tracks=False, masks=None, boundary=None, confidence=None, instance_groups=None, parts=None)
+                         tracks=False, masks=None, boundary=None, confidence=None, instance_groups=None, parts=None, clean_area=None)
 
     push(frames, gt=None) takes uint8 RGB frames [n][Hs][Ws][3] (or one [Hs][Ws][3]; torch tensor on the model's GPU or the CPU, or
     a numpy array; NV12 or UYVY frames with pixel_format, below) and returns [(frame_index, result), ...] for the frames whose clip is now complete.  finish() runs what is
@@ -394,6 +394,26 @@ class VideoSegmenter:
     joined by row with instance_report() under report="deferred" and with track_report() under tracks=True.  parts=None: every
     result, launch and captured graph is what it is without the keyword.
 
+    clean_area=A (2 .. 2^30 pixels; out="labels" | "overlay", both protocols, every scores mode, batch > 1 and graph=True; a model of 1 ..
+    64 classes; clean_keep=None, clean_connectivity=8 | 4, clean_max=4096): the label map cleaned before anything reads it - specks out,
+    small holes filled.  Wherever a step's label map is made, the launches of hip.labels_clean (utils.instruments.clean_labels states
+    the result) follow the label launch and precede everything else: a connected component of any class with fewer than A pixels,
+    unless its class is in clean_keep (the classes that are thin by nature - thread, needle; the ids are the caller's), takes the class
+    that most of its pixel edges towards stable pixels lead to; a speck among specks stays, and of a frame's small components the first
+    clean_max in raster order can change.  With the keyword the labels are the cleaned labels everywhere: the returned labels or
+    overlay, the moments, grouped labels, components, tracks, masks, parts and contacts come from the cleaned map (the tracker's parking
+    is as it was: the cleaning sits in front of the chain), and confidence is the probability of the cleaned label.  With ground truth
+    the scores are those of the cleaned labels: the label launch runs without gt, then the cleaning, then one launch of
+    hip.labels_score takes the counts scores="frame" builds its lists from, scores="deferred" logs and protocol="cadis" adds to the
+    confusion matrix, and boundary="deferred" reads the cleaned labels.  Under graph=True the cleaning launches are part of the captured
+    steady step; the workspace is the segmenter's own, allocated by the warm-up frames (it only grows, retired ones are kept), the
+    cleaned map is a fresh tensor per eager step and the graph's buffer under replay, so the labels of the last replayed step of a push
+    are a view of the graph's buffer, as they are without the keyword.  The cleaning's stats - the frame's small components, not
+    bounded by clean_max, and the pixels whose label changed - go into a small device log, one row per released frame, copied out of
+    the graph's buffer after a replay: no download and no synchronisation per frame.  clean_report() downloads it once and returns
+    video_report.CleanReport over every frame released since reset_metrics(), in instrument_report()'s order and with its sequence
+    ordinals.  clean_area=None: every result, launch and captured graph is what it is without the keyword.
+
     Runs under torch.no_grad().  Refuses (StswinHipError): a model in train mode, a model or frames not on the GPU, a frame size
     that differs from the earlier frames'."""
 
@@ -406,7 +426,8 @@ class VideoSegmenter:
                  tracks: bool = False, track_iou: int = 100, track_same_class: bool = True, masks: Optional[str] = None,
                  mask_runs: int = 16384, track_max_gap: int = 0, boundary: Optional[str] = None, boundary_bins: int = 32,
                  boundary_skip: Optional[Sequence[int]] = None, confidence: Optional[str] = None, confidence_low: int = 128,
-                 instance_groups=None, parts: Optional[str] = None):
+                 instance_groups=None, parts: Optional[str] = None, clean_area: Optional[int] = None, clean_keep: Optional[Sequence[int]] = None,
+                 clean_connectivity: int = 8, clean_max: int = 4096):
         if out not in ("logits", "labels", "overlay"):
             raise StswinHipError(f"out must be 'logits', 'labels' or 'overlay', got {out!r}")
         if pixel_format not in PIXEL_FORMATS:
@@ -485,6 +506,12 @@ class VideoSegmenter:
                 raise StswinHipError(f"boundary_skip holds classes 0 .. 63, got {boundary_skip!r}")
         self.boundary, self.boundary_bins, self.boundary_skip = boundary, boundary_bins, boundary_skip
         self._classes = classes
+        if clean_area is None and (clean_keep is not None or clean_connectivity != 8 or clean_max != 4096):
+            raise StswinHipError("clean_keep, clean_connectivity and clean_max belong to clean_area=A")
+        # clean_area: the launches of hip.labels_clean behind every label launch, its workspace and the log of its stats
+        self.cleaner = None if clean_area is None else LabelCleaner(self.device, classes, out, clean_area, clean_keep, clean_connectivity, clean_max)
+        self.clean_area, self.clean_connectivity, self.clean_max = clean_area, clean_connectivity, clean_max
+        self.clean_keep = self.cleaner.keep if self.cleaner is not None else None
         # boundary="deferred": a row per frame pushed with gt, beside _score_log; the call's output row and workspace are the segmenter's
         self._boundary_log = DeviceLog(self.device, {"counts": ((classes, 2, 2 + boundary_bins), torch.int32)})
         self._boundary_out = self._boundary_ws = None
@@ -544,12 +571,16 @@ class VideoSegmenter:
         self._score_log.end_sequence()    # scores="deferred": the sequence that ends here uses up its ordinal if it has rows in the log
         self.chain.reset()                # report="deferred": likewise, with its own ordinal; tracks: ids restart at 0
         self._boundary_log.end_sequence()  # boundary="deferred": likewise
+        if self.cleaner is not None:
+            self.cleaner.log.end_sequence()  # clean_area: likewise
 
     def reset_metrics(self) -> None:
         """Clear what an evaluation pools and reset() keeps: the confusion matrix (protocol="cadis"), the score log and its sequence
         ordinal (scores="deferred"), the instrument log and its ordinal (report="deferred"), the count of unmatched ground-truth
         pixels (gt_table); masks="deferred", confidence="deferred" and parts="deferred" log into the instrument log; the boundary log
-        and its ordinal (boundary="deferred")."""
+        and its ordinal (boundary="deferred"); the log of the cleaning's stats and its ordinal (clean_area)."""
+        if self.cleaner is not None:
+            self.cleaner.log.clear()
         if self._cm is not None:
             self._cm.zero_()
         self._score_log.clear()
@@ -588,6 +619,14 @@ class VideoSegmenter:
         res = BoundaryScores.from_counts(cols["counts"], sequences, frames)
         res.names = list(names) if names is not None else None
         return res
+
+    def clean_report(self):
+        """clean_area=A: one download of the stats log -> video_report.CleanReport over every frame released since reset_metrics() - per
+        frame the small components of its raw label map (small[r] > clean_max: a truncated frame) and the pixels whose label changed -
+        rows ordered by sequence and frame (.sequences[r], .frames[r]) as instrument_report() orders them."""
+        if self.cleaner is None:
+            raise StswinHipError("clean_report() belongs to clean_area=A")
+        return self.cleaner.report()
 
     def _boundary(self, frame: int, gt: torch.Tensor, lab: torch.Tensor) -> None:
         """boundary="deferred": the five launches of hip.boundary_counts on a scored frame's gt and labels [1][*out_size], behind the
@@ -862,7 +901,8 @@ class VideoSegmenter:
                  tracked: bool = False):
         """ResNet on the new frames' images, clip assembly, Swin / ASPP / head: -> logits (B, nc, H, W), and with labels = True the
         labels (B, *out_size), or for out="overlay" the overlay (B, *out_size, 3) on `frames`, one uint8 [1][Hs][Ws][3] per clip, and
-        with report what the labels yield per clip (_finish_labels; `tracked`: the graph's steady step, the tracker's launches in it).
+        with report what the labels yield per clip (_finish_labels; `tracked`: the graph's steady step, the tracker's launches in it),
+        and with clean_area the cleaning's stats (B, 2): the labels are then the cleaned ones, made behind the label launch.
         Every launch on the current stream, no host synchronisation (graph-capturable)."""
         m = self.model
         hip.arena_reset(self.device)
@@ -885,8 +925,34 @@ class VideoSegmenter:
         hip.clip_assemble(self._ring, tok, clips, table, B, n_new)
         logits = m.forward_frame_tokens(clips, h, w, self.size[0], self.size[1])
         if labels:
-            return (logits,) + self._finish_labels(self._labels(logits), frames, steady=tracked, logits=logits)
-        return logits, None, None
+            lab, stats = self._clean(self._labels(logits))
+            return (logits,) + self._finish_labels(lab, frames, steady=tracked, logits=logits) + (stats,)
+        return logits, None, None, None
+
+    def _clean(self, lab: Optional[torch.Tensor]):
+        """clean_area: a step's (a clip's) labels -> (the cleaned labels, the stats), behind the label launch and in front of
+        everything that reads the labels; without the keyword (or without labels) the labels themselves and None."""
+        if self.cleaner is None or lab is None:
+            return lab, None
+        return self.cleaner.clean(lab)
+
+    def _score_cleaned(self, g: int, logits: torch.Tensor, gt: torch.Tensor):
+        """clean_area with ground truth: the label launch without gt, the cleaning launches, then hip.labels_score counts the cleaned
+        labels as the fused launches count their own -> (labels, stats, (dice, iou) or ())."""
+        lab, stats = self._clean(self._labels(logits))
+        gt = gt.contiguous()
+        if self.cadis:
+            if self._cm is None:
+                self._cm = torch.zeros(self.metric_classes, self.metric_classes, dtype=torch.int64, device=self.device)
+            hip.labels_score(lab, gt, self._classes, cm=self._cm)
+            return lab, stats, ()
+        counts = hip.labels_score(lab, gt, self._classes)[0]
+        if self.scores == "deferred":
+            self._score_log.append(g, counts=counts)
+            return lab, stats, ()
+        from .utils.EndoMetric import _frame_lists
+        dices, ious = _frame_lists(counts.cpu().numpy().astype(np.float64))
+        return lab, stats, (dices[0], ious[0])
 
     def _finish_labels(self, lab: torch.Tensor, frames, clips: Optional[List[int]] = None, steady: bool = False,
                        logits: Optional[torch.Tensor] = None):
@@ -933,13 +999,13 @@ class VideoSegmenter:
         B, n_new = len(st.clips), len(st.new)
         want_labels = self.out != "logits" and not any(g in self._gt for g in st.clips)
         if self.graph and self._steady(st):
-            logits, labels, extras, replayed, frames = self._run_graph(st, want_labels)
+            logits, labels, extras, stats, replayed, frames = self._run_graph(st, want_labels)
         else:
             img = self._ingest_new(st.new) if n_new else None
             frames = [self._kept.pop(g) for g in st.clips] if self._table is not None else None
-            logits, labels, extras = self._compute(img, self._upload_table(st.table()), B, n_new, want_labels, frames)
+            logits, labels, extras, stats = self._compute(img, self._upload_table(st.table()), B, n_new, want_labels, frames)
             replayed = False
-        return self._results(st.clips, logits, labels, frames, extras), replayed
+        return self._results(st.clips, logits, labels, frames, extras, stats), replayed
 
     def _run_graph(self, st: Step, want_labels: bool):
         src, r = self._frames.pop(st.new[0])
@@ -960,7 +1026,7 @@ class VideoSegmenter:
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
-                logits, labels, extras = self._compute(self._static_image(raw, u8), table, 1, 1, want_labels, frames, tracked)
+                logits, labels, extras, stats = self._compute(self._static_image(raw, u8), table, 1, 1, want_labels, frames, tracked)
                 logits = logits.clone()
             torch.cuda.current_stream().wait_stream(side)
             torch.cuda.synchronize()
@@ -968,29 +1034,34 @@ class VideoSegmenter:
             graph = torch.cuda.CUDAGraph()
             autocast = torch.is_autocast_enabled()
             with torch.cuda.graph(graph):
-                out, out_labels, out_extras = self._compute(self._static_image(raw, u8), table, 1, 1, want_labels, frames, tracked)
-            self._g = Captured(graph, raw, table, out, out_labels, want_labels, autocast, u8, out_extras)
-            return logits, labels, extras, False, frames
+                out, out_labels, out_extras, out_stats = self._compute(self._static_image(raw, u8), table, 1, 1, want_labels, frames, tracked)
+            self._g = Captured(graph, raw, table, out, out_labels, want_labels, autocast, u8, out_extras, out_stats)
+            return logits, labels, extras, stats, False, frames
         if torch.is_autocast_enabled() != g.autocast:
             raise StswinHipError("autocast differs from the state the step was captured under: make a new VideoSegmenter")
         self._put_frames(src, r, 1, g.raw)
         self._upload_table(st.table(), g.table)
         g.graph.replay()
-        return g.out, g.labels, g.extras, True, [g.u8] if self._table is not None else None
+        return g.out, g.labels, g.extras, g.stats, True, [g.u8] if self._table is not None else None
 
     def _results(self, clips: List[int], logits: torch.Tensor, labels: Optional[torch.Tensor], frames=None,
-                 extras: Optional[List[Yield]] = None) -> List[Tuple[int, object]]:
-        """`labels`: the step's labels (out="overlay": its overlays) and with report their `extras` per clip, or None when some clip
-        has ground truth or out="logits": each clip's labels then come from its own (scoring) launch."""
+                 extras: Optional[List[Yield]] = None, stats: Optional[torch.Tensor] = None) -> List[Tuple[int, object]]:
+        """`labels`: the step's labels (out="overlay": its overlays), with report their `extras` per clip and with clean_area the
+        cleaning's `stats`, or None when some clip has ground truth or out="logits": each clip's labels then come from its own
+        (scoring) launch."""
         if labels is not None:
             results = list(labels)
+            if stats is not None:
+                self.cleaner.released(clips, stats)
         else:
             results, extras = [], []
             for b, g in enumerate(clips):
                 gt = self._gt.pop(g, None)
                 scored = ()
                 if gt is None:
-                    lab = self._labels(logits[b:b + 1]) if self.out != "logits" else None
+                    lab, stats = self._clean(self._labels(logits[b:b + 1]) if self.out != "logits" else None)
+                elif self.cleaner is not None:     # the scores are those of the cleaned labels
+                    lab, stats, scored = self._score_cleaned(g, logits[b:b + 1], gt)
                 elif self.cadis:
                     lab = self._labels(logits[b:b + 1], gt, want=self.out != "logits")
                 elif self.scores == "deferred":       # the counts stay on the device: no download, no synchronisation
@@ -1000,6 +1071,8 @@ class VideoSegmenter:
                     from .utils.EndoMetric import predict_and_score
                     lab, dices, ious = predict_and_score(logits[b:b + 1], self.out_size, gt)
                     scored = (dices[0], ious[0])
+                if self.cleaner is not None:
+                    self.cleaner.released([g], stats)
                 if gt is not None and self.boundary is not None:
                     self._boundary(g, gt, lab)
                 r, y = logits[b], None
@@ -1013,7 +1086,8 @@ class VideoSegmenter:
 
 # The graph's steady step: the static buffers it reads (raw: the pushed frame; u8: the RGB frame, the same tensor for pixel_format="rgb";
 # the slot table) and writes (out: the logits; with want_labels the labels or overlays and the report chain's extras), its autocast state
-Captured = namedtuple("Captured", "graph raw table out labels want_labels autocast u8 extras")
+# and with clean_area the cleaning's stats
+Captured = namedtuple("Captured", "graph raw table out labels want_labels autocast u8 extras stats")
 
 
 def _clone(r):

@@ -1,5 +1,6 @@
 """What a VideoSegmenter makes of its label maps beside the result (its docstring states the keywords): the chain moments -> instances
--> tracks -> masks -> confidence -> parts with its buffers (ReportChain), its record (Yield), the tracker's frame order (TrackSequencer) and the device log."""
+-> tracks -> masks -> confidence -> parts with its buffers (ReportChain), its record (Yield), the tracker's frame order (TrackSequencer) and the device log;
+and what it does to them before anything reads them: the cleaning of clean_area (LabelCleaner) and its report (CleanReport)."""
 from __future__ import annotations
 
 from collections import namedtuple
@@ -65,6 +66,75 @@ class DeviceLog:
             shape, dtype = self.columns[name]
             cols[name] = self.data[name][:n].cpu().numpy()[order] if n else torch.zeros(0, *shape, dtype=dtype).numpy()
         return cols, [self.keys[r][0] for r in order], [self.keys[r][1] for r in order]
+
+
+class CleanReport:
+    """VideoSegmenter(clean_area=A).clean_report(): what the cleaning did per released frame, rows ordered by sequence and frame.
+    frames[r], sequences[r]: the row's frame index and its sequence's ordinal; small[r]: the small components of the frame's raw label
+    map (not bounded by clean_max: small[r] > max_small is a truncated frame); changed[r]: the pixels whose label changed."""
+
+    def __init__(self, stats, frames, sequences, max_small: int):
+        self.frames, self.sequences, self.max_small = list(frames), list(sequences), max_small
+        self.small, self.changed = stats[:, 0].copy(), stats[:, 1].copy()
+
+    def __len__(self):
+        return len(self.frames)
+
+    def as_rows(self) -> List[dict]:
+        return [dict(sequence=s, frame=f, small=int(k), changed=int(c), truncated=bool(k > self.max_small))
+                for s, f, k, c in zip(self.sequences, self.frames, self.small, self.changed)]
+
+
+class LabelCleaner:
+    """clean_area of a VideoSegmenter: the launches of hip.labels_clean on every label map the segmenter makes, in front of everything
+    that reads the labels.  Owns the workspace (it only grows; the ones it replaced are kept, a captured step may still use them) and
+    the device log of the stats, one row per released frame.  The cleaned map and the stats are fresh per step (under capture: the
+    graph's), as the labels they replace are."""
+
+    def __init__(self, device, classes: int, out: str, area, keep, connectivity, max_small):
+        if area is None:
+            raise StswinHipError("internal error: a LabelCleaner without clean_area")
+        if out == "logits":
+            raise StswinHipError("clean_area cleans the label map: out must be 'labels' or 'overlay'")
+        if isinstance(area, bool) or not isinstance(area, int) or not 2 <= area <= 1 << 30:
+            raise StswinHipError(f"clean_area must be None or an int 2 .. 2^30 (pixels; 1 would change nothing), got {area!r}")
+        if not 1 <= classes <= 64:
+            raise StswinHipError(f"clean_area: the model has {classes} classes, hip.labels_clean takes 1 .. 64")
+        if keep is None:
+            keep = ()
+        try:
+            keep = tuple(keep)
+        except TypeError:
+            keep = (keep,)
+        if any(isinstance(c, bool) or not isinstance(c, int) or not 0 <= c <= 63 for c in keep):
+            raise StswinHipError(f"clean_keep holds classes 0 .. 63, got {keep!r}")
+        if isinstance(connectivity, bool) or connectivity not in (4, 8):
+            raise StswinHipError(f"clean_connectivity must be 4 or 8, got {connectivity!r}")
+        if isinstance(max_small, bool) or not isinstance(max_small, int) or not 1 <= max_small <= 65536:
+            raise StswinHipError(f"clean_max must be an int 1 .. 65536, got {max_small!r}")
+        self.device, self.classes = device, classes
+        self.area, self.keep, self.connectivity, self.max_small = area, keep, connectivity, max_small
+        self.ws = None
+        self.retired = []
+        self.log = DeviceLog(device, dict(stats=((2,), torch.int32)))
+
+    def clean(self, labels: torch.Tensor):
+        """labels [B][H][W] -> (the cleaned labels, stats int32 [B][2]): no allocation but the outputs, no synchronisation."""
+        need = hip.labels_clean_scratch(*labels.shape, self.classes, self.max_small)
+        if self.ws is None or self.ws.numel() < need:
+            if self.ws is not None:
+                self.retired.append(self.ws)
+            self.ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return hip.labels_clean(labels, self.classes, self.area, self.connectivity, self.keep, self.max_small, workspace=self.ws)
+
+    def released(self, frames: Sequence[int], stats: torch.Tensor) -> None:
+        """The clips of `frames` are released: their stats rows [B][2] into the log (a device copy each)."""
+        for b, g in enumerate(frames):
+            self.log.append(g, stats=stats[b:b + 1])
+
+    def report(self) -> CleanReport:
+        cols, sequences, frames = self.log.download("stats")
+        return CleanReport(cols["stats"], frames, sequences, self.max_small)
 
 
 class Yield(namedtuple("Yield", "moments rows total ids started runs count conf class_sums instance_sums parts contacts",
