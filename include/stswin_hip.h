@@ -812,6 +812,43 @@ int stswin_instance_parts(const unsigned char* labels /*[n][H][W]*/, const int* 
 /* the geometry of stswin_instance_parts (the tests place their shapes around it): which = 0: the tile's height (32), 1: its width
  * (128), 2: the slots of the on-chip table (64); anything else: -1. */
 int stswin_instance_parts_geometry(int which);
+/* ---- clearance of the instances (stswincl_amd/utils/instruments.py instance_clearance, VideoSegmenter(clearance=...)): how near an
+ * instance comes to what it does not touch.  labels uint8 [n][H][W] and components int32 [n][H][W] as for stswin_instance_parts ->
+ * out int64 [n][K][nc][3].  For frame f, ordinal i < K and class c < nc, with I the pixels of components == i and Q those of labels == c:
+ *   out[f][i][c] = (d2, p, q): d2 the smallest squared Euclidean pixel distance between a pixel of I and a pixel of Q; p = y W + x the
+ *       smallest raster index among the pixels of I that reach d2; q the smallest raster index among the pixels of Q at d2 from p;
+ *   out[f][i][c] = (-1, -1, -1) where I is empty, bit c of target_mask is clear, Q is empty, instance i itself holds a pixel of class
+ *       c (an own class: with grouped components an arm's shaft, wrist and clasper; a plane per class cannot leave an instance's own
+ *       pixels out, so the distance between two instances of one class is not measured), or max_d2 >= 0 and d2 > max_d2.
+ * Ordinals -1 and >= K are nobody's, labels >= nc are nowhere.  max_d2 = -1: no limit.  out is written in full by the call (by the last
+ * launch; nothing needs clearing beforehand, a second call overwrites).  workspace: caller-owned, 8-byte aligned, >=
+ * stswin_instance_clearance_scratch(n, H, W, nc, K) = 8 n (S W + 1 + K nc + K) + n H W (2 nc + 1) bytes with S = ceil(H / 64) (the
+ * segment table uint64 [n][S][W] and the maps' classes uint64 [n] of stswin_boundary_counts; the keys uint64 [n][K][nc]; the classes
+ * each instance holds, uint64 [n][K]; the column distances uint16 [n][nc][H][W]; the contour codes uint8 [n][H][W]); nothing in it needs
+ * clearing (fill kernel on the stream, no memset node) and nothing survives the call.  Six launches whatever nc, K and the maps hold -
+ * fill; mark the contours of the target classes and the classes each instance holds; classes per segment and column distances, the
+ * two kernels of stswin_boundary_counts over n maps; query: every pixel of an instance with a 4-neighbour of another ordinal or
+ * outside the image (a nearest pixel always is one) searches the plane of every present target class its instance does not hold,
+ * bounded by the pair found so far (alone up to 8 columns, then the wave for one pixel at a time or for the whole row at once), and lowers the 64-bit key d2 2^28 + p by an atomic minimum; resolve: a wave per (f, i, c) finds q
+ * on the circle of radius^2 d2 around p - no synchronisation, no allocation, no host read (graph-capturable); no kernel waits on
+ * another workgroup.  Integer arithmetic and integer atomics only (or, min): exact, independent of the order (bit-reproducible); float
+ * square roots only seed integer roots, integer comparisons decide them.  components 4-byte and out 8-byte aligned, labels at any
+ * address, any W; 1 <= H, W <= 16384 (d2 < 2^30, p < 2^28), 1 <= nc <= 64, 1 <= K <= 1024.  The buffers must not overlap (the host
+ * wrapper checks).
+ * Errors, before anything is launched: -1920 n, H or W <= 0, or H or W > 16384 (or more workgroups than a grid holds; also what
+ * stswin_instance_clearance_scratch returns for such a shape); -1921 labels, components, out or workspace NULL; -1922 nc outside 1 ..
+ * 64 and -1923 K outside 1 .. 1024 (both from stswin_instance_clearance_scratch too); -1924 workspace_bytes too small or workspace not
+ * 8-byte aligned; -1925 components not 4-byte or out not 8-byte aligned; -1926 max_d2 < -1. */
+long stswin_instance_clearance_scratch(int n, int H, int W, int nc, int K);
+int stswin_instance_clearance(const unsigned char* labels /*[n][H][W]*/, const int* components /*[n][H][W]*/,
+                              long long* out /*[n][K][nc][3]*/, int n, int H, int W, int nc, int K, long target_mask, long max_d2,
+                              void* workspace, long workspace_bytes, void* stream);
+/* the geometry of stswin_instance_clearance (the tests place their shapes around it): which = 0 .. 3: what stswin_boundary_geometry
+ * gives (the query tile 16 x 64, the columns of a workgroup and the rows of a segment of the column pass, 64 and 64); 4: the columns
+ * a lane searches to each side on its own before the wave searches together, 64 columns a step (8); 5: the pixels of a row the near
+ * search may leave over for the wave to take one by one (2) - more of them search at once, each column loaded once for all;
+ * anything else: -1. */
+int stswin_instance_clearance_geometry(int which);
 /* ---- the label map cleaned: specks out, small holes filled (stswincl_amd/utils/instruments.py clean_labels states the result bit
  * for bit; VideoSegmenter(clean_area=A)).  labels uint8 [n][H][W] -> out uint8 [n][H][W], stats int32 [n][2].
  *   The components of every class c < nc, nothing skipped, under `connectivity` 4 or 8, are those of stswin_label_components; pixels

@@ -4012,6 +4012,273 @@ extern "C" int stswin_boundary_counts(const long long* gt, const unsigned char* 
   return 0;
 }
 
+// Clearance of the instances (stswincl_amd/utils/instruments.py, instance_clearance, states the result; VideoSegmenter(clearance=...)):
+// per instance ordinal i < K and target class c that the instance does not hold itself, the smallest squared Euclidean distance d2
+// between a pixel p of the instance and a pixel q of the class, with the first such p and, for it, the first such q in raster order.
+// Six launches whatever nc, K and the maps hold, the two in the middle being the boundary scores' own, over n maps instead of 2 n:
+//   1 clr_fill_kernel     keys uint64 [n][K][nc] all ones (no pair yet), own uint64 [n][K] and present uint64 [n] zero
+//   2 clr_mark_kernel     labels -> the code map uint8 [n][H][W] (bnd_code: the pixel's class where it is a contour pixel of a target
+//                         class, BND_NONE elsewhere) and own[f][i], the classes instance i holds, one bit each.  The bit is set from
+//                         the first pixel of every horizontal run of equal (ordinal, class) - every class an instance holds starts
+//                         such a run, whatever the ordinals have to do with the labels - and only where it is not set yet
+//   3 bnd_mask_kernel, 4 bnd_column_kernel   as they stand: the planes g uint16 [n][nc][H][W] of the target classes
+//   5 clr_query_kernel    bnd_query_kernel's tiling.  A pixel p of ordinal i in 0 .. K-1 takes part when a 4-neighbour has another
+//                         ordinal or lies outside the image.  That loses nothing: were all four neighbours of a minimising p in the
+//                         instance, the one a step towards q (along the axis of the larger |p - q| component; q != p because the
+//                         instance holds no pixel of the class) would be of the instance and strictly nearer to q.  The same step
+//                         taken from q shows that the nearest pixel of the class is a contour pixel of it, so the planes, which hold
+//                         the contours only, give every p outside the class its exact distance to the class.  Per present target
+//                         class c outside own[f][i] the search of bnd_query_kernel runs under the bound min(d2 of the current key,
+//                         max_d2) + 1 - a distance equal to the key's still counts, its p may be the smaller one; a stale, larger
+//                         key only costs columns - and what it finds below the bound goes into the key d2 << 28 | p by a 64-bit
+//                         atomicMin (d2 < 2^30, p < 2^28): the smallest d2, and among its pixels the smallest p, in any order.
+//                         Where the near search leaves more than CLR_SOLO pixels of a row over (a horizontal stretch of border far
+//                         from the class), the row searches at once instead of pixel by pixel: the same minimum, each column
+//                         loaded once for all of them and dropped for all when its g^2 cannot lower the worst of them
+//   6 clr_resolve_kernel  a wave per (f, i, c): no key -> three -1; else over the rows y + dy, |dy| <= floor(sqrt(d2)), with d2 - dy^2
+//                         a perfect square dx^2, the pixels (y + dy, x -+ dx) with labels == c, the smallest index by a wave minimum
+// Integer arithmetic and integer atomics (or, min) only; the float root only seeds the integer root, comparisons decide it.  No kernel
+// uses scratch memory or waits on another workgroup.
+#define CLR_P_BITS 28
+#define CLR_NO_KEY (~0ull)
+#define CLR_SOLO 2                      // up to that many pixels of a row left over by the near search are searched for one by one
+
+__global__ __launch_bounds__(BND_THREADS) void clr_fill_kernel(unsigned long long* __restrict__ keys, long nkeys,
+                                                               unsigned long long* __restrict__ own, long nown,
+                                                               unsigned long long* __restrict__ present, int maps) {
+  const long i = (long)blockIdx.x * BND_THREADS + threadIdx.x;
+  if (i < maps) present[i] = 0ull;                                        // (bnd_mask_kernel gathers into them)
+  if (i < nown) own[i] = 0ull;
+  if (i < nkeys) keys[i] = CLR_NO_KEY;
+}
+
+__global__ __launch_bounds__(BND_THREADS) void clr_mark_kernel(const unsigned char* __restrict__ labels, const int* __restrict__ comp,
+                                                               unsigned char* __restrict__ codes, unsigned long long* own, long pixels,
+                                                               int H, int W, int nc, int K, unsigned long long skip) {
+  const long i = (long)blockIdx.x * BND_THREADS + threadIdx.x;           // (f, y, x)
+  if (i >= pixels) return;
+  const long hw = (long)H * W;
+  const long f = i / hw, r = i - f * hw;
+  const int y = (int)(r / W), x = (int)(r - (long)y * W);
+  codes[i] = (unsigned char)bnd_code(labels + f * hw, y, x, H, W, nc, skip);
+  const int o = comp[i];
+  const unsigned v = labels[i];
+  if (o < 0 || o >= K || v >= (unsigned)nc) return;
+  if (x > 0 && comp[i - 1] == o && labels[i - 1] == v) return;            // not the first pixel of its run
+  unsigned long long* w = own + f * K + o;
+  if (!(__hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> v & 1ull)) atomicOr(w, 1ull << v);
+}
+
+// grid: (frame f, tile row, tile column), the tile column fastest
+__global__ __launch_bounds__(BND_THREADS) void clr_query_kernel(const int* __restrict__ comp, const unsigned short* __restrict__ g,
+                                                                const unsigned long long* __restrict__ present,
+                                                                const unsigned long long* __restrict__ own, unsigned long long* keys,
+                                                                int H, int W, int nc, int K, unsigned long long targets, int limit,
+                                                                int tx, int ty) {
+  unsigned b = blockIdx.x;
+  const int bx = (int)(b % (unsigned)tx);
+  b /= (unsigned)tx;
+  const int by = (int)(b % (unsigned)ty);
+  const long f = (long)(b / (unsigned)ty);
+  const unsigned long long there = present[f] & targets;                  // the target classes the map has a pixel of
+  if (!there) return;
+  const long hw = (long)H * W;
+  const int* cf = comp + f * hw;
+  const unsigned short* planes = g + f * nc * hw;
+  const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;   // BND_TW is the wave's width: a wave owns rows of the tile
+  const int x = bx * BND_TW + lane;
+  for (int yy = wave; yy < BND_TH; yy += BND_THREADS / 64) {
+    const int y = by * BND_TH + yy;
+    if (y >= H) break;                                                    // (the whole wave)
+    int ord = -1;                                                         // the ordinal of a pixel that takes part, else -1
+    if (x < W) {
+      const int* p = cf + (long)y * W + x;
+      const int o = *p;
+      if (o >= 0 && o < K &&
+          (y == 0 || y == H - 1 || x == 0 || x == W - 1 || p[-W] != o || p[W] != o || p[-1] != o || p[1] != o))
+        ord = o;
+    }
+    if (!__ballot(ord >= 0)) continue;
+    const unsigned long long held = ord >= 0 ? own[f * K + ord] : ~0ull;
+    unsigned long long* kp = keys + (f * K + max(ord, 0)) * nc;
+    const unsigned long long at = (unsigned long long)((long)y * W + x);
+    for (unsigned long long cs = there; cs; cs &= cs - 1) {
+      const int c = __ffsll((long long)cs) - 1;
+      const bool take = ord >= 0 && !(held >> c & 1ull);
+      if (!__ballot(take)) continue;
+      const unsigned short* gr = planes + (long)c * hw + (long)y * W;
+      // every lane searches for its own pixel up to BND_NEAR columns to both sides; that settles the pixel when best <= (BND_NEAR + 1)^2
+      int bound = 0, mine = 0;
+      bool far = false;
+      if (take) {
+        const unsigned long long d = __hip_atomic_load(kp + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> CLR_P_BITS;
+        bound = (d < (unsigned long long)limit ? (int)d : limit) + 1;     // only a d2 < bound is of interest
+        mine = bound;
+        const int g0 = gr[x];
+        if (g0 != (int)BND_FAR) mine = min(mine, g0 * g0);
+        int dx = 1;
+        for (; dx <= BND_NEAR && dx * dx < mine; ++dx) {
+          const int l = x - dx >= 0 ? (int)gr[x - dx] : (int)BND_FAR, r = x + dx < W ? (int)gr[x + dx] : (int)BND_FAR;
+          const int v = min(l, r);
+          if (v != (int)BND_FAR) mine = min(mine, dx * dx + v * v);
+        }
+        far = dx * dx < mine && (x - dx >= 0 || x + dx < W);             // columns from dx on could still be nearer
+      }
+      unsigned long long todo = __ballot(far);
+      if (__popcll(todo) > CLR_SOLO) {
+        // many of the row's pixels are left over: the row searches at once.  Ring k is the 64 columns of the tile (k = 0) or the 64
+        // columns 64 k to the left and to the right of them; a lane loads one column of the ring, and every column that can still
+        // matter to the worst lane (g^2 below the largest best among the lanes left over) is handed to all lanes, one readlane each
+        int bmax = far ? mine : 0;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) bmax = max(bmax, __shfl_xor(bmax, o));
+        const int x0 = bx * BND_TW;
+        for (int k = 0;; ++k) {
+          const int reach = 64 * k - 63;                                  // the smallest |dx| between a lane and a column of ring k >= 1
+          if (k > 0 && (reach * reach >= bmax || (x0 - reach < 0 && x0 + 64 * k >= W))) break;
+          for (int side = 0; side < (k == 0 ? 1 : 2); ++side) {
+            const int cs = side == 0 ? x0 - 64 * k : x0 + 64 * k;
+            const int xc = cs + lane;
+            const int v = xc >= 0 && xc < W ? (int)gr[xc] : (int)BND_FAR;
+            const int v2 = v == (int)BND_FAR ? BND_INF : v * v;
+            unsigned long long m = __ballot(v2 < bmax);
+            while (m) {
+              const int j = __ffsll((long long)m) - 1;
+              m &= m - 1;
+              const int dx = x - (cs + j);
+              mine = min(mine, __mul24(dx, dx) + __builtin_amdgcn_readlane(v2, j));
+            }
+          }
+          bmax = far ? mine : 0;
+#pragma unroll
+          for (int o = 32; o > 0; o >>= 1) bmax = max(bmax, __shfl_xor(bmax, o));
+        }
+        todo = 0;
+      }
+      while (todo) {                                                      // few: one after the other, the wave searches together
+        const int i = __ffsll((long long)todo) - 1;
+        todo &= todo - 1;
+        const int xp = bx * BND_TW + i;
+        int best = __shfl(mine, i);
+        for (int base = BND_NEAR + 1;; base += 64) {                      // lane l takes the columns xp - dx and xp + dx, dx = base + l
+          const int dx = base + lane;
+          const int l = xp - dx >= 0 ? (int)gr[xp - dx] : (int)BND_FAR, r = xp + dx < W ? (int)gr[xp + dx] : (int)BND_FAR;
+          const int v = min(l, r);
+          int cand = v == (int)BND_FAR ? BND_INF : dx * dx + v * v;
+#pragma unroll
+          for (int o = 32; o > 0; o >>= 1) cand = min(cand, __shfl_xor(cand, o));
+          best = min(best, cand);
+          const int nb = base + 64;                                       // every column further out has dx >= nb
+          if (nb * nb >= best || (xp - nb < 0 && xp + nb >= W)) break;
+        }
+        if (lane == i) mine = best;
+      }
+      if (take && mine < bound) atomicMin(kp + c, (unsigned long long)mine << CLR_P_BITS | at);
+    }
+  }
+}
+
+// the largest k with k k <= d2 (d2 < 2^30): the float root seeds, integer comparisons decide
+__device__ __forceinline__ int clr_floor_sqrt(int d2) {
+  int k = (int)sqrtf((float)d2);
+  while (k * k > d2) --k;
+  while ((k + 1) * (k + 1) <= d2) ++k;
+  return k;
+}
+
+// a wave per entry e = (f, i, c) of the keys; a workgroup takes BND_THREADS / 64 of them
+__global__ __launch_bounds__(BND_THREADS) void clr_resolve_kernel(const unsigned char* __restrict__ labels,
+                                                                  const unsigned long long* __restrict__ keys,
+                                                                  long long* __restrict__ out, long entries, int H, int W, int nc, int K) {
+  const long e = (long)blockIdx.x * (BND_THREADS / 64) + (threadIdx.x >> 6);
+  if (e >= entries) return;                                               // (the whole wave)
+  const int lane = (int)threadIdx.x & 63;
+  const unsigned long long key = keys[e];
+  long long* o = out + 3 * e;
+  if (key == CLR_NO_KEY) {
+    if (lane < 3) o[lane] = -1;
+    return;
+  }
+  const unsigned c = (unsigned)(e % nc);
+  const unsigned char* lab = labels + e / ((long)K * nc) * H * W;
+  const int d2 = (int)(key >> CLR_P_BITS), p = (int)(key & ((1ull << CLR_P_BITS) - 1));
+  const int y = p / W, x = p - y * W;
+  const int R = clr_floor_sqrt(d2);
+  int q = BND_INF;
+  for (int t = lane; t <= 2 * R; t += 64) {
+    const int dy = t - R, yq = y + dy;
+    if (yq < 0 || yq >= H) continue;
+    const int rem = d2 - dy * dy, dx = clr_floor_sqrt(rem);
+    if (dx * dx != rem) continue;
+    const unsigned char* row = lab + (long)yq * W;
+    if (x + dx < W && row[x + dx] == c) q = min(q, yq * W + x + dx);
+    if (x - dx >= 0 && row[x - dx] == c) q = min(q, yq * W + x - dx);
+  }
+#pragma unroll
+  for (int s = 32; s > 0; s >>= 1) q = min(q, __shfl_xor(q, s));
+  if (lane == 0) {
+    o[0] = d2;
+    o[1] = p;
+    o[2] = q;
+  }
+}
+
+extern "C" int stswin_instance_clearance_geometry(int which) {
+  return which == 4 ? BND_NEAR : which == 5 ? CLR_SOLO : stswin_boundary_geometry(which);
+}
+
+extern "C" long stswin_instance_clearance_scratch(int n, int H, int W, int nc, int K) {
+  if (n <= 0 || H <= 0 || W <= 0 || H > 16384 || W > 16384) return -1920;
+  if (nc < 1 || nc > 64) return -1922;
+  if (K < 1 || K > 1024) return -1923;
+  const long S = (H + BND_SEG - 1) / BND_SEG;
+  // the table uint64 [n][S][W], the maps' classes uint64 [n], the keys uint64 [n][K][nc], the instances' classes uint64 [n][K], the
+  // planes uint16 [n][nc][H][W], the codes uint8 [n][H][W]
+  return 8 * (long)n * (S * W + 1 + (long)K * nc + K) + (long)n * H * W * (2 * (long)nc + 1);
+}
+
+extern "C" int stswin_instance_clearance(const unsigned char* labels, const int* components, long long* out, int n, int H, int W, int nc,
+                                         int K, long target_mask, long max_d2, void* workspace, long workspace_bytes, void* stream) {
+  if (n <= 0 || H <= 0 || W <= 0 || H > 16384 || W > 16384) return -1920;
+  if (labels == nullptr || components == nullptr || out == nullptr || workspace == nullptr) return -1921;
+  if (nc < 1 || nc > 64) return -1922;
+  if (K < 1 || K > 1024) return -1923;
+  if (workspace_bytes < stswin_instance_clearance_scratch(n, H, W, nc, K) || ((uintptr_t)workspace & 7)) return -1924;
+  if (((uintptr_t)components & 3) || ((uintptr_t)out & 7)) return -1925;
+  if (max_d2 < -1) return -1926;
+  const long pixels = (long)n * H * W, nkeys = (long)n * K * nc, nown = (long)n * K;
+  const int bands = (W + BND_COLS - 1) / BND_COLS, tx = (W + BND_TW - 1) / BND_TW, ty = (H + BND_TH - 1) / BND_TH;
+  const int S = (H + BND_SEG - 1) / BND_SEG;
+  const long fill_blocks = (nkeys + BND_THREADS - 1) / BND_THREADS, mark_blocks = (pixels + BND_THREADS - 1) / BND_THREADS;
+  const long mask_blocks = (long)n * S * bands, col_blocks = mask_blocks * nc, query_blocks = (long)n * tx * ty;
+  const long resolve_blocks = (nkeys + BND_THREADS / 64 - 1) / (BND_THREADS / 64);
+  if (fill_blocks > 0x7fffffffL || mark_blocks > 0x7fffffffL || col_blocks > 0x7fffffffL || query_blocks > 0x7fffffffL ||
+      resolve_blocks > 0x7fffffffL)
+    return -1920;
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned long long all = nc == 64 ? ~0ull : (1ull << nc) - 1;
+  const unsigned long long targets = (unsigned long long)target_mask & all;
+  const int limit = max_d2 < 0 || max_d2 > (1L << 30) ? 1 << 30 : (int)max_d2;            // every d2 is < 2^30
+  unsigned long long* table = reinterpret_cast<unsigned long long*>(workspace);
+  unsigned long long* present = table + (long)n * S * W;
+  unsigned long long* keys = present + n;
+  unsigned long long* own = keys + nkeys;
+  unsigned short* g = reinterpret_cast<unsigned short*>(own + nown);
+  unsigned char* codes = reinterpret_cast<unsigned char*>(g) + 2 * pixels * nc;
+  hipLaunchKernelGGL(clr_fill_kernel, dim3((unsigned)fill_blocks), dim3(BND_THREADS), 0, st, keys, nkeys, own, nown, present, n);
+  hipLaunchKernelGGL(clr_mark_kernel, dim3((unsigned)mark_blocks), dim3(BND_THREADS), 0, st, labels, components, codes, own, pixels, H, W,
+                     nc, K, ~targets);
+  hipLaunchKernelGGL(bnd_mask_kernel, dim3((unsigned)mask_blocks), dim3(BND_COLS), 0, st, (const unsigned char*)codes, table, present, H, W, S, bands);
+  hipLaunchKernelGGL(bnd_column_kernel, dim3((unsigned)col_blocks), dim3(BND_COLS), 0, st, (const unsigned char*)codes,
+                     (const unsigned long long*)table, g, H, W, nc, S, bands, ~targets);
+  hipLaunchKernelGGL(clr_query_kernel, dim3((unsigned)query_blocks), dim3(BND_THREADS), 0, st, components, (const unsigned short*)g,
+                     (const unsigned long long*)present, (const unsigned long long*)own, keys, H, W, nc, K, targets, limit, tx, ty);
+  hipLaunchKernelGGL(clr_resolve_kernel, dim3((unsigned)resolve_blocks), dim3(BND_THREADS), 0, st, labels,
+                     (const unsigned long long*)keys, out, nkeys, H, W, nc, K);
+  STSWIN_CHECK_LAUNCH();
+  return 0;
+}
+
 // Frames as a video source delivers them (stswincl_amd/utils/yuv.py states the arithmetic): NV12 or UYVY -> the HWC RGB frame that
 // stswin_frame_ingest and stswin_labels_overlay read, and RGB -> NV12.  matrix int32 [3][4]: out_c = clamp((m[c][0] t0 + m[c][1] t1 +
 // m[c][2] t2 + m[c][3]) >> 14, 0, 255) in int32 (|sum| < 2^25).  A thread owns YUV_PPT = 8 (wide body) or 2 (byte body) consecutive

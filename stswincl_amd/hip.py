@@ -1972,6 +1972,104 @@ def instance_parts(labels: torch.Tensor, components: torch.Tensor, K: int, nc: i
     return tuple(out)
 
 
+def instance_clearance_geometry():
+    """(rows, columns of the tile a workgroup of the query pass owns, columns of a workgroup and rows of a segment of the column pass,
+    columns a lane searches to each side before the wave searches together, 64 a step, pixels of a row the wave still takes one by
+    one) of hip.instance_clearance (stswin_instance_clearance_geometry)."""
+    geo = load().stswin_instance_clearance_geometry
+    return tuple(int(geo(i)) for i in range(6))
+
+
+def instance_clearance_scratch(n: int, H: int, W: int, nc: int, K: int) -> int:
+    """Bytes of workspace hip.instance_clearance needs for maps [n][H][W] of nc classes and K instances:
+    8 n (ceil(H / 64) W + 1 + K nc + K) + n H W (2 nc + 1)."""
+    for what, v in (("n", n), ("H", H), ("W", W), ("nc", nc), ("K", K)):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise StswinHipError(f"instance_clearance: {what} must be an int, got {v!r}")
+    b = int(load().stswin_instance_clearance_scratch(n, H, W, nc, K))
+    if b == -1922:
+        raise StswinHipError(f"instance_clearance: nc = {nc!r} classes, the kernel takes 1 .. 64")
+    if b == -1923:
+        raise StswinHipError(f"instance_clearance: K must be an int 1 .. 1024, got {K!r}")
+    if b < 0:
+        raise StswinHipError(f"instance_clearance: {n} maps of {H} x {W}, the kernel takes up to 16384 x 16384")
+    return b
+
+
+def instance_clearance(labels: torch.Tensor, components: torch.Tensor, K: int, nc: int, targets=None, max_distance: Optional[int] = None,
+                       out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint8 labels [n][H][W] and int32 components [n][H][W] (hip.label_components' map, -1 = none) -> int64 [n][K][nc][3]: per frame,
+    instance ordinal i < K and class c < nc the triple (d2, p, q) - d2 the smallest squared Euclidean pixel distance between a pixel
+    with components == i and a pixel with labels == c, p = y W + x the first pixel of the instance in raster order that reaches it, q
+    the first pixel of the class at that distance from p - or (-1, -1, -1) where the instance or the class is empty, c is not in
+    `targets` (default: every class), the instance itself holds a pixel of class c (own classes are not measured) or d2 >
+    max_distance^2.  Ordinals -1 and >= K are nobody's, labels >= nc are nowhere (utils.instruments.instance_clearance is the numpy
+    definition, matched bit for bit).  out: written in full, a second call overwrites; workspace: uint8, 8-byte aligned, >=
+    instance_clearance_scratch(n, H, W, nc, K) bytes.  With both given the call allocates nothing, and it never synchronises
+    (graph-capturable).  Six launches.  Returns out (include/stswin_hip.h, stswin_instance_clearance)."""
+    if not isinstance(labels, torch.Tensor) or labels.dtype != torch.uint8 or labels.dim() != 3 or not labels.is_contiguous():
+        raise StswinHipError(f"instance_clearance: labels must be contiguous uint8 [n][H][W], got {_got(labels)}")
+    if (not isinstance(components, torch.Tensor) or components.dtype != torch.int32 or components.shape != labels.shape
+            or not components.is_contiguous()):
+        raise StswinHipError(f"instance_clearance: components must be contiguous int32 {tuple(labels.shape)} as the labels are, got "
+                             f"{_got(components)}")
+    if not labels.is_cuda or not components.is_cuda:
+        raise StswinHipError("instance_clearance: labels and components must be on the GPU (no CPU path exists; "
+                             "utils.instruments.instance_clearance is the numpy definition)")
+    if components.device != labels.device:
+        raise StswinHipError(f"instance_clearance: components must be on {labels.device} as the labels are, got {components.device}")
+    n, H, W = labels.shape
+    if n <= 0 or H <= 0 or W <= 0:
+        raise StswinHipError(f"instance_clearance: empty labels {tuple(labels.shape)}")
+    if H > 16384 or W > 16384:
+        raise StswinHipError(f"instance_clearance: a {H} x {W} map, the kernel takes up to 16384 x 16384")
+    if isinstance(K, bool) or not isinstance(K, int) or not 1 <= K <= 1024:
+        raise StswinHipError(f"instance_clearance: K must be an int 1 .. 1024, got {K!r}")
+    if isinstance(nc, bool) or not isinstance(nc, int) or not 1 <= nc <= 64:
+        raise StswinHipError(f"instance_clearance: nc = {nc!r} classes, the kernel takes 1 .. 64")
+    if targets is None:
+        targets = range(nc)
+    try:
+        targets = tuple(targets)
+    except TypeError:
+        targets = (targets,)
+    if any(isinstance(c, bool) or not isinstance(c, int) or not 0 <= c < nc for c in targets):
+        raise StswinHipError(f"instance_clearance: targets holds classes 0 .. {nc - 1}, got {targets!r}")
+    if max_distance is not None and (isinstance(max_distance, bool) or not isinstance(max_distance, int) or max_distance < 0):
+        raise StswinHipError(f"instance_clearance: max_distance must be None or an int >= 0 (pixels), got {max_distance!r}")
+    dev = labels.device
+    shape = (n, K, nc, 3)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.int64, device=dev)
+    elif not isinstance(out, torch.Tensor) or out.dtype != torch.int64 or tuple(out.shape) != shape or not out.is_contiguous() or out.device != dev:
+        raise StswinHipError(f"instance_clearance: out must be contiguous int64 [{n}][{K}][{nc}][3] on {dev}, got {_got(out)}")
+    need = instance_clearance_scratch(n, H, W, nc, K)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.dim() != 1 or not workspace.is_contiguous()
+          or workspace.device != dev):
+        raise StswinHipError(f"instance_clearance: workspace must be contiguous uint8 [bytes] on {dev}, got {_got(workspace)}")
+    elif workspace.numel() < need:
+        raise StswinHipError(f"instance_clearance: a workspace of {workspace.numel()} bytes, {n} maps of {H} x {W}, {nc} classes and {K} "
+                             f"instances need {need}")
+    elif workspace.data_ptr() % 8:
+        raise StswinHipError("instance_clearance: workspace must be 8-byte aligned")
+    bufs = (("labels", labels), ("components", components), ("out", out), ("workspace", workspace))
+    for i, (wa, a) in enumerate(bufs[:3]):
+        for wb, b in bufs[max(i + 1, 2):]:
+            if _same_memory(a, b):
+                raise StswinHipError(f"instance_clearance: {wb} shares memory with {wa}")
+    mask = 0
+    for c in targets:
+        mask |= 1 << c
+    if mask >= 1 << 63:                      # (the mask travels in a C long: bit 63 is its sign bit)
+        mask -= 1 << 64
+    max_d2 = -1 if max_distance is None else min(max_distance * max_distance, 1 << 30)       # (every d2 is < 2^30)
+    _check(load().stswin_instance_clearance(_p(labels), _p(components), _p(out), n, H, W, nc, K, mask, max_d2, _p(workspace),
+                                            workspace.numel(), _stream()), "instance_clearance")
+    return out
+
+
 def labels_clean_geometry():
     """(vote tile height, vote tile width, raster chunk of the numbering pass, slots of the on-chip vote table) of hip.labels_clean
     (stswin_labels_clean_geometry)."""

@@ -20,7 +20,9 @@ matching on intersection over union in integers, and TrackReport reads the ids b
 group_table maps the classes that are parts of one instrument (shaft, wrist, clasper) to one representative, so that the components of
 the grouped labels are whole instruments (VideoSegmenter(instance_groups=...)); instance_parts says per instance and class what it
 is made of (the ten integers again) and how many pixel edges it shares with each class outside itself (hip.instance_parts,
-VideoSegmenter(parts=...)), and PartsReport reads both beside the instance and track reports.
+VideoSegmenter(parts=...)), and PartsReport reads both beside the instance and track reports.  instance_clearance says how near an
+instance comes to each class it does not hold - the exact squared distance and the two pixels that realise it (hip.instance_clearance,
+VideoSegmenter(clearance=...)) - and ClearanceReport reads it the same way.
 
 clean_labels states what hip.labels_clean writes (VideoSegmenter(clean_area=A)): the label map with its small components relabelled by
 the vote of their stable neighbours - specks out, small holes filled - before anything above reads it.
@@ -836,5 +838,149 @@ class PartsReport:
                 if self.tracks is not None:
                     row["track"] = int(self.tracks.ids[r, i])
                 row["parts"], row["touches"] = self.parts(r, int(i)), self.touches(r, int(i))
+                out.append(row)
+        return out
+
+
+def instance_clearance(labels, components, K: int, nc: int, targets=None, max_distance=None) -> np.ndarray:
+    """Integer labels [n][H][W] and components [n][H][W] (label_components' map, -1 = none; or one [H][W] each) -> int64
+    [n][K][nc][3]: how near each instance comes to each class, what hip.instance_clearance gives bit for bit.
+
+    For frame f, ordinal i < K and class c < nc, with I the pixels of components == i and Q the pixels of labels == c, the entry is
+    (d2, p, q): d2 the smallest squared Euclidean pixel distance between a pixel of I and a pixel of Q, p = y W + x the smallest raster
+    index among the pixels of I that reach d2, q the smallest raster index among the pixels of Q at squared distance d2 from p.  It is
+    (-1, -1, -1) where I is empty, c is not in `targets` (default: every class 0 .. nc - 1), Q is empty, instance i itself holds a
+    pixel of class c, or max_distance = r is given and d2 > r^2.  Ordinals -1 and >= K are nobody's, labels >= nc are nowhere, as in
+    instance_parts.
+
+    Own classes are left out on purpose: the kernels measure against one plane of distances per class, and a plane cannot leave out
+    the instance's own pixels, so the distance between two instruments of one class is not measured here.  With instance_groups an
+    arm's own shaft, wrist and clasper are its own classes; everything else is measured.
+
+    Only contour pixels are compared (boundary.contour, of the instance's mask and of the class's): were a pixel of a nearest pair
+    surrounded by its own set, its neighbour a step towards the other pixel would be nearer."""
+    from .boundary import contour, nearest_d2
+    lab, comp = np.asarray(labels), np.asarray(components)
+    if lab.ndim == 2 and comp.ndim == 2:
+        lab, comp = lab[None], comp[None]
+    if lab.ndim != 3 or lab.dtype.kind not in "iu" or min(lab.shape) < 1:
+        raise ValueError(f"instance_clearance: labels are integers [n][H][W], got {lab.dtype} {lab.shape}")
+    if comp.shape != lab.shape or comp.dtype.kind not in "iu":
+        raise ValueError(f"instance_clearance: components are integers {lab.shape} as the labels are, got {comp.dtype} {comp.shape}")
+    if isinstance(K, bool) or int(K) != K or not 1 <= K <= 1024:
+        raise ValueError(f"instance_clearance: K is 1 .. 1024, got {K!r}")
+    if isinstance(nc, bool) or int(nc) != nc or not 1 <= nc <= 64:
+        raise ValueError(f"instance_clearance: 1 .. 64 classes, got {nc!r}")
+    if targets is None:
+        targets = range(nc)
+    try:
+        targets = sorted({int(c) for c in targets})
+    except TypeError:
+        raise ValueError(f"instance_clearance: targets holds classes 0 .. {nc - 1}, got {targets!r}") from None
+    if any(not 0 <= c < nc for c in targets):
+        raise ValueError(f"instance_clearance: targets holds classes 0 .. {nc - 1}, got {targets!r}")
+    if max_distance is not None and (isinstance(max_distance, bool) or int(max_distance) != max_distance or max_distance < 0):
+        raise ValueError(f"instance_clearance: max_distance is None or an int >= 0, got {max_distance!r}")
+    n, H, W = lab.shape
+    lab, comp = lab.astype(np.int64), comp.astype(np.int64)
+    out = np.full((n, K, nc, 3), -1, dtype=np.int64)
+    for f in range(n):
+        there = {c: np.argwhere(contour(lab[f] == c)) for c in targets}                  # (argwhere lists in raster order)
+        there = {c: pts for c, pts in there.items() if len(pts)}
+        owned = (comp[f] >= 0) & (comp[f] < K)
+        for i in np.unique(comp[f][owned]) if there else ():
+            inside = comp[f] == i
+            own = set(np.unique(lab[f][inside]).tolist())
+            mine = np.argwhere(contour(inside))
+            for c, pts in there.items():
+                if c in own:
+                    continue
+                d = nearest_d2(mine, pts)
+                k = int(np.argmin(d))                                                     # the first of the smallest: the smallest index
+                if max_distance is not None and d[k] > int(max_distance) ** 2:
+                    continue
+                e = ((pts - mine[k]) ** 2).sum(axis=1)
+                j = int(np.argmin(e))
+                out[f, i, c] = d[k], mine[k, 0] * W + mine[k, 1], pts[j, 0] * W + pts[j, 1]
+    return out
+
+
+class ClearanceReport:
+    """How near the instances come to what they do not touch (hip.instance_clearance, VideoSegmenter(clearance="deferred")
+    .clearance_report()), per row-frame r, instance ordinal i < K and class c, from clearance int64 [rows][K][nc][3], the triples
+    (d2, p, q) of instance_clearance, (-1, -1, -1) where nothing is measured:
+
+      measured bool    [rows][K][nc]     a distance exists
+      d2       int64   [rows][K][nc]     the squared distance in pixels, -1 where none
+      p, q     int64   [rows][K][nc]     the raster indices y W + x of the instance's pixel and of the class's, -1 where none
+
+    distance(r, i) gives class -> sqrt(d2) for the measured classes, nearest(r, i, c) the two pixels ((y, x), (y, x)).
+    instances / tracks: the InstanceReport and TrackReport of the same rows (None: none); as_rows() then lists the present instances
+    with their class and track.  frames / sequences / names as InstrumentReport's."""
+
+    def __init__(self, clearance, size: Sequence[int], names: Optional[Sequence[str]] = None, frames: Optional[Sequence[int]] = None,
+                 sequences: Optional[Sequence[int]] = None, instances=None, tracks=None):
+        cl = np.asarray(clearance)
+        if cl.ndim == 3:
+            cl = cl[None]
+        if cl.ndim != 4 or cl.shape[3] != 3 or cl.dtype.kind not in "iu":
+            raise ValueError(f"ClearanceReport: clearance is integers [rows][K][nc][3], got {cl.dtype} {cl.shape}")
+        n, K, nc = cl.shape[:3]
+        if names is not None and len(names) != nc:
+            raise ValueError(f"ClearanceReport: {len(names)} names for {nc} classes")
+        for what, v in (("frames", frames), ("sequences", sequences)):
+            if v is not None and len(v) != n:
+                raise ValueError(f"ClearanceReport: {len(v)} {what} for {n} rows")
+        if tracks is not None and instances is None:
+            instances = tracks.report
+        if instances is not None and (len(instances) != n or instances.present.shape[1] != K):
+            raise ValueError(f"ClearanceReport: an instance report of {len(instances)} rows and {instances.present.shape[1]} instances "
+                             f"for {n} rows and {K} instances")
+        H, W = (int(v) for v in size)
+        self.size = (H, W)
+        self.names = list(names) if names is not None else None
+        self.frames = [int(f) for f in frames] if frames is not None else list(range(n))
+        self.sequences = [int(s) for s in sequences] if sequences is not None else [0] * n
+        self.instances, self.tracks = instances, tracks
+        self.clearance = cl.astype(np.int64)
+        self.d2, self.p, self.q = (self.clearance[..., k] for k in range(3))
+        self.measured = self.d2 >= 0
+        if self.measured.any() and (W < 1 or max(self.p.max(), self.q.max()) >= H * W):
+            raise ValueError(f"ClearanceReport: pixel indices up to {max(self.p.max(), self.q.max())} in a frame of {H} x {W}")
+
+    def __len__(self) -> int:
+        return len(self.frames)
+
+    def distance(self, r: int, i: int) -> dict:
+        """class -> the distance in pixels (sqrt of d2) from instance i of row r to the nearest pixel of that class, for the classes
+        measured."""
+        return {int(c): float(np.sqrt(float(self.d2[r, i, c]))) for c in np.nonzero(self.measured[r, i])[0]}
+
+    def nearest(self, r: int, i: int, c: int):
+        """((y, x), (y, x)): the pixel of instance i of row r nearest to class c and the pixel of the class nearest to it; None where
+        nothing is measured."""
+        if not self.measured[r, i, c]:
+            return None
+        W = self.size[1]
+        p, q = int(self.p[r, i, c]), int(self.q[r, i, c])
+        return (p // W, p % W), (q // W, q % W)
+
+    def as_rows(self) -> List[dict]:
+        """One dict per instance, in row order then instance order, for a log: sequence, frame, instance, class (and name) and track
+        where the instance and track reports were given, distance as above and nearest as class -> ((y, x), (y, x)).  With an
+        instance report its present instances are listed, else the instances with a measured class."""
+        out = []
+        some = self.instances.present if self.instances is not None else self.measured.any(axis=2)
+        for r in range(len(self)):
+            for i in np.nonzero(some[r])[0]:
+                row = {"sequence": self.sequences[r], "frame": self.frames[r], "instance": int(i)}
+                if self.instances is not None:
+                    row["class"] = int(self.instances.cls[r, i])
+                    if self.names is not None:
+                        row["name"] = self.names[row["class"]]
+                if self.tracks is not None:
+                    row["track"] = int(self.tracks.ids[r, i])
+                row["distance"] = self.distance(r, int(i))
+                row["nearest"] = {c: self.nearest(r, int(i), c) for c in row["distance"]}
                 out.append(row)
         return out

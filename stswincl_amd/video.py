@@ -195,7 +195,8 @@ class VideoSegmenter:
     """Segment video sequences with an eval-mode TswinPlus, one result per frame, each frame's ResNet features computed once.
 
     seg = VideoSegmenter(model, batch=1, out="logits" | "labels" | "overlay", out_size=None, graph=False, report=None, instances=None,
-                         tracks=False, masks=None, boundary=None, confidence=None, instance_groups=None, parts=None, clean_area=None)
+                         tracks=False, masks=None, boundary=None, confidence=None, instance_groups=None, parts=None, clean_area=None,
+                         clearance=None)
 
     push(frames, gt=None) takes uint8 RGB frames [n][Hs][Ws][3] (or one [Hs][Ws][3]; torch tensor on the model's GPU or the CPU, or
     a numpy array; NV12 or UYVY frames with pixel_format, below) and returns [(frame_index, result), ...] for the frames whose clip is now complete.  finish() runs what is
@@ -394,6 +395,27 @@ class VideoSegmenter:
     joined by row with instance_report() under report="deferred" and with track_report() under tracks=True.  parts=None: every
     result, launch and captured graph is what it is without the keyword.
 
+    clearance="frame" | "deferred" (needs instances=K; with or without instance_groups; both protocols, every scores mode, batch > 1,
+    graph=True and clean_area, whose cleaned map it then reads; clearance_to=None, clearance_max=None): how near each instance comes to
+    what it does not touch - clasper to small intestine, needle driver to kidney, an instrument to the pupil - where contacts of
+    parts= says nothing until the two regions meet.  Wherever hip.instance_parts would run - behind the component launches and before
+    the next clip's components overwrite the map, the scoring paths with ground truth included; nothing depends on the tracker - the
+    six launches of hip.instance_clearance (utils.instruments.instance_clearance states the result) take over the labels (ungrouped)
+    and the chain's component map, per instance ordinal i < K and class c, clearance int64 [K][nc][3] = (d2, p, q): the exact squared
+    Euclidean distance in pixels between the instance and the nearest pixel of the class, and the raster indices y W + x of the two
+    pixels that realise it, the first in raster order; (-1, -1, -1) where the instance or the class is absent, the class is not in
+    clearance_to (a sequence of classes; default all), the distance exceeds clearance_max pixels, or the instance holds a pixel of the
+    class itself: own classes - with instance_groups an arm's shaft, wrist and clasper - are not measured, so neither is the distance
+    between two instruments of one class.  clearance="frame": a result r becomes r + (clearance,) behind whatever report, masks,
+    confidence and parts append, on the device.  Under graph=True the launches are part of the captured steady step, the workspace is
+    the segmenter's own, allocated by the warm-up frames (it only grows, retired ones are kept), and the tensor of the last replayed
+    step of a push is a view of the graph's buffer; with ground truth it is made after the replay.  clearance="deferred": results are
+    unchanged and the tensor goes into the device log; clearance_report(names=None) downloads once and returns
+    utils.instruments.ClearanceReport - distance(r, i) class -> pixels, nearest(r, i, c) the two pixels as ((y, x), (y, x)) - over
+    every frame released since reset_metrics(), in instrument_report()'s order and with its sequence ordinals, joined by row with
+    instance_report() under report="deferred" and with track_report() under tracks=True.  clearance=None: every result, launch and
+    captured graph is what it is without the keyword; clearance_to or clearance_max without it is refused.
+
     clean_area=A (2 .. 2^30 pixels; out="labels" | "overlay", both protocols, every scores mode, batch > 1 and graph=True; a model of 1 ..
     64 classes; clean_keep=None, clean_connectivity=8 | 4, clean_max=4096): the label map cleaned before anything reads it - specks out,
     small holes filled.  Wherever a step's label map is made, the launches of hip.labels_clean (utils.instruments.clean_labels states
@@ -427,7 +449,8 @@ class VideoSegmenter:
                  mask_runs: int = 16384, track_max_gap: int = 0, boundary: Optional[str] = None, boundary_bins: int = 32,
                  boundary_skip: Optional[Sequence[int]] = None, confidence: Optional[str] = None, confidence_low: int = 128,
                  instance_groups=None, parts: Optional[str] = None, clean_area: Optional[int] = None, clean_keep: Optional[Sequence[int]] = None,
-                 clean_connectivity: int = 8, clean_max: int = 4096):
+                 clean_connectivity: int = 8, clean_max: int = 4096, clearance: Optional[str] = None,
+                 clearance_to: Optional[Sequence[int]] = None, clearance_max: Optional[int] = None):
         if out not in ("logits", "labels", "overlay"):
             raise StswinHipError(f"out must be 'logits', 'labels' or 'overlay', got {out!r}")
         if pixel_format not in PIXEL_FORMATS:
@@ -478,7 +501,8 @@ class VideoSegmenter:
         self._score_log = DeviceLog(self.device, {"counts": ((3, classes), torch.int32)})     # scores="deferred": a row per scored frame
         self.chain = ReportChain(self.device, classes, protocol, out, report, min_area, instances, connectivity, instance_skip, tracks,
                                  track_iou, track_same_class, masks, mask_runs, track_max_gap, confidence, confidence_low,
-                                 self.align_corners, parts, instance_groups)
+                                 self.align_corners, parts, instance_groups, clearance, clearance_to, clearance_max)
+        self.clearance, self.clearance_to, self.clearance_max = clearance, self.chain.clearance_to, clearance_max
         self.confidence, self.confidence_low = confidence, confidence_low
         self.parts, self.instance_groups = parts, self.chain.instance_groups
         self.report, self.min_area, self.instances, self.connectivity, self.instance_skip = report, min_area, instances, connectivity, self.chain.instance_skip
@@ -577,7 +601,7 @@ class VideoSegmenter:
     def reset_metrics(self) -> None:
         """Clear what an evaluation pools and reset() keeps: the confusion matrix (protocol="cadis"), the score log and its sequence
         ordinal (scores="deferred"), the instrument log and its ordinal (report="deferred"), the count of unmatched ground-truth
-        pixels (gt_table); masks="deferred", confidence="deferred" and parts="deferred" log into the instrument log; the boundary log
+        pixels (gt_table); masks="deferred", confidence="deferred", parts="deferred" and clearance="deferred" log into the instrument log; the boundary log
         and its ordinal (boundary="deferred"); the log of the cleaning's stats and its ordinal (clean_area)."""
         if self.cleaner is not None:
             self.cleaner.log.clear()
@@ -738,6 +762,30 @@ class VideoSegmenter:
             return PartsReport(cols["parts"], cols["contacts"], size, names, frames, sequences, inst, trk)
         except ValueError as e:
             raise StswinHipError(f"parts_report: {e}") from e
+
+    def clearance_report(self, names: Optional[Sequence[str]] = None):
+        """clearance="deferred": one download of the clearance log -> utils.instruments.ClearanceReport over every frame released since
+        reset_metrics() - per instance the distance to every class measured and the two pixels that realise it - rows ordered by
+        sequence and frame as instrument_report()'s, with its sequence ordinals; with report="deferred" joined by row with
+        instance_report(names), with tracks=True with track_report(names) too."""
+        if self.clearance != "deferred":
+            raise StswinHipError("clearance_report() belongs to clearance='deferred'")
+        if self.tracks and self.chain.parked:
+            raise StswinHipError("clearance_report(): released frames still wait for their predecessors (finish() the sequence first)")
+        from .utils.instruments import ClearanceReport, InstanceReport, TrackReport
+        joined = self.report == "deferred"
+        wanted = ("clearance",) + (("rows", "total") if joined else ()) + (("ids", "started") if joined and self.tracks else ())
+        cols, sequences, frames = self.chain.log.download(*wanted)          # the one download: every column the report is made of
+        size = self.out_size or (0, 0)
+        inst = trk = None
+        try:
+            if joined:
+                inst = InstanceReport.from_rows(cols["rows"], cols["total"], size, self.min_area, names, frames, sequences)
+                if self.tracks:
+                    trk = TrackReport.from_ids(inst, cols["ids"], cols["started"])
+            return ClearanceReport(cols["clearance"], size, names, frames, sequences, inst, trk)
+        except ValueError as e:
+            raise StswinHipError(f"clearance_report: {e}") from e
 
     def instance_report(self, names: Optional[Sequence[str]] = None):
         """report="deferred" with instances=K: one download of the instance log -> utils.instruments.InstanceReport (min_area as given

@@ -1,5 +1,5 @@
 """What a VideoSegmenter makes of its label maps beside the result (its docstring states the keywords): the chain moments -> instances
--> tracks -> masks -> confidence -> parts with its buffers (ReportChain), its record (Yield), the tracker's frame order (TrackSequencer) and the device log;
+-> tracks -> masks -> confidence -> parts -> clearance with its buffers (ReportChain), its record (Yield), the tracker's frame order (TrackSequencer) and the device log;
 and what it does to them before anything reads them: the cleaning of clean_area (LabelCleaner) and its report (CleanReport)."""
 from __future__ import annotations
 
@@ -137,22 +137,24 @@ class LabelCleaner:
         return CleanReport(cols["stats"], frames, sequences, self.max_small)
 
 
-class Yield(namedtuple("Yield", "moments rows total ids started runs count conf class_sums instance_sums parts contacts",
-                       defaults=(None,) * 12)):
+class Yield(namedtuple("Yield", "moments rows total ids started runs count conf class_sums instance_sums parts contacts clearance",
+                       defaults=(None,) * 13)):
     """What the labels [B][*out_size] of a step (or of one clip, B = 1) yield on the device: moments int64 [B][nc][10]; with instances
     rows int64 [B][K][12] and total int32 [B]; once tracked ids int32 [B][K] and started int32 [B][1]; with masks runs int32
     [B][cap][2] and count int32 [B]; with confidence conf uint8 [B][*out_size], class_sums int64 [B][nc][3] and, with instances,
-    instance_sums int64 [B][K][3]; with parts parts int64 [B][K][nc][10] and contacts int64 [B][K][nc].  Absent fields are None."""
+    instance_sums int64 [B][K][3]; with parts parts int64 [B][K][nc][10] and contacts int64 [B][K][nc]; with clearance clearance int64 [B][K][nc][3].  Absent fields are
+    None."""
     __slots__ = ()
 
     def clip(self, b: int) -> "Yield":
         """Clip b's part [1][...]."""
         return Yield(*(None if t is None else t[b:b + 1] for t in self))
 
-    def appended(self, result, report: bool = True, masks: bool = False, confidence: bool = False, parts: bool = False):
+    def appended(self, result, report: bool = True, masks: bool = False, confidence: bool = False, parts: bool = False,
+                 clearance: bool = False):
         """report="frame": a clip's result r -> r + (moments, rows, total, ids), what there is of them; masks="frame": then
-        + (runs, count); confidence="frame": then + (conf, class_sums[, instance_sums]); parts="frame": then + (parts, contacts); all
-        on the device."""
+        + (runs, count); confidence="frame": then + (conf, class_sums[, instance_sums]); parts="frame": then + (parts, contacts);
+        clearance="frame": then + (clearance,); all on the device."""
         extra = tuple(t[0] for t in self[:4] if t is not None) if report else ()
         if masks:
             extra += (self.runs[0], self.count[0])
@@ -160,11 +162,13 @@ class Yield(namedtuple("Yield", "moments rows total ids started runs count conf 
             extra += tuple(t[0] for t in (self.conf, self.class_sums, self.instance_sums) if t is not None)
         if parts:
             extra += (self.parts[0], self.contacts[0])
+        if clearance:
+            extra += (self.clearance[0],)
         return result + extra if isinstance(result, tuple) else (result,) + extra
 
     def logged(self, log: DeviceLog, frame: int, tracked: bool = True, report: bool = True, masks: bool = False,
-               confidence: bool = False, parts: bool = False) -> int:
-        """report="deferred", masks="deferred", confidence="deferred" and / or parts="deferred": a clip's row in the log -> its index
+               confidence: bool = False, parts: bool = False, clearance: bool = False) -> int:
+        """report="deferred", masks="deferred", confidence="deferred", parts="deferred" and / or clearance="deferred": a clip's row in the log -> its index
         (tracked = False: ids and started are written when it is tracked); the columns of what is not deferred are left alone.  Of the
         confidence the sums are logged, not the map."""
         values = dict(moments=self.moments, rows=self.rows, total=self.total, ids=self.ids if tracked else None,
@@ -175,6 +179,8 @@ class Yield(namedtuple("Yield", "moments rows total ids started runs count conf 
             values.update(class_sums=self.class_sums, instance_sums=self.instance_sums)
         if parts:
             values.update(parts=self.parts, contacts=self.contacts)
+        if clearance:
+            values.update(clearance=self.clearance)
         return log.append(frame, **values)
 
 
@@ -209,8 +215,8 @@ class ReportChain:
     """report / instances / tracks / masks / confidence of a VideoSegmenter: hip.label_moments, then the launches of
     hip.label_components, then those of hip.track_instances, then those of hip.rle_encode (on the component map with instances, else on
     the labels), then hip.upsample_confidence on the logits the labels came from and hip.confidence_sums over the labels (and over
-    the component map with instances), then hip.instance_parts over the labels and the component map, on every label map the segmenter
-    makes.  With instance_groups the component launches read the grouped labels, which hip.gt_decode makes of the labels with the
+    the component map with instances), then hip.instance_parts and hip.instance_clearance over the labels and the component map, on every
+    label map the segmenter makes.  With instance_groups the component launches read the grouped labels, which hip.gt_decode makes of the labels with the
     persistent table of utils.instruments.group_table; everything else reads the labels themselves.  The segmenter calls labelled() where a step's labels exist and
     released() where its frames are handed out (step_is_steady() is the check in front of the graph's steady step, which tracks inside
     itself).  Owns what persists across steps: the component map, the grouped labels and the workspaces (they only grow; the ones they replaced are kept, a
@@ -218,7 +224,27 @@ class ReportChain:
 
     def __init__(self, device, classes: int, protocol: str, out: str, report, min_area, instances, connectivity, instance_skip, tracks,
                  track_iou, track_same_class, masks=None, mask_runs=16384, track_max_gap=0, confidence=None, confidence_low=128,
-                 align_corners=True, parts=None, instance_groups=None):
+                 align_corners=True, parts=None, instance_groups=None, clearance=None, clearance_to=None, clearance_max=None):
+        if clearance not in (None, "frame", "deferred"):
+            raise StswinHipError(f"clearance must be None, 'frame' or 'deferred', got {clearance!r}")
+        if clearance is None and (clearance_to is not None or clearance_max is not None):
+            raise StswinHipError("clearance_to and clearance_max belong to clearance='frame' or 'deferred'")
+        if clearance is not None and out == "logits":
+            raise StswinHipError("clearance belongs to out='labels' and out='overlay' (the distances are taken over the label map)")
+        if clearance is not None and instances is None:
+            raise StswinHipError("clearance says how near the instances come to what they do not touch: it needs instances=K")
+        if clearance is not None:
+            if not 1 <= classes <= 64:
+                raise StswinHipError(f"clearance: the model has {classes} classes, hip.instance_clearance takes 1 .. 64")
+            if clearance_to is not None:
+                try:
+                    clearance_to = tuple(clearance_to)
+                except TypeError:
+                    clearance_to = (clearance_to,)
+                if any(isinstance(c, bool) or not isinstance(c, int) or not 0 <= c < classes for c in clearance_to):
+                    raise StswinHipError(f"clearance_to holds classes 0 .. {classes - 1}, got {clearance_to!r}")
+            if clearance_max is not None and (isinstance(clearance_max, bool) or not isinstance(clearance_max, int) or clearance_max < 0):
+                raise StswinHipError(f"clearance_max must be None or an int >= 0 (pixels), got {clearance_max!r}")
         if parts not in (None, "frame", "deferred"):
             raise StswinHipError(f"parts must be None, 'frame' or 'deferred', got {parts!r}")
         if parts is not None and out == "logits":
@@ -292,6 +318,8 @@ class ReportChain:
         self.device, self.classes, self.report, self.min_area = device, classes, report, min_area
         self.confidence, self.confidence_low, self.align_corners = confidence, confidence_low, bool(align_corners)
         self.parts, self.instance_groups = parts, instance_groups
+        self.clearance, self.clearance_to, self.clearance_max = clearance, clearance_to, clearance_max
+        self.clr_ws = None                    # clearance: the workspace (retired ones go where the component map's do)
         self.group_table = self.grouped = None        # instance_groups: the class -> representative table (persistent: a captured graph
         if instance_groups is not None:               # reads it) and the grouped labels, a buffer that only grows, as cc_map does
             from .utils.instruments import group_table
@@ -316,7 +344,8 @@ class ReportChain:
                              dict(class_sums=((classes, 3), torch.int64)) if confidence == "deferred" else {},
                              dict(instance_sums=((instances, 3), torch.int64)) if confidence == "deferred" and instances is not None else {},
                              dict(parts=((instances, classes, 10), torch.int64), contacts=((instances, classes), torch.int64))
-                             if parts == "deferred" else {})
+                             if parts == "deferred" else {},
+                             dict(clearance=((instances, classes, 3), torch.int64)) if clearance == "deferred" else {})
 
     def reset(self) -> None:
         """The sequence ends: its ordinal in the log, ids restart at 0 (a fill kernel on the stream), what is parked is dropped."""
@@ -335,7 +364,7 @@ class ReportChain:
         until the next clip's labels) or in the graph's steady step (`steady`: one frame, in frame order); released() tracks the rest.
         The encoder's launches come last: they need nothing from the tracker, so a frame that is parked is encoded here, before the
         next clip's components overwrite the map.  So do the confidence launches, on the `logits` [B][nc][h][w] the labels were made
-        from: the map, its sums over the labels and, with instances, over the component map.  And so does the parts launch, on the
+        from: the map, its sums over the labels and, with instances, over the component map.  And so do the parts launch and the clearance launches, on the
         labels (ungrouped) and the component map."""
         if self.report is None and self.masks is None and self.confidence is None:
             return None
@@ -369,6 +398,10 @@ class ReportChain:
             B, H, W = labels.shape
             pt, ct = hip.instance_parts(labels, self.cc_map[:B * H * W].view(B, H, W), self.instances, self.classes)
             ys = [c._replace(parts=pt[b:b + 1], contacts=ct[b:b + 1]) for b, c in enumerate(ys)]
+        if self.clearance is not None:
+            B, H, W = labels.shape
+            cl = self._clearance(labels, self.cc_map[:B * H * W].view(B, H, W))
+            ys = [c._replace(clearance=cl[b:b + 1]) for b, c in enumerate(ys)]
         return ys
 
     def released(self, frames: Sequence[int], results: list, ys: Optional[List[Yield]]) -> list:
@@ -379,13 +412,13 @@ class ReportChain:
             return results
         if self.tracks:
             ys = [y if y.ids is not None else self._track(g, b, y) for b, (g, y) in enumerate(zip(frames, ys))]
-        if "frame" in (self.report, self.masks, self.confidence, self.parts):
-            results = [y.appended(r, self.report == "frame", self.masks == "frame", self.confidence == "frame", self.parts == "frame")
-                       for r, y in zip(results, ys)]
-        if "deferred" in (self.report, self.masks, self.confidence, self.parts):
+        if "frame" in (self.report, self.masks, self.confidence, self.parts, self.clearance):
+            results = [y.appended(r, self.report == "frame", self.masks == "frame", self.confidence == "frame", self.parts == "frame",
+                                  self.clearance == "frame") for r, y in zip(results, ys)]
+        if "deferred" in (self.report, self.masks, self.confidence, self.parts, self.clearance):
             for g, y in zip(frames, ys):
                 row = y.logged(self.log, g, g not in self.parked, self.report == "deferred", self.masks == "deferred",
-                               self.confidence == "deferred", self.parts == "deferred")
+                               self.confidence == "deferred", self.parts == "deferred", self.clearance == "deferred")
                 if g in self.parked and self.report == "deferred":
                     self.parked[g].log_row = row
         return results
@@ -434,6 +467,18 @@ class ReportChain:
         runs = torch.empty(maps.shape[0], self.mask_runs, 2, dtype=torch.int32, device=self.device)
         count = torch.empty(maps.shape[0], dtype=torch.int32, device=self.device)
         return hip.rle_encode(maps, self.mask_runs, out=(runs, count), workspace=self.rle_ws)
+
+    def _clearance(self, labels: torch.Tensor, components: torch.Tensor) -> torch.Tensor:
+        """clearance int64 [B][K][nc][3] of labels and components [B][H][W].  The workspace only ever grows, as the component launches'
+        does; the result is fresh per step (under capture: the graph's)."""
+        need = hip.instance_clearance_scratch(*labels.shape, self.classes, self.instances)
+        if self.clr_ws is None or self.clr_ws.numel() < need:
+            if self.clr_ws is not None:
+                self.cc_retired.append(self.clr_ws)
+            self.clr_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        out = torch.empty(labels.shape[0], self.instances, self.classes, 3, dtype=torch.int64, device=self.device)
+        return hip.instance_clearance(labels, components, self.instances, self.classes, self.clearance_to, self.clearance_max, out=out,
+                                      workspace=self.clr_ws)
 
     def _track(self, frame: int, b: int, y: Yield) -> Yield:
         """y with the ids [1][K] and started [1][1] of released frame `frame`, whose components clip b of the map holds.  A frame the
