@@ -293,7 +293,12 @@ int stswin_tuning_build(void);
  * slabs in a fixed order behind the launch boundary, so a training step gives the same bits every time it runs.  The `scratch`
  * arguments below are that space: uninitialised fp32, at least stswin_<entry>_scratch(...) floats, 16-byte aligned, private to the
  * call until the next kernel on the stream has run (one buffer per stream can serve every call).
- *   out_s[b*obs + j] (+)= sum_{p < nslabs} ws[b*ws_batch_stride + p*slab_stride + s*seg_len + j],  s < nseg <= 3, j < seg_len */
+ *   out_s[b*obs + j] (+)= sum_{p < nslabs} ws[b*ws_batch_stride + p*slab_stride + s*seg_len + j],  s < nseg <= 3, j < seg_len
+ * The kernel loads and stores float4: ws, every non-NULL out_s and - in bytes - slab_stride, ws_batch_stride and out_batch_stride (obs) must
+ * be 16-byte aligned, seg_len a multiple of 4 (-1110 where a length or a stride is not; the pointers are the caller's to keep aligned).  A NULL
+ * out_s skips segment s.  nseg > 3: -1110; nseg <= 0, seg_len <= 0, nslabs <= 0 or batch <= 0: 0, nothing is written.  The association of the
+ * sum depends on nslabs alone: 16 slab lanes (64 from nslabs = 96) each add every 16th (64th) slab in order, the lane sums are added in lane
+ * order - the same bits whether the fold is launched at once or queued (below). */
 int stswin_slab_fold(const float* ws, long slab_stride, long ws_batch_stride, int nslabs, int seg_len, int nseg, float* out0, float* out1,
                      float* out2, long out_batch_stride, int batch, int accumulate, void* stream);
 
@@ -308,13 +313,19 @@ long stswin_colsum_scratch(int M, int N);
 int stswin_colsum(int dtype, const void* y, long ldy, float* out, int M, int N, float* scratch, void* stream);
 
 /* ---- nn.LayerNorm (swin_512.py:160,166 norm1/norm2; :253,:274 PatchMerging.norm with the 2x2 gather fused:
- * row r = concat_s x[rows[s][r]][0:Cseg]).  mean/rstd (fp32 [M]) are saved for the backward. */
+ * row r = concat_s x[rows[s][r]][0:Cseg]).  mean/rstd (fp32 [M]) are saved for the backward; mean == NULL: neither is written.
+ * A row lives in registers, 16 bytes per lane and piece.  Largest C = S*Cseg (beyond it -1104, or -1106 where the backward's (waves + 1) x C
+ * fp32 LDS table would pass 64 KiB):      forward   bf16 8192   fp32 4096        backward   bf16 3272   fp32 2048
+ * Cseg and every pitch must be a multiple of 16 bytes' worth of elements (8 bf16 / 4 fp32): -1105.  A NULL scratch: -1111. */
 int stswin_layernorm_fwd(int dtype, const void* x, long ldx, const int* rows, int S, int Cseg, void* y, long ldy,
                          const float* gamma, const float* beta, float* mean, float* rstd, int M, float eps, void* stream);
 int stswin_layernorm_bwd(int dtype, const void* dy, long lddy, const void* x, long ldx, const int* rows, int S, int Cseg,
                          const float* gamma, const float* mean, const float* rstd, void* dx, long lddx, float* dgamma,
                          float* dbeta, int M, int accumulate_dx,
-                         float* dxsum /* optional fp32 [S*Cseg]: += column sums of the dx written */,
+                         float* dxsum /* optional fp32 [S*Cseg]: += column sums of dx (in the layout of dy: column s*Cseg + c of row r is
+                                         what goes to dx[rows[s][r]][c]) taken from the fp32 values BEFORE they are rounded to the output type -
+                                         with accumulate_dx, old + LN'(dy) in fp32.  In bf16 this is NOT the sum of the stored values: it is
+                                         the better bias gradient of the Linear that produced x. */,
                          float* scratch /* >= stswin_layernorm_bwd_scratch(M, S*Cseg) floats: one [3][S*Cseg] slab (dgamma | dbeta |
                                            dxsum partial sums) per workgroup; folded into dgamma / dbeta / dxsum (+=) in slab order */,
                          void* stream);

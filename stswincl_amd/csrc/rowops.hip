@@ -673,7 +673,7 @@ __global__ __launch_bounds__(NW * 64) void ln_bwd_kernel(const T* dy, long lddy,
   };
   fold(dg, rep);
   fold(db, rep + C);
-  if constexpr (DXS) fold(ds, rep + 2 * C);     // column sums of the written dx (= the bias gradient of the Linear that produced x)
+  if constexpr (DXS) fold(ds, rep + 2 * C);     // column sums of dx before its rounding to T (= the bias gradient of the Linear that produced x)
 }
 
 // part[blockIdx.y][n] = sum of rows [blockIdx.y * rows_per_block, ...) of Y[:, n]   (bias gradients; slab_fold_kernel adds the

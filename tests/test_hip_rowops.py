@@ -109,7 +109,7 @@ def test_layernorm_bwd_accumulate_and_column_sums(dtype, m, c, acc, dxs):
     lim = 2e-4 * m if dtype == torch.float32 else 0.05 * m ** 0.5
     assert torch.allclose(dg, gr.grad, atol=lim, rtol=1e-3) and torch.allclose(db, br.grad, atol=lim, rtol=1e-3)
     if dxs:
-        assert torch.allclose(cs, dx.float().sum(0), atol=lim, rtol=2e-3)      # sums of the values as written (rounded to the output type)
+        assert torch.allclose(cs, dx.float().sum(0), atol=lim, rtol=2e-3)      # the kernel sums the fp32 values before they are rounded to the output type (include/stswin_hip.h); the rounded ones are within lim
     if acc:      # the same sum with the accumulated-into tensor as a separate read-only operand (stswin_layernorm_bwd_add): same bits
         dg2, db2 = torch.zeros(c, device="cuda"), torch.zeros(c, device="cuda")
         cs2 = torch.zeros(c, device="cuda") if dxs else None
