@@ -566,8 +566,10 @@ int stswin_pair_loss_bwd(const float* pos, const float* all, const float* cnt, c
                          float* dpos, float* dneg, void* stream);
 
 /* ---- f4: inference post-processing (seg18/test.py:153-158 + utils/EndoMetric.py): labels[f][y][x] = argmax_c of the
- * bilinear (align_corners = True) resize of NCHW logits [F][nc][h][w] to (H, W); with gt (int64 [F][H][W]) also
- * counts[f][0|1|2][c] = |gt == c|, |pred == c|, |gt == c and pred == c|  (int32, zeroed by the caller). */
+ * bilinear (align_corners = True) resize of NCHW logits [F][nc][h][w] (nc <= 64) to (H, W); the first maximum wins.  With gt (int64
+ * [F][H][W]) also counts[f][0|1|2][c] += |gt == c|, |pred == c|, |gt == c and pred == c| for c < nc (int32, zeroed by the caller).  gt
+ * is compared as int64: a value outside 0 .. nc-1, 2^32 + 3 included, is no class, as for the two entries that count below.
+ * Errors (nothing is launched): -1406 nc outside 1 .. 64; frames, h, w, H or W <= 0; logits or labels NULL; gt without counts. */
 int stswin_upsample_argmax(int dtype, const void* logits, unsigned char* labels, const long* gt, int* counts, int frames,
                            int nc, int h, int w, int H, int W, void* stream);
 /* ---- CaDIS evaluation (segcata/cata_test.py:115-170 + utils/cata_metrics.py ConfusionMatrix): labels[f][y][x] = argmax_c of the
@@ -575,7 +577,9 @@ int stswin_upsample_argmax(int dtype, const void* logits, unsigned char* labels,
  * (cata_test.py:129: src = max((in / out) (dst + 0.5) - 0.5, 0)); first maximum wins.  labels may be NULL (not written).  With gt
  * (int64 [F][H][W]) and cm (uint64 [ncm][ncm], ncm <= 64) every pixel with 0 <= gt < ncm and 0 <= label < ncm adds 1 to
  * cm[gt][label] (rows gt, columns prediction, as the reference's `num_classes * gt + pred`).  The matrix is accumulated, never
- * cleared: the caller zeroes it once per evaluation.  Integer atomics only (exact, independent of order). */
+ * cleared: the caller zeroes it once per evaluation.  gt is compared as int64.  Integer atomics only (exact, independent of order).
+ * Errors (nothing is launched): -1406 nc outside 1 .. 64, or frames, h, w, H or W <= 0; -1407 logits NULL; -1408 gt without cm, cm
+ * without gt, or (with both) ncm outside 1 .. 64; -1409 neither cm nor labels. */
 int stswin_upsample_argmax_cm(int dtype, const void* logits, unsigned char* labels, const long* gt, unsigned long long* cm, int ncm,
                               int align_corners, int frames, int nc, int h, int w, int H, int W, void* stream);
 /* ---- colour overlay of a label map (stswincl_amd/utils/visualize.py, VideoSegmenter(out="overlay")): labels uint8 [n][H][W],

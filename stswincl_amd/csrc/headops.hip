@@ -1023,10 +1023,10 @@ __global__ __launch_bounds__(256) void upsample_argmax_kernel(const TL* logits, 
     }
     labels[(long)f * per_frame + px] = (unsigned char)arg;
     if (gt) {
-      const int g = (int)gt[(long)f * per_frame + px];
-      if (g >= 0 && g < 64) atomicAdd(&hist[g], 1);
+      const long g = gt[(long)f * per_frame + px];          // compared as int64: 2^32 + 3 is no class, as in the two kernels below
+      if (g >= 0 && g < 64) atomicAdd(&hist[(int)g], 1);
       atomicAdd(&hist[64 + arg], 1);
-      if (g == arg) atomicAdd(&hist[128 + arg], 1);
+      if (g == (long)arg) atomicAdd(&hist[128 + arg], 1);
     }
   }
   if (gt) {
@@ -1040,7 +1040,8 @@ __global__ __launch_bounds__(256) void upsample_argmax_kernel(const TL* logits, 
 
 extern "C" int stswin_upsample_argmax(int dtype, const void* logits, unsigned char* labels, const long* gt, int* counts,
                                       int frames, int nc, int h, int w, int H, int W, void* stream) {
-  if (nc <= 0 || nc > 64) return -1406;
+  if (nc <= 0 || nc > 64 || frames <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0) return -1406;
+  if (logits == nullptr || labels == nullptr || (gt != nullptr && counts == nullptr)) return -1406;
   const long bpf = ((long)H * W + 255) / 256;
   dim3 grid((unsigned)(bpf * frames));
   hipStream_t st = (hipStream_t)stream;

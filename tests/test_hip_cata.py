@@ -7,6 +7,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import labels_ref
 import pil_resize_ref as R
 from stswincl_amd import hip, video
 from stswincl_amd.net.Ours.base_cata_np import TswinPlusv5
@@ -47,6 +48,7 @@ def test_kernel_matches_torch_and_counts_its_own_labels(dtype, nc, align, h, w, 
     differ = (labels.long() != want).float().mean().item()
     print(f"[cata] {dtype} nc {nc} align {align} {h}x{w}->{H}x{W}: {differ:.2e} of labels differ from torch")
     assert differ < TIE_BOUND
+    assert labels_ref.outside(logits, labels, H, W, int(align))[0] == 0      # every label is one its float64 values allow
     assert torch.equal(cm, _bincount(gt, labels, ncm))
     assert int(cm.sum()) > 0
     # the same matrix without the label write, and the label-only form

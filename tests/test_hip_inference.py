@@ -4,6 +4,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import labels_ref
 from stswincl_amd.utils import EndoMetric as E
 
 pytestmark = pytest.mark.gpu
@@ -21,6 +22,7 @@ def test_predict_and_score_matches_reference_formulation(dtype):
     lab = labels.cpu().long()
     mism = (lab != ref)
     assert float(mism.float().mean()) < 2e-4          # only exact near-ties may differ (interpolation rounding)
+    assert labels_ref.outside(logits.cuda(), labels, H, W, 1)[0] == 0       # and every label is one its float64 values allow
     for i in range(f):
         rd = E.general_dice(gt[i].numpy(), lab[i].numpy())
         rj = E.general_jaccard(gt[i].numpy(), lab[i].numpy())
